@@ -17,20 +17,26 @@ a miss anywhere repeats the call without the prior on every rank) -- `first_boun
 calls, the speculative ones and the repeats.  The tail is query-sharded: ONE
 all_to_all carries the per-shard lists of a rank's rows to it, the canonical merge, value gathers, last hop and decoder
 run on B/G rows, and one all_gather of the [n, C] outputs completes the step (ragraph_amd/sharded.py,
-RAGraph._forward_key_shard); values / labels are replicated (1 GB), the cheap GNN part runs on every rank.  The other
-layout (bank replicated, QUERY batch split, no data-path collective) is timed right after and reported as
-`query_sharded`; `--shard queries` makes it the headline instead.  `--backend gloo` runs the same job over gloo (device
+RAGraph._forward_key_shard); values / labels are replicated (1 GB), the cheap GNN part runs on every rank.  With `--full`
+the other layout (bank replicated, QUERY batch split, no data-path collective) is timed right after and reported as
+`query_sharded`, and one more step times every collective (`collectives_per_step`); `--shard queries` makes the other
+layout the headline instead.  `--backend gloo` runs the same job over gloo (device
 tensors staged through the host: two ranks on ONE GPU, tests/test_gpu_two_rank.py).
 
 The steps cycle `--batches` (8) DISTINCT feature tensors (seeds 4321, 4322, ...: same distribution) through warm-up and the
 timed region, so the filtered call's learnt first bound meets queries it has not seen; `first_bound` reports the prior each
 timed step ran under and the queries its verify launch had to scan (`repeated_batch`: round 5's one-batch replay, secondary).
 
-After the timed region (outside it) the LAST timed batch's retrieval is CHECKED: 1024 evenly spaced queries are re-scored on
-the exact fp32 kernel (same indices and score bits required) and 4 of them against the CPU oracle (`verified`).
+A plain run sets up, warms up, times the steps, writes the last timed step's output when `--dump-outputs DIR` is given
+(DIR/class_probs.npy) and prints its line; everything below that takes runs or checks of its own needs `--full`.
+
+With `--full`, after the timed region (outside it) the LAST timed batch's retrieval is CHECKED: 1024 evenly spaced queries
+are re-scored on the exact fp32 kernel (same indices and score bits required) and 4 of them against the CPU oracle
+(`verified`).
 
 Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` for the dominant kernel (the bf16 MFMA
-filter of the exact top-k) and, at N = 1, next to the timed region: `retrieval_small_batch` (the reference's real batch
+filter of the exact top-k, from events recorded in the timed steps themselves) and, with `--full` at N = 1, next to the
+timed region: `retrieval_small_batch` (the reference's real batch
 sizes, B = 1 / 16 / 256 / 512 / 4096, HBM-bound up to a few hundred queries), `exact_fp32` (the same step on the fp32
 MFMA kernels alone), `gnn_fwd` (the metric's second half: GNN-forward nodes/s with SURVEY 8(d)'s byte model, the counter
 bytes of the same kernels, the CPU port's rate and a graph with structure), `configs` (c1, c3, few-shot, the c5-shaped
@@ -61,6 +67,7 @@ BF16_MFMA_PEAK_TFLOPS = 2516.6  # MI355X_MICROARCH.md: ~2.5 PF dense = 1024 flop
 INT8_MFMA_PEAK_TOPS = 5033.2    # same guide, Matrix cores: I8 "the cycles of the BF16 form at 2x the K, so 2x BF16 per clock"
 HBM_PEAK_GBS = 8000.0           # spec; ~6300 achievable
 VERIFY_ROWS = 1024              # rows of the timed path re-scored on the exact fp32 kernel after the timed region
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: at most this much; a larger output is written as a fixed sample of its rows
 TRAFFIC_JSON = next((p for p in (os.path.join(ROOT, "profiles", f"r{r}_pmc_traffic.json") for r in (6, 5, 4)) if os.path.exists(p)),
                     os.path.join(ROOT, "profiles", "r5_pmc_traffic.json"))
 
@@ -100,7 +107,17 @@ def parse():
                          "the host; lets several ranks share one GPU for a functional check)")
     ap.add_argument("--exact-fp32", action="store_true",
                     help="retrieve with the fp32 MFMA kernel only (no bf16 filter) in the timed region")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the checks and the other measurements: the verification of the timed "
+                         "retrieval, the CPU baseline, the other sizes, configs and precisions, the other layouts (N > 1) and "
+                         "the collective timing step; without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (the forward's [n, C] float32 class probabilities) to "
+                         "DIR/class_probs.npy; past 64 MB a fixed seeded sample of its rows")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 class EventTimer:
@@ -660,6 +677,21 @@ def _group_prior_report(model):
             "phase0_exchanges": getattr(tgb, "exchange_count", {}).get(0, 0)}
 
 
+def dump_outputs(out, dirname):
+    """--dump-outputs: the last timed step's output -- what a caller of the forward receives, [n, C] class probabilities --
+    as DIR/class_probs.npy in float32.  Past DUMP_MAX_BYTES, rows drawn once by a fixed seed (ascending), the same rows on
+    every run of the same arguments."""
+    import numpy as np
+
+    a = out.detach().float().cpu().numpy()
+    a = a.reshape(a.shape[0], -1)
+    if a.nbytes > DUMP_MAX_BYTES:
+        rows = DUMP_MAX_BYTES // (a.itemsize * a.shape[1])
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "class_probs.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def timed_steps(step, steps, world, dev, on_step=None):
     """Exactly `steps` forwards between barrier + synchronize on both sides; MAX over ranks."""
     if world > 1:
@@ -784,8 +816,10 @@ def main():
     beat("timed steps")
     elapsed, out = timed_steps(step, args.steps, world, dev, grab_filter_ms)
     topk_timer.enabled = filt_timer.enabled = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
     collectives = None
-    if world > 1 or force_dist:
+    if args.full and (world > 1 or force_dist):
         # what its collectives cost: one more step OUTSIDE the timed region with every collective of ragraph_amd.sharded
         # bracketed by events on the stream it is ordered on (what the process group is: `ranks_seen`, the pre-flight above)
         from ragraph_amd import sharded as SH
@@ -804,7 +838,7 @@ def main():
     cand_levels = K.filter_stats_levels(last[3].cpu().tolist()) if last is not None else []
     assert torch.isfinite(out).all()
     verified = None
-    if args.emulate_rank_of <= 1 and not args.exact_fp32 and not args.no_extras:
+    if args.full and args.emulate_rank_of <= 1 and not args.exact_fp32 and not args.no_extras:
         # (every rank: the sharded check has collectives; profiling runs -- --no-extras -- keep their kernel lists clean)
         verified = verify_retrieval(model, feats_all[(step_no[0] - 1) % nb], adj, args, world,
                                     with_oracle=(rank == 0 and world == 1 and not args.no_cpu_baseline))
@@ -945,11 +979,12 @@ def main():
         result["first_bound"]["group"] = gp
     if ranks_seen is not None:
         result["ranks_seen"] = ranks_seen
-        result["collectives_per_step"] = collectives
+        if collectives is not None:
+            result["collectives_per_step"] = collectives
     if args.emulate_rank_of > 1:
         result["emulated"] = (f"rank 0 of a {args.emulate_rank_of}-GPU job ({args.shard}-sharded), collectives replaced by "
                               f"their local part: value is NOT a job throughput")
-    extras = not args.no_extras and args.emulate_rank_of <= 1
+    extras = args.full and not args.no_extras and args.emulate_rank_of <= 1
     if world > 1 and extras:
         # the other layouts, right after (every rank must take part): bank replicated + query batch split, and -- from 4
         # ranks -- query groups x key shards

@@ -23,16 +23,11 @@ def pytest_collection_modifyitems(session, config, items):
 _two_rank = None
 
 
-def pytest_collection_finish(session):
-    """tests/test_gpu_two_rank.py: its two worker processes must be started before THIS process initialises the GPU
-    (collection imports the test modules but runs no kernel).  Only when that test is among the collected (not
-    deselected) items and a device node exists -- /dev/kfd: probing through torch could initialise HIP in this
-    process on builds without amdsmi.  The workers run beside the other tests and the test collects their reports."""
-    global _two_rank
-    if _two_rank is not None or os.environ.get("RAGRAPH_SKIP_TWO_RANK") == "1":
-        return
-    if not any("test_gpu_two_rank" in item.nodeid for item in session.items) or not os.path.exists("/dev/kfd"):
-        return
+HYBRID_WAIT_S = 900   # the four hybrid ranks' whole run, waited for before any test starts
+
+
+def _start_ranks(worker, world, prefix):
+    """`world` processes of tests/<worker> (RANK WORLD PORT OUT), each logging to OUT/rank<r>.log."""
     import socket
     import subprocess
     import tempfile
@@ -40,21 +35,42 @@ def pytest_collection_finish(session):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    out = tempfile.mkdtemp(prefix="ragraph_two_rank_")
-    worker = os.path.join(ROOT, "tests", "two_rank_worker.py")
+    out = tempfile.mkdtemp(prefix=prefix)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    logs = [open(os.path.join(out, f"rank{r}.log"), "w") for r in range(2)]
-    procs = [subprocess.Popen([sys.executable, worker, str(r), "2", str(port), out], env=env, stdout=logs[r],
-                              stderr=subprocess.STDOUT) for r in range(2)]
-    # ... and the four ranks of the hybrid layout (2 query groups x 2 key shards): tests/hybrid_worker.py
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port4 = s.getsockname()[1]
-    out4 = tempfile.mkdtemp(prefix="ragraph_hybrid_")
-    worker4 = os.path.join(ROOT, "tests", "hybrid_worker.py")
-    logs4 = [open(os.path.join(out4, f"rank{r}.log"), "w") for r in range(4)]
-    procs4 = [subprocess.Popen([sys.executable, worker4, str(r), "4", str(port4), out4], env=env, stdout=logs4[r],
-                               stderr=subprocess.STDOUT) for r in range(4)]
+    logs = [open(os.path.join(out, f"rank{r}.log"), "w") for r in range(world)]
+    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", worker), str(r), str(world), str(port), out],
+                              env=env, stdout=logs[r], stderr=subprocess.STDOUT) for r in range(world)]
+    return procs, out, logs
+
+
+def pytest_collection_finish(session):
+    """tests/test_gpu_two_rank.py: its worker processes must be started before THIS process initialises the GPU
+    (collection imports the test modules but runs no kernel).  Only when that test is among the collected (not
+    deselected) items and a device node exists -- /dev/kfd: probing through torch could initialise HIP in this
+    process on builds without amdsmi.  The four ranks of the hybrid layout (2 query groups x 2 key shards:
+    tests/hybrid_worker.py) run first and are waited for here; then the two ranks of tests/two_rank_worker.py start and
+    run beside the other tests.  So at most four processes have the GPU open at once (the hybrid ranks; later this
+    process, the two ranks and a child process a test starts), and the tests collect the reports."""
+    global _two_rank
+    if _two_rank is not None or os.environ.get("RAGRAPH_SKIP_TWO_RANK") == "1":
+        return
+    if not any("test_gpu_two_rank" in item.nodeid for item in session.items) or not os.path.exists("/dev/kfd"):
+        return
+    import subprocess
+    import time
+
+    procs4, out4, logs4 = _start_ranks("hybrid_worker.py", 4, "ragraph_hybrid_")
+    deadline = time.monotonic() + HYBRID_WAIT_S
+    for p in procs4:
+        try:
+            p.wait(timeout=max(deadline - time.monotonic(), 1))
+        except subprocess.TimeoutExpired:   # (its missing report fails test_four_ranks_hybrid_layout)
+            break
+    for p in procs4:
+        if p.poll() is None:
+            p.kill()
+            p.wait()
+    procs, out, logs = _start_ranks("two_rank_worker.py", 2, "ragraph_two_rank_")
     _two_rank = (procs, out, logs, procs4, out4, logs4)
 
 

@@ -1,5 +1,5 @@
 """Host-side pieces of bench.py that need no GPU: the N > 1 watchdog (a rank whose phase stops changing ends the job with
-every rank's last heartbeat on stderr and a non-zero exit code) and the byte models of the GNN block."""
+every rank's last heartbeat on stderr and a non-zero exit code), the byte models of the GNN block and --dump-outputs."""
 import json
 import os
 import subprocess
@@ -39,3 +39,24 @@ def test_gnn_byte_model_matches_survey_8d():
     assert abs(b["hop_ideal"] / 1e9 - 0.214) < 0.002
     assert abs(b["hop_no_reuse"] / 1e9 - 1.23) < 0.02
     assert b["forward_ideal"] == b["encode_ideal"] + 3 * b["hop_ideal"]
+
+
+def test_dump_outputs_caps_the_bytes_with_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: the whole output as float32 when it fits; past the cap, the same seeded rows (ascending) every time."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    out = torch.arange(3000, dtype=torch.float64).reshape(1000, 3)
+    bench.dump_outputs(out, str(tmp_path / "whole"))
+    a = np.load(tmp_path / "whole" / "class_probs.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, out.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1200)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(out, str(tmp_path / d))
+    s1, s2 = np.load(tmp_path / "s1" / "class_probs.npy"), np.load(tmp_path / "s2" / "class_probs.npy")
+    assert s1.nbytes <= 1200 and s1.shape == (100, 3) and np.array_equal(s1, s2)
+    rows = s1[:, 0].astype(np.int64) // 3
+    assert (np.diff(rows) > 0).all() and np.array_equal(s1, a[rows])

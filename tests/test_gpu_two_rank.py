@@ -1,7 +1,8 @@
 """Two real processes on the real HIP library (-m gpu): the key-sharded and the query-sharded forward of RAGraph_node
 under a world-size-2 process group, bit for bit against the single-process result.  The ranks are started by
 tests/conftest.py at session start -- before this pytest process has made any GPU call (a process that has initialised
-the GPU must not fork + exec on the GPU pool) -- and run beside the other tests; this test collects their reports."""
+the GPU must not fork + exec on the GPU pool); the four ranks of the hybrid layout finish before the first test, the two
+ranks run beside the other tests.  These tests collect their reports."""
 import json
 import os
 

@@ -7,8 +7,8 @@ R=$(pwd)
 O=$R/gpurun_out/$tag
 mkdir -p $O
 S="--steps 3 --warmup 1 --nodes 20000 --bank 200000"
-MASTER_PORT=29611 timeout 300 python bench.py --gpus 2 --backend gloo $S > $O/gloo2.json 2> $O/gloo2.err; echo "gloo2 rc=$?"
-MASTER_PORT=29612 timeout 400 python bench.py --gpus 4 --backend gloo --shard hybrid $S > $O/gloo4_hybrid.json 2> $O/gloo4_hybrid.err; echo "gloo4 hybrid rc=$?"
+MASTER_PORT=29611 timeout 300 python bench.py --full --gpus 2 --backend gloo $S > $O/gloo2.json 2> $O/gloo2.err; echo "gloo2 rc=$?"
+MASTER_PORT=29612 timeout 400 python bench.py --full --gpus 4 --backend gloo --shard hybrid $S > $O/gloo4_hybrid.json 2> $O/gloo4_hybrid.err; echo "gloo4 hybrid rc=$?"
 RAGRAPH_BENCH_HANG_RANK=1 MASTER_PORT=29613 timeout 200 python bench.py --gpus 2 --backend gloo --dist-timeout 20 $S > $O/hang.json 2> $O/hang.err; echo "hang rc=$? (expected non-zero)"
 grep -h "ranks_seen\|bench_watchdog" $O/*.err | cut -c1-600
 for sh in keys queries hybrid; do

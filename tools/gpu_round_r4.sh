@@ -6,7 +6,7 @@ tag=${1:-r4}
 R=$(pwd)
 O=$R/gpurun_out/$tag
 mkdir -p $O
-python bench.py --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 $R/bench.py --steps 3 --warmup 1 --no-extras > $O/stats.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o p -- python3 $R/bench.py --steps 2 --warmup 1 --no-extras > $O/pmc_fetch.log 2>&1

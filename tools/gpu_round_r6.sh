@@ -8,7 +8,7 @@ tag=${1:-r6}
 R=$(pwd)
 O=$R/gpurun_out/$tag
 mkdir -p $O
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 python tools/bench_configs.py > $O/configs.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o s -- python3 $R/bench.py --steps 3 --warmup 3 --no-extras > $O/stats.log 2>&1

@@ -6,7 +6,7 @@ tag=${1:-r6m}
 R=$(pwd)
 O=$R/gpurun_out/$tag
 mkdir -p $O
-python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
 one() {  # tag, args...
   t=$1; shift
   python bench.py --no-extras --steps 10 --warmup 5 "$@" 2>$O/$t.err | python -c "
