@@ -653,6 +653,38 @@ int ragraph_binorm_edges_f32(const int64_t* users, const int64_t* items, const i
                              int64_t num_items, int64_t* edges, float* norm, int64_t* times, int64_t* nedges, void* ws,
                              size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * f4  edge (link-prediction) evaluation -- RAGraph_edge/utils/metrics.py:83-141 (Metric.eval), :143-200 (eval_grouped)
+ *
+ * ragraph_topk_dot_masked_f32: metrics.py:104-116 + 210-214 for ALL test users in one call: score(b, i) = U[users[b]] . I[i]
+ *   (no normalisation; the single fmaf chain in natural order of ragraph_linear_f32, hence its bits), every item of query b's
+ *   history hist_items[hist_rowptr[b] .. hist_rowptr[b+1]) scored as mask_value (-1e8 from Python: SCORED, not removed,
+ *   so a user with fewer than k other items gets masked items at mask_value in ascending index order, as _mask_history_pos
+ *   + torch.topk), then the canonical top-k (score descending, index ascending; NaN never selected).
+ *   users [B] int64 row ids into U [n_rows_U, D], or NULL (query b = row b).  Histories may be unsorted and hold
+ *   duplicates.  1 <= k <= min(N, RAGRAPH_TOPK_MAX), any D >= 1.  out_scores [B,k] fp32, out_idx [B,k] int64.
+ *   A history id outside [0, N), a user id outside [0, n_rows_U) or a hist_rowptr that does not run from 0 to nnz
+ *   monotonically returns RAGRAPH_EINVAL before anything is written (one 4-byte read-back per call).
+ *   Dispatch as ragraph_topk_cosine_f32 (same rules, same RAGRAPH_TOPK_SLAB switch): D in {64,128,256} and k <= 32 take the
+ *   fused kernels' masked instantiations, where no [B, N] matrix exists; otherwise ~1 GiB score slabs (dense kernel,
+ *   masked fill of the slab, row top-k).  ws: ragraph_topk_dot_masked_workspace_bytes(B, N, D, k, nnz). */
+size_t ragraph_topk_dot_masked_workspace_bytes(int64_t B, int64_t N, int D, int k, int64_t nnz);
+int ragraph_topk_dot_masked_f32(const float* U, int64_t n_rows_U, const int64_t* users, int64_t B, const float* I, int64_t N,
+                                int D, int k, const int64_t* hist_rowptr, const int64_t* hist_items, int64_t nnz,
+                                float mask_value, float* out_scores, int64_t* out_idx, void* ws, size_t ws_bytes,
+                                void* stream);
+
+/* ragraph_rank_metrics_f64: metrics.py:12-46 (recall, ndcg, precision) + :60-80 (eval_batch) + :131-133 (the batch sums)
+ *   over the ranked lists idx [U, kmax] int64 and the ground truth gt_items[gt_rowptr[u] .. gt_rowptr[u+1]) of user u.
+ *   Hit: idx[u][i] is in the list (duplicates do not count twice); recall_n = the list's raw length; IDCG over
+ *   min(k, length) positions, 0 -> 1; precision = hits / k.  For each k = ks[t] (1 <= k <= kmax, nks <= 16):
+ *   out[0*nks + t] recall, out[1*nks + t] ndcg, out[2*nks + t] precision (device, fp64), each the sum over batches of
+ *   `batch` users (in user order, every batch summed user by user) of batch_sum / U, added batch by batch -- a fixed
+ *   order, so the result is deterministic.  ws: ragraph_rank_metrics_workspace_bytes(U, nks, batch). */
+size_t ragraph_rank_metrics_workspace_bytes(int64_t U, int nks, int64_t batch);
+int ragraph_rank_metrics_f64(const int64_t* idx, int64_t U, int kmax, const int64_t* gt_rowptr, const int64_t* gt_items,
+                             const int* ks, int nks, int64_t batch, double* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

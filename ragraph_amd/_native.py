@@ -128,6 +128,11 @@ SIGNATURES = {
     "ragraph_sample_prob_f32": (_i32, [_vp, _vp, _vp, _i64, _f32, _f32, _vp, _vp]),
     "ragraph_csr_row_sums_f32": (_i32, [_vp, _vp, _i64, _vp, _vp]),
     "ragraph_position_codes_batch_f32": (_i32, [_vp, _i64, _i32, _vp, _i32, _f32, _vp, _vp, _vp]),
+    "ragraph_topk_dot_masked_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i64]),
+    "ragraph_topk_dot_masked_f32": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _f32, _vp, _vp, _vp,
+                                          _sz, _vp]),
+    "ragraph_rank_metrics_workspace_bytes": (_sz, [_i64, _i32, _i64]),
+    "ragraph_rank_metrics_f64": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _sz, _vp]),
 }
 
 

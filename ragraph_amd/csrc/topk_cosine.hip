@@ -71,6 +71,21 @@ __device__ __forceinline__ void list_insert_lane(float* ls, int* li, int k, int 
   li[p * stride] = idx;
 }
 
+// Is key `idx` in query row q's exclusion list (ascending, duplicates allowed)?  Binary search in global memory: it is
+// asked only for candidates that already beat the list's k-th score, a few hundred per query over a whole stream.
+__device__ __forceinline__ bool hist_contains(const int64_t* __restrict__ rp, const int* __restrict__ col, int64_t q,
+                                              int idx) {
+  int64_t lo = rp[q];
+  const int64_t end = rp[q + 1];
+  int64_t hi = end;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (col[mid] < idx) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < end && col[lo] == idx;
+}
+
 struct TopkParams {
   const float* Qn;   // [B,D] normalised queries (big kernel) / RAW queries (small-batch kernel)
   const float* Kn;   // [N,D] normalised keys
@@ -89,6 +104,11 @@ struct TopkParams {
   float* part_s;           // [B][nsplit][k]
   int* part_i;
   const float* thr_init;   // small-batch kernel: per-query lower bound of the k-th best score at [q*k + k-1], or NULL
+  // inner-product top-k with per-query exclusion lists (MASKED instantiations only, ragraph_topk_dot_masked_f32):
+  // query b's excluded keys are hcol[hrp[b] .. hrp[b+1]), ascending; such a key scores mask_value instead of its product
+  const int64_t* hrp;
+  const int* hcol;
+  float mask_value;
   int ablate;              // DIAGNOSTIC ONLY (env RAGRAPH_TOPK_ABLATE, results invalid when non-zero): bit0 skip the
                            // top-k epilogue, bit1 skip global loads + LDS writes, bit2 skip the stage barrier (both
                            // 2-slot variant); DMA ring: bit4 skip the DMA, bit5 skip the FULL / FREE counters
@@ -132,7 +152,7 @@ __device__ unsigned long long g_topk_timing[8];
 #define RG_T(var_)
 #endif
 
-template <int D, int RING>
+template <int D, int RING, bool MASKED = false>
 __global__ void __launch_bounds__(512, 2) topk_stream_kernel(TopkParams p) {
   using C = TopkCfg<D>;
   // ONE __shared__ object; everything below is an offset from it so every access stays a ds_* instruction.
@@ -270,7 +290,10 @@ __global__ void __launch_bounds__(512, 2) topk_stream_kernel(TopkParams p) {
         asm volatile("" ::"v"(m));
         m = RG_NEG_INF;
       }
-      if (__any(m >= thr)) {
+      // MASKED: while the k-th score is still at or below mask_value (list warm-up, or a query with fewer than k
+      // unexcluded keys) every key is a candidate, since an excluded key would enter at mask_value
+      const bool all_cand = MASKED && p.mask_value >= thr;
+      if (__any(m >= thr || all_cand)) {
         // rare path (~k ln(n/k) times per query over the stream): the wave inserts its candidates one at a time with
         // all 64 lanes cooperating on each insert (sorted list: one ballot for the position, one shuffle for the shift).
         const int key_base = (int)(n_begin + (int64_t)s * C::STAGE_KEYS + t * 32) + 4 * h;
@@ -278,8 +301,15 @@ __global__ void __launch_bounds__(512, 2) topk_stream_kernel(TopkParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int idx = key_base + (r & 3) + 8 * (r >> 2);
-          if (acc[r] >= thr && idx < (int)n_end) mask |= 1u << r;
+          if ((acc[r] >= thr || all_cand) && idx < (int)n_end) mask |= 1u << r;
         }
+        // lanes of query row qrow(j) drop candidates the (tightened) threshold excludes
+#define RG_TOPK_PRUNE()                                                                           \
+  do {                                                                                            \
+    if (!(MASKED && p.mask_value >= thr)) {                                                       \
+      _Pragma("unroll") for (int r = 0; r < 16; ++r) if ((mask >> r & 1u) && acc[r] < thr) mask &= ~(1u << r); \
+    }                                                                                             \
+  } while (0)
         unsigned long long pend = __ballot(mask != 0);
         if (__popcll(pend) > 8) {
           // DENSE regime (start of a stream): every lane inserts into its own query's list; the two half-wave lanes of
@@ -292,17 +322,15 @@ __global__ void __launch_bounds__(512, 2) topk_stream_kernel(TopkParams p) {
 #pragma unroll
             for (int r = 1; r < 16; ++r) my_sc = (r0 == r) ? acc[r] : my_sc;
             const int idx = key_base + (r0 & 3) + 8 * (r0 >> 2);
+            if (MASKED && mask != 0 && hist_contains(p.hrp, p.hcol, min(q0 + wave * 32 + j, p.B - 1), idx))
+              my_sc = p.mask_value;
 #pragma unroll 1
             for (int hh = 0; hh < 2; ++hh) {
               if (mask != 0 && h == hh) list_insert_lane(qls, qli, k, 1, my_sc, idx);
             }
             mask &= mask - 1;
             thr = qls[k - 1];
-            if (mask) {
-#pragma unroll
-              for (int r = 0; r < 16; ++r)
-                if ((mask >> r & 1u) && acc[r] < thr) mask &= ~(1u << r);
-            }
+            if (mask) RG_TOPK_PRUNE();
             pend = __ballot(mask != 0);
           }
         }
@@ -312,6 +340,9 @@ __global__ void __launch_bounds__(512, 2) topk_stream_kernel(TopkParams p) {
           float my_sc = acc[0];
 #pragma unroll
           for (int r = 1; r < 16; ++r) my_sc = (r0 == r) ? acc[r] : my_sc;
+          if (MASKED && lane == src &&
+              hist_contains(p.hrp, p.hcol, min(q0 + wave * 32 + j, p.B - 1), key_base + (r0 & 3) + 8 * (r0 >> 2)))
+            my_sc = p.mask_value;
           const float sc = __shfl(my_sc, src);
           const int idx = __shfl(key_base + (r0 & 3) + 8 * (r0 >> 2), src);
           const int qs = src & 31;
@@ -320,13 +351,10 @@ __global__ void __launch_bounds__(512, 2) topk_stream_kernel(TopkParams p) {
           if (j == qs) thr = nthr;  // both half-wave lanes of that query
           if (lane == src) mask &= mask - 1;
           // drop remaining candidates the tightened threshold already excludes (only lanes of query qs can change)
-          if (j == qs && mask) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-              if ((mask >> r & 1u) && acc[r] < thr) mask &= ~(1u << r);
-          }
+          if (j == qs && mask) RG_TOPK_PRUNE();
           pend = __ballot(mask != 0);
         }
+#undef RG_TOPK_PRUNE
       }
 #ifdef RG_TOPK_TIMING
       tw_epi += __builtin_amdgcn_s_memtime() - te0;
@@ -512,7 +540,7 @@ struct SmallCfg {
   static size_t lds_bytes(int k) { return (size_t)WAVES * (sizeof(float) * TILE_FLOATS + (size_t)k * 16 * 8); }
 };
 
-template <int D>
+template <int D, bool MASKED = false>
 __global__ void __launch_bounds__(512, 2) topk_smallb_kernel(TopkParams p) {
   using C = SmallCfg<D>;
   extern __shared__ float4 smem4[];
@@ -539,7 +567,7 @@ __global__ void __launch_bounds__(512, 2) topk_smallb_kernel(TopkParams p) {
   {
     float my_d = 1.f;
     const int nq = (int)min((int64_t)16, p.B - qbase);  // queries of this group
-    for (int jj = 0; jj < nq; ++jj) {
+    for (int jj = 0; jj < (MASKED ? 0 : nq); ++jj) {  // MASKED: inner products of the raw rows
       float pp = 0.f;
       for (int c = lane; c < D / 4; c += 64) {
         const float4 v = reinterpret_cast<const float4*>(p.Qn + (qbase + jj) * D)[c];
@@ -559,7 +587,7 @@ __global__ void __launch_bounds__(512, 2) topk_smallb_kernel(TopkParams p) {
     for (int m = 0; m < D / 4; ++m) {
       const float4 v = qp[m];
       const float x = sl == 0 ? v.x : sl == 1 ? v.y : sl == 2 ? v.z : v.w;
-      breg[m] = x / my_d;
+      breg[m] = MASKED ? x : x / my_d;
     }
   }
   for (int i = lane; i < k * 16; i += 64) {
@@ -609,35 +637,43 @@ __global__ void __launch_bounds__(512, 2) topk_smallb_kernel(TopkParams p) {
       for (int m = 0; m < D / 4; ++m) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * m], breg[m], acc, 0, 0, 0);
 
       const float mx = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3]));
-      if (__any(mx >= thr)) {
+      // MASKED: at or below mask_value every key is a candidate (an excluded one enters at mask_value)
+      const bool all_cand = MASKED && p.mask_value >= thr;
+      if (__any(mx >= thr || all_cand)) {
         // rare path: the wave inserts the candidates one at a time, all 64 lanes cooperating on each insert
         const int key_base = (int)(t * C::TILE_KEYS) + sub * 16 + 4 * sl;
         unsigned mask = 0;
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (acc[r] >= thr && key_base + r < (int)p.N) mask |= 1u << r;
+          if ((acc[r] >= thr || all_cand) && key_base + r < (int)p.N) mask |= 1u << r;
+#define RG_SMALL_PRUNE()                                                                          \
+  do {                                                                                            \
+    if (!(MASKED && p.mask_value >= thr)) {                                                       \
+      _Pragma("unroll") for (int r = 0; r < 4; ++r) if ((mask >> r & 1u) && acc[r] < thr) mask &= ~(1u << r); \
+    }                                                                                             \
+  } while (0)
         unsigned long long pend = __ballot(mask != 0);
         if (__popcll(pend) > 8) {
           // DENSE regime (no floor yet, or many queries): lane-private inserts, the 4 lanes of a query take turns
           while (pend) {
             const int r0 = __ffs(mask) - 1;
-            const float my_sc = r0 == 1 ? acc[1] : r0 == 2 ? acc[2] : r0 == 3 ? acc[3] : acc[0];
+            float my_sc = r0 == 1 ? acc[1] : r0 == 2 ? acc[2] : r0 == 3 ? acc[3] : acc[0];
+            if (MASKED && mask != 0 && hist_contains(p.hrp, p.hcol, qbase + j, key_base + r0)) my_sc = p.mask_value;
 #pragma unroll 1
             for (int ss = 0; ss < 4; ++ss) {
               if (mask != 0 && sl == ss) list_insert_lane(ls + j, li + j, k, 16, my_sc, key_base + r0);
             }
             mask &= mask - 1;
             if (live) thr = fmaxf(thr_floor, ls[(k - 1) * 16 + j]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if ((mask >> r & 1u) && acc[r] < thr) mask &= ~(1u << r);
+            RG_SMALL_PRUNE();
             pend = __ballot(mask != 0);
           }
         }
         while (pend) {
           const int src = __ffsll((long long)pend) - 1;          // wave-uniform: lowest lane with a candidate
           const int r0 = __ffs(mask) - 1;                        // (meaningful on lane src)
-          const float my_sc = r0 == 1 ? acc[1] : r0 == 2 ? acc[2] : r0 == 3 ? acc[3] : acc[0];
+          float my_sc = r0 == 1 ? acc[1] : r0 == 2 ? acc[2] : r0 == 3 ? acc[3] : acc[0];
+          if (MASKED && lane == src && hist_contains(p.hrp, p.hcol, qbase + j, key_base + r0)) my_sc = p.mask_value;
           const float sc = __shfl(my_sc, src);
           const int idx = __shfl(key_base + r0, src);
           const int q = src & 15;
@@ -645,11 +681,10 @@ __global__ void __launch_bounds__(512, 2) topk_smallb_kernel(TopkParams p) {
           if (live && j == q) thr = fmaxf(thr_floor, nthr);
           if (lane == src) mask &= mask - 1;
           // drop this lane's remaining candidates that the tightened threshold already excludes
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if ((mask >> r & 1u) && acc[r] < thr) mask &= ~(1u << r);
+          RG_SMALL_PRUNE();
           pend = __ballot(mask != 0);
         }
+#undef RG_SMALL_PRUNE
       }
     }
   }
@@ -954,12 +989,12 @@ static TopkPlan plan_topk(int64_t B, int64_t N, int D, int k) {
   return pl;
 }
 
-template <int D, int RING>
+template <int D, int RING, bool MASKED = false>
 static int launch_topk_ring(const TopkParams& p, int64_t qtiles, hipStream_t st) {
   using C = TopkCfg<D>;
   const size_t lds = C::lds_bytes(p.k, RING);
   static DeviceOnce lds_once;  // per device (common.h)
-  if (hipError_t e = raise_dynamic_lds(lds_once, &topk_stream_kernel<D, RING>, 160 * 1024); e != hipSuccess) {
+  if (hipError_t e = raise_dynamic_lds(lds_once, &topk_stream_kernel<D, RING, MASKED>, 160 * 1024); e != hipSuccess) {
     set_error("topk_cosine: cannot raise dynamic LDS limit: %s", hipGetErrorString(e));
     return RAGRAPH_EDEVICE;
   }
@@ -968,7 +1003,7 @@ static int launch_topk_ring(const TopkParams& p, int64_t qtiles, hipStream_t st)
   unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_topk_timing), zero, sizeof(zero));
 #endif
-  hipLaunchKernelGGL((topk_stream_kernel<D, RING>), dim3((unsigned)grid), dim3(C::THREADS), lds, st, p);
+  hipLaunchKernelGGL((topk_stream_kernel<D, RING, MASKED>), dim3((unsigned)grid), dim3(C::THREADS), lds, st, p);
   RG_CHECK_LAUNCH("topk_cosine");
 #ifdef RG_TOPK_TIMING
   (void)hipDeviceSynchronize();
@@ -984,7 +1019,7 @@ static int launch_topk_ring(const TopkParams& p, int64_t qtiles, hipStream_t st)
   return RAGRAPH_OK;
 }
 
-template <int D>
+template <int D, bool MASKED = false>
 static int launch_topk(const TopkParams& p, int64_t qtiles, hipStream_t st) {
   // the barrier-free 3-slot ring needs 3 x 33 KB of stages next to the 2 KB * k of lists in the 160 KB LDS
   static const int ring_env = [] {  // diagnostic override (read once): RAGRAPH_TOPK_RING = 2, 3 or 4
@@ -993,24 +1028,24 @@ static int launch_topk(const TopkParams& p, int64_t qtiles, hipStream_t st) {
   }();
   const bool fits3 = TopkCfg<D>::lds_bytes(p.k, 3) <= 160 * 1024;
   const bool want3 = ring_env >= 3;
-  if constexpr (D == 256) {
+  if constexpr (D == 256 && !MASKED) {  // (the masked kernels read raw item rows: no packed copy)
     const bool fits4 = TopkCfg<D>::lds_bytes(p.k, 4) <= 160 * 1024;
     if (p.Kp && fits4 && ring_env != 2 && ring_env != 3 && !(p.ablate & 6)) return launch_topk_ring<D, 4>(p, qtiles, st);
   }
-  if (fits3 && want3 && !(p.ablate & 6)) return launch_topk_ring<D, 3>(p, qtiles, st);
-  return launch_topk_ring<D, 2>(p, qtiles, st);
+  if (fits3 && want3 && !(p.ablate & 6)) return launch_topk_ring<D, 3, MASKED>(p, qtiles, st);
+  return launch_topk_ring<D, 2, MASKED>(p, qtiles, st);
 }
 
-template <int D>
+template <int D, bool MASKED = false>
 static int launch_smallb(const TopkParams& p, hipStream_t st) {
   using C = SmallCfg<D>;
   const size_t lds = C::lds_bytes(p.k);
   static DeviceOnce lds_once;  // per device (common.h)
-  if (hipError_t e = raise_dynamic_lds(lds_once, &topk_smallb_kernel<D>, 160 * 1024); e != hipSuccess) {
+  if (hipError_t e = raise_dynamic_lds(lds_once, &topk_smallb_kernel<D, MASKED>, 160 * 1024); e != hipSuccess) {
     set_error("topk_cosine(small batch): cannot raise dynamic LDS limit: %s", hipGetErrorString(e));
     return RAGRAPH_EDEVICE;
   }
-  hipLaunchKernelGGL(topk_smallb_kernel<D>, dim3((unsigned)(p.nsplit * p.ngroups)), dim3(512), lds, st, p);
+  hipLaunchKernelGGL((topk_smallb_kernel<D, MASKED>), dim3((unsigned)(p.nsplit * p.ngroups)), dim3(512), lds, st, p);
   RG_CHECK_LAUNCH("topk_cosine(small batch)");
   return RAGRAPH_OK;
 }
@@ -1213,6 +1248,9 @@ extern "C" int ragraph_topk_cosine_bank_f32(const float* Q, int64_t B, const flo
   p.nstages_total = pl.nstages_total;
   p.part_s = part_s;
   p.part_i = part_i;
+  p.hrp = nullptr;
+  p.hcol = nullptr;
+  p.mask_value = 0.f;
   static const int ablate_env = [] {  // timing-only diagnostic switches (read once), see TopkParams::ablate
     const char* e = getenv("RAGRAPH_TOPK_ABLATE");
     return e ? atoi(e) : 0;
@@ -1263,4 +1301,228 @@ extern "C" int ragraph_topk_merge_f32(const float* scores, const int64_t* idx, i
   RG_REQUIRE((int64_t)G * k <= 4096, RAGRAPH_EUNSUPPORTED, "topk_merge: G*k=%lld > 4096", (long long)G * k);
   return launch_select<int64_t>(scores, idx, G, B, k, (int64_t)B * k, (int64_t)k, (int64_t)0, out_scores, out_idx,
                                 as_stream(stream));
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Inner-product top-k with per-query exclusion lists: RAGraph_edge/utils/metrics.py:104-116 + 210-214 (rating =
+// user_emb[users] @ item_emb.T, training-history items set to -1e8, torch.topk).  The fused kernels are the cosine
+// kernels' MASKED instantiations (raw rows, no normalisation; a candidate that beats the k-th score is looked up in its
+// query's sorted exclusion list and, if found, offered at mask_value instead).  Slab path: dense kernel, masked fill of
+// the slab's columns, row top-k.  The same fmaf chains everywhere, hence the same bits as linear + fill + topk_rows.
+// ------------------------------------------------------------------------------------------------------------------
+namespace ragraph {
+// bad |= 1: a history id outside [0, N); 2: a user id outside [0, nU); 4: rowptr not monotone from 0 to nnz
+__global__ void __launch_bounds__(256) masked_check_kernel(const int64_t* __restrict__ users, int64_t B, int64_t nU,
+                                                           const int64_t* __restrict__ rp, const int64_t* __restrict__ hist,
+                                                           int64_t nnz, int64_t N, int* bad) {
+  const int64_t n = nnz > B + 1 ? nnz : B + 1;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    if (i < nnz && (hist[i] < 0 || hist[i] >= N)) atomicOr(bad, 1);
+    if (i < B) {
+      if (users && (users[i] < 0 || users[i] >= nU)) atomicOr(bad, 2);
+      if (rp[i] > rp[i + 1]) atomicOr(bad, 4);
+    }
+    if (i == 0 && (rp[0] != 0 || rp[B] != nnz)) atomicOr(bad, 4);
+  }
+}
+
+// S[(b - b0) * ld + (c - n0)] = value for every history entry (b, c) with b in [b0, b0 + nb), c in [n0, n0 + nn)
+__global__ void __launch_bounds__(256) masked_fill_slab_kernel(float* __restrict__ S, int64_t ld,
+                                                               const int64_t* __restrict__ rows,
+                                                               const int64_t* __restrict__ hist, int64_t nnz, int64_t b0,
+                                                               int64_t nb, int64_t n0, int64_t nn, float value) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= nnz) return;
+  const int64_t b = rows[e] - b0, c = hist[e] - n0;
+  if (b >= 0 && b < nb && c >= 0 && c < nn) S[b * ld + c] = value;
+}
+
+struct MaskedWs {  // byte offsets into the workspace
+  size_t ug, bad, rows, hcol, perm, crp, coo, coo_bytes, rest;
+};
+
+static MaskedWs masked_ws_layout(int64_t B, int64_t N, int D, int64_t nnz) {
+  MaskedWs w;
+  const int64_t n = B > N ? B : N;  // coo_to_csr sorts by row * n + col: both must be < n
+  w.ug = 0;
+  w.bad = align_up((size_t)B * D * sizeof(float), 256);
+  w.rows = w.bad + 256;
+  w.hcol = w.rows + align_up((size_t)nnz * sizeof(int64_t), 256);
+  w.perm = w.hcol + align_up((size_t)nnz * sizeof(int), 256);
+  w.crp = w.perm + align_up((size_t)nnz * sizeof(int64_t), 256);
+  w.coo = w.crp + align_up((size_t)(n + 1) * sizeof(int64_t), 256);
+  w.coo_bytes = nnz > 0 ? align_up(ragraph_coo_to_csr_workspace_bytes(nnz, n), 256) : 0;
+  w.rest = w.coo + w.coo_bytes;
+  return w;
+}
+
+static bool masked_slab(int64_t B, int64_t N, int D, int k) { return !fused_width(D) || k > 32 || use_slab(B, N, D); }
+}  // namespace ragraph
+
+extern "C" size_t ragraph_topk_dot_masked_workspace_bytes(int64_t B, int64_t N, int D, int k, int64_t nnz) {
+  if (B < 1 || N < 1 || k < 1 || D < 1 || nnz < 0) return 0;
+  const MaskedWs w = masked_ws_layout(B, N, D, nnz);
+  if (masked_slab(B, N, D, k)) {
+    const int64_t rows = slab_rows_for(B, N), G = slab_chunks(N), nc = cdiv(N, G);
+    size_t bytes = align_up((size_t)rows * nc * sizeof(float), 256);
+    if (G > 1) bytes += align_up((size_t)G * rows * k * sizeof(float), 256) + align_up((size_t)G * rows * k * sizeof(int64_t), 256);
+    return w.rest + bytes;
+  }
+  const TopkPlan pl = plan_topk(B, N, D, k);
+  return w.rest + pl.part_s_bytes + pl.part_i_bytes;
+}
+
+extern "C" int ragraph_topk_dot_masked_f32(const float* U, int64_t n_rows_U, const int64_t* users, int64_t B,
+                                           const float* I, int64_t N, int D, int k, const int64_t* hist_rowptr,
+                                           const int64_t* hist_items, int64_t nnz, float mask_value, float* out_scores,
+                                           int64_t* out_idx, void* ws, size_t ws_bytes, void* stream) {
+  RG_REQUIRE(U && I && hist_rowptr && out_scores && out_idx && ws && (nnz == 0 || hist_items), RAGRAPH_EINVAL,
+             "topk_dot_masked: null pointer");
+  RG_REQUIRE(B >= 1 && N >= 1 && D >= 1 && nnz >= 0 && n_rows_U >= 1, RAGRAPH_EINVAL,
+             "topk_dot_masked: B=%lld N=%lld D=%d nnz=%lld n_rows_U=%lld", (long long)B, (long long)N, D, (long long)nnz,
+             (long long)n_rows_U);
+  RG_REQUIRE(users || B <= n_rows_U, RAGRAPH_EINVAL, "topk_dot_masked: B=%lld rows of a %lld-row U", (long long)B,
+             (long long)n_rows_U);
+  RG_REQUIRE(k >= 1 && k <= N, RAGRAPH_EINVAL, "topk_dot_masked: k=%d out of range for N=%lld", k, (long long)N);
+  RG_REQUIRE(k <= RAGRAPH_TOPK_MAX, RAGRAPH_EUNSUPPORTED, "topk_dot_masked: k=%d > %d (RAGRAPH_TOPK_MAX)", k,
+             RAGRAPH_TOPK_MAX);
+  RG_REQUIRE(N < (int64_t)INT_MAX - 1024 && B < (int64_t)INT_MAX && nnz < (int64_t)INT_MAX, RAGRAPH_EUNSUPPORTED,
+             "topk_dot_masked: N, B and nnz must fit int32");
+  RG_REQUIRE(aligned16(U) && aligned16(I) && aligned16(ws), RAGRAPH_EINVAL, "topk_dot_masked: U, I, ws must be 16-B aligned");
+  RG_REQUIRE(ws_bytes >= ragraph_topk_dot_masked_workspace_bytes(B, N, D, k, nnz), RAGRAPH_EWORKSPACE,
+             "topk_dot_masked: workspace %zu < %zu", ws_bytes, ragraph_topk_dot_masked_workspace_bytes(B, N, D, k, nnz));
+  hipStream_t st = as_stream(stream);
+  char* w0 = static_cast<char*>(ws);
+  const MaskedWs w = masked_ws_layout(B, N, D, nnz);
+  const int64_t nsort = B > N ? B : N;
+
+  // ids first (one read-back): nothing below may index with an id that is out of range
+  int* bad = reinterpret_cast<int*>(w0 + w.bad);
+  if (hipMemsetAsync(bad, 0, sizeof(int), st) != hipSuccess) {
+    set_error("topk_dot_masked: memset failed");
+    return RAGRAPH_EDEVICE;
+  }
+  {
+    const int64_t n = nnz > B + 1 ? nnz : B + 1;
+    const int64_t blocks = cdiv(n, 256) < 4096 ? cdiv(n, 256) : 4096;
+    hipLaunchKernelGGL(masked_check_kernel, dim3((unsigned)blocks), dim3(256), 0, st, users, B, n_rows_U, hist_rowptr,
+                       hist_items, nnz, N, bad);
+    RG_CHECK_LAUNCH("topk_dot_masked(check)");
+  }
+  int bad_h = 0;
+  if (hipMemcpyAsync(&bad_h, bad, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    set_error("topk_dot_masked: read-back of the id check failed");
+    return RAGRAPH_EDEVICE;
+  }
+  RG_REQUIRE(!(bad_h & 1), RAGRAPH_EINVAL, "topk_dot_masked: a history item id is outside [0, %lld)", (long long)N);
+  RG_REQUIRE(!(bad_h & 2), RAGRAPH_EINVAL, "topk_dot_masked: a user id is outside [0, %lld)", (long long)n_rows_U);
+  RG_REQUIRE(!(bad_h & 4), RAGRAPH_EINVAL, "topk_dot_masked: hist_rowptr is not a CSR row pointer over %lld items",
+             (long long)nnz);
+
+  // query rows (the reference's user_emb[user_batch], metrics.py:104)
+  float* Ug = reinterpret_cast<float*>(w0 + w.ug);
+  int rc = users ? ragraph_gather_rows_f32(U, n_rows_U, D, users, B, 0, Ug, stream)
+                 : (hipMemcpyAsync(Ug, U, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess
+                        ? RAGRAPH_OK : RAGRAPH_EDEVICE);
+  if (rc != RAGRAPH_OK) return rc;
+  int64_t* rows = reinterpret_cast<int64_t*>(w0 + w.rows);
+  int* hcol = reinterpret_cast<int*>(w0 + w.hcol);
+  if (nnz > 0) {  // every query's exclusion list sorted ascending (duplicates kept): row ids, then a stable key sort
+    rc = ragraph_csr_row_ids_i64(hist_rowptr, B, nnz, rows, stream);
+    if (rc == RAGRAPH_OK)
+      rc = ragraph_coo_to_csr_i64(rows, hist_items, nnz, nsort, 1, reinterpret_cast<int64_t*>(w0 + w.crp),
+                                  reinterpret_cast<int64_t*>(w0 + w.perm), hcol, w0 + w.coo, w.coo_bytes, stream);
+    if (rc != RAGRAPH_OK) return rc;
+  }
+  char* rest = w0 + w.rest;
+
+  if (masked_slab(B, N, D, k)) {
+    const int64_t srows = slab_rows_for(B, N), G = slab_chunks(N), nc = cdiv(N, G);
+    const size_t s_bytes = align_up((size_t)srows * nc * sizeof(float), 256);
+    const size_t ps_bytes = G > 1 ? align_up((size_t)G * srows * k * sizeof(float), 256) : 0;
+    RG_REQUIRE(G * k <= 4096, RAGRAPH_EUNSUPPORTED, "topk_dot_masked: %lld key chunks x k=%d exceed the merge", (long long)G, k);
+    float* S = reinterpret_cast<float*>(rest);
+    float* part_s = reinterpret_cast<float*>(rest + s_bytes);
+    int64_t* part_i = reinterpret_cast<int64_t*>(rest + s_bytes + ps_bytes);
+    for (int64_t b0 = 0; rc == RAGRAPH_OK && b0 < B; b0 += srows) {
+      const int64_t nb = (B - b0 < srows) ? B - b0 : srows;
+      for (int64_t g = 0; rc == RAGRAPH_OK && g < G; ++g) {
+        const int64_t n0 = g * nc, nn = (N - n0 < nc) ? N - n0 : nc;
+        rc = ragraph_linear_f32(Ug + b0 * D, nb, D, I + n0 * D, nn, nullptr, RAGRAPH_ACT_NONE, 0.f, S, stream);
+        if (rc != RAGRAPH_OK) break;
+        if (nnz > 0) {
+          hipLaunchKernelGGL(masked_fill_slab_kernel, dim3((unsigned)cdiv(nnz, 256)), dim3(256), 0, st, S, nn, rows,
+                             hist_items, nnz, b0, nb, n0, nn, mask_value);
+          RG_CHECK_LAUNCH("topk_dot_masked(fill)");
+        }
+        if (G == 1) {
+          rc = ragraph_topk_rows_f32(S, nb, nn, nn, k, out_scores + b0 * k, out_idx + b0 * k, stream);
+          break;
+        }
+        rc = ragraph_topk_rows_f32(S, nb, nn, nn, k, part_s + g * nb * k, part_i + g * nb * k, stream);
+        if (rc == RAGRAPH_OK && n0 != 0) {
+          hipLaunchKernelGGL(add_idx_base_kernel, dim3((unsigned)cdiv(nb * k, 256)), dim3(256), 0, st, part_i + g * nb * k,
+                             nb * k, n0);
+          RG_CHECK_LAUNCH("topk_dot_masked(chunk base)");
+        }
+      }
+      if (rc == RAGRAPH_OK && G > 1)
+        rc = launch_select<int64_t>(part_s, part_i, (int)G, nb, k, nb * k, (int64_t)k, (int64_t)0, out_scores + b0 * k,
+                                    out_idx + b0 * k, st);
+    }
+    return rc;
+  }
+
+  const TopkPlan pl = plan_topk(B, N, D, k);
+  float* part_s = reinterpret_cast<float*>(rest);
+  int* part_i = reinterpret_cast<int*>(rest + pl.part_s_bytes);
+  TopkParams p;
+  memset(&p, 0, sizeof(p));
+  p.Qn = Ug;
+  p.Kn = I;
+  p.Kp = nullptr;
+  p.B = B;
+  p.N = N;
+  p.k = k;
+  p.nsplit = pl.nsplit;
+  p.ngroups = (int)cdiv(B, 16);
+  p.qtiles = cdiv(B, 256);
+  p.xcd_map = pl.xcd_map;
+  p.wgs_per_group = pl.wgs_per_group;
+  p.lb_min = pl.lb_min;
+  p.warm_stages = pl.warm_stages;
+  p.depth[0] = pl.depth[0];
+  p.depth[1] = pl.depth[1];
+  p.nstages_total = pl.nstages_total;
+  p.part_s = part_s;
+  p.part_i = part_i;
+  p.thr_init = nullptr;
+  p.hrp = hist_rowptr;  // the sorted lists keep the caller's row pointer
+  p.hcol = hcol;
+  p.mask_value = mask_value;
+  p.ablate = 0;
+  if (use_streaming(B, k, D)) {
+    const int64_t prefix = 4096;  // the masked k-th best of a prefix bounds the final masked k-th best from below
+    if (B >= 4 && N >= 16 * prefix && k <= prefix) {
+      TopkParams pp = p;
+      pp.N = prefix;
+      pp.nsplit = (int)cdiv(cdiv(prefix, 16 * (256 / D)), 8);
+      if (pp.nsplit > pl.nsplit) pp.nsplit = pl.nsplit;
+      rc = D == 256 ? launch_smallb<256, true>(pp, st) : D == 128 ? launch_smallb<128, true>(pp, st) : launch_smallb<64, true>(pp, st);
+      if (rc != RAGRAPH_OK) return rc;
+      rc = launch_merge_sorted<int>(part_s, part_i, pp.nsplit, B, k, (int64_t)k, (int64_t)pp.nsplit * k, 0, out_scores,
+                                    out_idx, st);
+      if (rc != RAGRAPH_OK) return rc;
+      p.thr_init = out_scores;
+    }
+    rc = D == 256 ? launch_smallb<256, true>(p, st) : D == 128 ? launch_smallb<128, true>(p, st) : launch_smallb<64, true>(p, st);
+    if (rc != RAGRAPH_OK) return rc;
+    return launch_merge_sorted<int>(part_s, part_i, pl.nsplit, B, k, (int64_t)k, (int64_t)pl.nsplit * k, 0, out_scores,
+                                    out_idx, st);
+  }
+  const int64_t qtiles = cdiv(B, 256);
+  rc = D == 256 ? launch_topk<256, true>(p, qtiles, st) : D == 128 ? launch_topk<128, true>(p, qtiles, st)
+                                                                   : launch_topk<64, true>(p, qtiles, st);
+  if (rc != RAGRAPH_OK) return rc;
+  return launch_select<int>(part_s, part_i, pl.nsplit, B, k, (int64_t)k, (int64_t)pl.nsplit * k, 0, out_scores, out_idx, st);
 }

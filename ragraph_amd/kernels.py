@@ -1307,3 +1307,66 @@ def mul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(a)
     N.check(L.ragraph_mul_f32(a.data_ptr(), b.data_ptr(), a.numel(), out.data_ptr(), _stream()), "mul")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# f4: edge (link-prediction) evaluation -- RAGraph_edge/utils/metrics.py:83-141
+def topk_dot_masked_workspace_bytes(B: int, n_items: int, D: int, k: int, nnz: int) -> int:
+    """Scratch bytes of one topk_dot_masked call (no [B, n_items] slab on the fused kernels)."""
+    return int(N.lib().ragraph_topk_dot_masked_workspace_bytes(B, n_items, D, k, nnz))
+
+
+def topk_dot_masked(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int, hist_rowptr: torch.Tensor,
+                    hist_items: torch.Tensor, users: torch.Tensor | None = None, mask_value: float = -1e8):
+    """(scores [B,k] f32, idx [B,k] i64): rating = user_emb[users] @ item_emb.T, the items of query b's history
+    hist_items[hist_rowptr[b]:hist_rowptr[b+1]] SCORED as mask_value (metrics.py:210-214), canonical top-k (metrics.py:116).
+    users=None: query b = row b.  Histories may be unsorted and hold duplicates; an id out of range raises."""
+    L = _ready()
+    ue = _f32c(user_emb, "topk_dot_masked.user_emb")
+    ie = _f32c(item_emb, "topk_dot_masked.item_emb")
+    rp = _idxc(hist_rowptr, "topk_dot_masked.hist_rowptr")
+    hi = _idxc(hist_items, "topk_dot_masked.hist_items")
+    us = None if users is None else _idxc(users, "topk_dot_masked.users")
+    if ue.dim() != 2 or ie.dim() != 2 or ue.shape[1] != ie.shape[1]:
+        raise RagraphNativeError(f"topk_dot_masked: bad shapes {tuple(ue.shape)} x {tuple(ie.shape)}")
+    if k > N.TOPK_MAX:
+        raise RagraphNativeError(f"topk_dot_masked: k={k} exceeds the kernels' limit of {N.TOPK_MAX}")
+    B = ue.shape[0] if us is None else us.numel()
+    Ni, D = ie.shape
+    if rp.numel() != B + 1:
+        raise RagraphNativeError(f"topk_dot_masked: hist_rowptr has {rp.numel()} entries, expected {B + 1}")
+    scores = torch.empty((B, k), dtype=torch.float32, device=ue.device)
+    idx = torch.empty((B, k), dtype=torch.int64, device=ue.device)
+    if B == 0:
+        return scores, idx
+    nnz = hi.numel()
+    ws = _workspace(L.ragraph_topk_dot_masked_workspace_bytes(B, Ni, D, k, nnz), ue.device)
+    N.check(L.ragraph_topk_dot_masked_f32(ue.data_ptr(), ue.shape[0], _ptr(us), B, ie.data_ptr(), Ni, D, k, rp.data_ptr(),
+                                          hi.data_ptr() if nnz else None, nnz, float(mask_value), scores.data_ptr(),
+                                          idx.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "topk_dot_masked")
+    return scores, idx
+
+
+RANK_METRICS = ("recall", "ndcg", "precision")   # the rows of rank_metrics' result
+
+
+def rank_metrics(idx: torch.Tensor, gt_rowptr: torch.Tensor, gt_items: torch.Tensor, ks, batch: int = 512):
+    """metrics.py:12-46 + 60-80 + 131-133 on the device: [3, len(ks)] float64 numpy array (rows recall, ndcg, precision)
+    of the ranked lists idx [U, kmax] against the ground-truth CSR; sums in batches of `batch` users, added batch by batch
+    (the reference's order).  One read-back of 3 x len(ks) doubles."""
+    L = _ready()
+    ix = _idxc(idx, "rank_metrics.idx")
+    rp = _idxc(gt_rowptr, "rank_metrics.gt_rowptr")
+    gi = _idxc(gt_items, "rank_metrics.gt_items")
+    if ix.dim() != 2:
+        raise RagraphNativeError(f"rank_metrics: idx must be [U, kmax], got {tuple(ix.shape)}")
+    U, kmax = ix.shape
+    if rp.numel() != U + 1:
+        raise RagraphNativeError(f"rank_metrics: gt_rowptr has {rp.numel()} entries, expected {U + 1}")
+    ks = [int(k) for k in ks]
+    karr = (ctypes.c_int * len(ks))(*ks)
+    out = torch.empty(3 * len(ks), dtype=torch.float64, device=ix.device)
+    ws = _workspace(L.ragraph_rank_metrics_workspace_bytes(U, len(ks), batch), ix.device)
+    N.check(L.ragraph_rank_metrics_f64(ix.data_ptr(), U, kmax, rp.data_ptr(), gi.data_ptr() if gi.numel() else None, karr,
+                                       len(ks), batch, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "rank_metrics")
+    return out.cpu().numpy().reshape(3, len(ks))
