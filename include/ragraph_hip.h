@@ -68,7 +68,9 @@ int ragraph_normalize_rows_f32(const float* X, int64_t n, int D, float* out, voi
  *   Q   [B,D] raw (un-normalised) queries; normalised inside (a1) into the workspace.
  *   Kn  [N,D] key bank ALREADY row-normalised by ragraph_normalize_rows_f32 (done once per bank version; the
  *       reference re-normalises its stored keys on every call, SimilarityFunctions.py:11).
- *   k   1 <= k <= min(N, RAGRAPH_TOPK_MAX) (larger k: ragraph_topk_select_rows_f32 over score slabs).  B,N >= 1.
+ *   k   1 <= k <= min(N, RAGRAPH_TOPK_ORDERED_MAX), B,N >= 1.  64 < k takes the score slabs below with the ordered
+ *       large-k selection (ragraph_topk_rows_large_f32); banks beyond one dense launch (65535 x 64 = 4 194 240 rows) are
+ *       scored in key chunks whose per-chunk lists the same selection merges.
  *       Any D >= 1, as the reference (SimilarityFunctions.py:6-16 takes every emb_size): the fused kernels are written
  *       for D in {64,128,256}; every other width takes materialised score slabs (~1 GiB of the workspace: dense kernel +
  *       row top-k, banks beyond 2^22 rows in key chunks merged in canonical order) -- the same fmaf chains, the same
@@ -79,7 +81,7 @@ int ragraph_normalize_rows_f32(const float* X, int64_t n, int D, float* out, voi
  *       32 < k <= 64 materialises ~1 GiB slabs of scores in the workspace (dense kernel + row top-k), same bits.
  *   idx_base  added to every returned index (this shard's first global row).
  *   out_scores [B,k] fp32 descending; out_idx [B,k] int64 (torch indexing dtype).
- *   Unsupported (returns RAGRAPH_EUNSUPPORTED): k > RAGRAPH_TOPK_MAX, shards of >= 2^31 rows.  NaN scores are never selected
+ *   Unsupported (returns RAGRAPH_EUNSUPPORTED): k > RAGRAPH_TOPK_ORDERED_MAX, shards of >= 2^31 rows.  NaN scores are never selected
  *   (torch.topk would rank NaN first) -- inputs are finite by contract.
  */
 #define RAGRAPH_TOPK_MAX 64
@@ -515,7 +517,8 @@ int ragraph_time_rescale_f32(const int64_t* t, int64_t n, float t_min, float t_m
  * torch.topk(scores, k) over a MATERIALISED score matrix (canonical order, agrees with the fused kernel on equal
  * scores) -- few-shot retrieve after mixing structure and semantic similarities
  * (RAGraph_node_fewshot/ragraph_utils/ToyGraphBase.py:58-64) and the evaluation's top-20 of user x item ratings
- * (RAGraph_edge/utils/metrics.py:116).  S [B, ld] row-major with N <= ld valid columns; k <= min(N, 64).
+ * (RAGraph_edge/utils/metrics.py:116).  S [B, ld] row-major with N <= ld valid columns; k <= min(N, 64) (larger k:
+ * ragraph_topk_rows_large_f32).
  * out_scores [B,k], out_idx [B,k] int64. */
 int ragraph_topk_rows_f32(const float* S, int64_t B, int64_t N, int64_t ld, int k, float* out_scores,
                           int64_t* out_idx, void* stream);
@@ -536,6 +539,22 @@ int ragraph_topk_select_rows_f32(const float* S, int64_t B, int64_t N, int64_t l
 size_t ragraph_topk_select_rows_workspace_bytes(int64_t B, int64_t N);
 int ragraph_topk_select_rows_ws_f32(const float* S, int64_t B, int64_t N, int64_t ld, int64_t k, float* out_kth,
                                     int64_t* out_idx, void* ws, size_t ws_bytes, void* stream);
+
+/* Ordered top-k for large k: torch.topk(S, k, sorted=True) over a materialised score matrix -- node retrieval with
+ * retrieve_num = num_class + 1 (RAGraph_node/ragraph_utils/ToyGraphBase.py:22), doubled with noise (:63-64,
+ * finetune-noise.py), and the few-shot flavour's retrieve_num (RAGraph_node_fewshot/ragraph_utils/ToyGraphBase.py:16,22,64).
+ * S [B, ld] row-major with N <= ld valid columns; 1 <= k <= min(N, RAGRAPH_TOPK_ORDERED_MAX), N < 2^31.
+ * out_scores [B,k] fp32 (the input's bits), out_idx [B,k] int64, canonical order (score descending, index ascending);
+ * -0 and +0 are one score (a tie), -inf is an ordinary score, NaN is never selected: a row with fewer than k other
+ * scores is padded with (-inf, INT64_MAX).  k > N: RAGRAPH_EINVAL; k > RAGRAPH_TOPK_ORDERED_MAX: RAGRAPH_EUNSUPPORTED;
+ * nothing is written then.  Coarse LDS histogram -> compaction of the winners' bin and above -> bitonic sort in LDS: two
+ * reads of a row (a third for skewed rows, digit refinement for heavy ties); rows of >= 65536 scores are spread over
+ * (chunk, row) workgroups whose sorted lists are merged by the same kernel.  Deterministic (no global atomics).
+ * ws: ragraph_topk_rows_large_workspace_bytes(B, N, k) bytes (0 for rows of < 65536 scores; ws may then be NULL). */
+#define RAGRAPH_TOPK_ORDERED_MAX 4096
+size_t ragraph_topk_rows_large_workspace_bytes(int64_t B, int64_t N, int64_t k);
+int ragraph_topk_rows_large_f32(const float* S, int64_t B, int64_t N, int64_t ld, int64_t k, float* out_scores,
+                                int64_t* out_idx, void* ws, size_t ws_bytes, void* stream);
 
 /* batch_pred[i, pos_list] = value  -- RAGraph_edge/utils/metrics.py:210-214 (_mask_history_pos, value = -1e8).
  * CSR (rowptr [B+1], col [nnz], both int64) lists the columns to overwrite in each row of S [B, ld]. */

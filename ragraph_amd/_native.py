@@ -21,7 +21,8 @@ SO_PATH = os.environ.get("RAGRAPH_HIP_SO", os.path.join(CSRC, "libragraph_hip.so
 
 OK, EINVAL, EUNSUPPORTED, EWORKSPACE, EDEVICE = 0, -1, -2, -3, -4
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_LEAKY, ACT_ELU = 0, 1, 2, 3, 4
-TOPK_MAX = 64
+TOPK_MAX = 64                # the fused kernels' list limit (RAGRAPH_TOPK_MAX)
+TOPK_ORDERED_MAX = 4096      # ordered top-k over exact fp32 score slabs (RAGRAPH_TOPK_ORDERED_MAX)
 
 _vp, _i64, _i32, _f32, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 
@@ -106,6 +107,8 @@ SIGNATURES = {
     "ragraph_topk_select_rows_f32": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "ragraph_topk_select_rows_workspace_bytes": (_sz, [_i64, _i64]),
     "ragraph_topk_select_rows_ws_f32": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "ragraph_topk_rows_large_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "ragraph_topk_rows_large_f32": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "ragraph_scatter_fill_f32": (_i32, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp]),
     "ragraph_floyd_warshall_f32": (_i32, [_vp, _i32, _vp, _vp]),
     "ragraph_position_code_f32": (_i32, [_vp, _i32, _vp, _i32, _f32, _vp, _vp]),

@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "topk_large.h"
 #include "segment_plan.h"
 
 namespace ragraph {
@@ -1096,8 +1097,27 @@ static size_t slab_workspace_bytes(int64_t B, int64_t N, int D, int k) {
   return bytes;
 }
 
+// 64 < k <= RAGRAPH_TOPK_ORDERED_MAX: the same score slabs, selected by the ordered large-k kernel (csrc/topk_large.hip).
+// Banks beyond one dense launch keep every key chunk's sorted list as packed candidates [rows][G * k] and merge them with the
+// same kernel (G * k exceeds what launch_select holds).  Layout: Qn | S slab | candidates (G > 1) | selection workspace.
+// Key chunks of at most 65535 x 64 columns, the dense kernel's launch limit (2^22 itself is 64 columns over it).
+static int64_t slab_large_chunks(int64_t N) { return cdiv(N, (int64_t)65535 * 64); }
+
+static size_t slab_large_workspace_bytes(int64_t B, int64_t N, int D, int k) {
+  const int64_t rows = slab_rows_for(B, N), G = slab_large_chunks(N), nc = cdiv(N, G);
+  size_t bytes = align_up((size_t)B * D * sizeof(float), 256) + align_up((size_t)rows * nc * sizeof(float), 256);
+  size_t sel = large_select_ws_bytes(rows, nc, k);
+  if (G > 1) {
+    bytes += align_up((size_t)rows * G * k * sizeof(unsigned long long), 256);
+    const size_t merge = large_select_ws_bytes(rows, G * k, k);
+    if (merge > sel) sel = merge;
+  }
+  return bytes + sel;
+}
+
 extern "C" size_t ragraph_topk_cosine_workspace_bytes(int64_t B, int64_t N, int D, int k) {
   if (B < 1 || N < 1 || k < 1 || D < 1) return 0;
+  if (k > RAGRAPH_TOPK_MAX) return k <= RAGRAPH_TOPK_ORDERED_MAX ? slab_large_workspace_bytes(B, N, D, k) : 0;
   if (!fused_width(D) || k > 32 || use_slab(B, N, D)) return slab_workspace_bytes(B, N, D, k);
   TopkPlan pl = plan_topk(B, N, D, k);
   return pl.qn_bytes + pl.part_s_bytes + pl.part_i_bytes;
@@ -1163,10 +1183,45 @@ extern "C" int ragraph_topk_cosine_bank_f32(const float* Q, int64_t B, const flo
   RG_REQUIRE(k >= 1 && k <= N, RAGRAPH_EINVAL, "topk_cosine: k=%d out of range for N=%lld (torch.topk raises too)", k,
              (long long)N);
   RG_REQUIRE(D >= 1, RAGRAPH_EINVAL, "topk_cosine: D=%d must be >= 1", D);
-  RG_REQUIRE(k <= RAGRAPH_TOPK_MAX, RAGRAPH_EUNSUPPORTED, "topk_cosine: k=%d > %d not supported by the fused kernel", k,
-             RAGRAPH_TOPK_MAX);
+  RG_REQUIRE(k <= RAGRAPH_TOPK_ORDERED_MAX, RAGRAPH_EUNSUPPORTED, "topk_cosine: k=%d > %d (RAGRAPH_TOPK_ORDERED_MAX)", k,
+             RAGRAPH_TOPK_ORDERED_MAX);
   RG_REQUIRE(N < (int64_t)INT_MAX - 1024, RAGRAPH_EUNSUPPORTED, "topk_cosine: shard rows must fit int32");
   RG_REQUIRE(aligned16(Q) && aligned16(Kn) && aligned16(ws), RAGRAPH_EINVAL, "topk_cosine: Q, Kn, ws must be 16-B aligned");
+  if (k > RAGRAPH_TOPK_MAX) {  // ordered large k over exact fp32 score slabs (see slab_large_workspace_bytes)
+    RG_REQUIRE(ws_bytes >= slab_large_workspace_bytes(B, N, D, k), RAGRAPH_EWORKSPACE, "topk_cosine: workspace too small");
+    hipStream_t st = as_stream(stream);
+    const int64_t rows = slab_rows_for(B, N), G = slab_large_chunks(N), nc = cdiv(N, G);
+    char* w = static_cast<char*>(ws);
+    float* Qn = reinterpret_cast<float*>(w);
+    w += align_up((size_t)B * D * sizeof(float), 256);
+    float* S = reinterpret_cast<float*>(w);
+    w += align_up((size_t)rows * nc * sizeof(float), 256);
+    unsigned long long* cand = reinterpret_cast<unsigned long long*>(w);
+    if (G > 1) w += align_up((size_t)rows * G * k * sizeof(unsigned long long), 256);
+    void* sel_ws = w;
+    int rc = ragraph_normalize_rows_f32(Q, B, D, Qn, stream);
+    for (int64_t b0 = 0; rc == RAGRAPH_OK && b0 < B; b0 += rows) {
+      const int64_t nb = (B - b0 < rows) ? B - b0 : rows;
+      if (G == 1) {
+        rc = ragraph_linear_f32(Qn + b0 * D, nb, D, Kn, N, nullptr, RAGRAPH_ACT_NONE, 0.f, S, stream);
+        if (rc == RAGRAPH_OK)
+          rc = large_select(S, nullptr, nb, N, N, k, 0u, S, N, idx_base, nullptr, 0, out_scores + b0 * k, out_idx + b0 * k,
+                            sel_ws, st);
+        continue;
+      }
+      for (int64_t g = 0; rc == RAGRAPH_OK && g < G; ++g) {  // key chunk g -> candidates [nb][g * k, (g + 1) * k)
+        const int64_t n0 = g * nc, nn = (N - n0 < nc) ? N - n0 : nc;
+        rc = ragraph_linear_f32(Qn + b0 * D, nb, D, Kn + n0 * D, nn, nullptr, RAGRAPH_ACT_NONE, 0.f, S, stream);
+        if (rc == RAGRAPH_OK)
+          rc = large_select(S, nullptr, nb, nn, nn, k, (unsigned)n0, nullptr, 0, 0, cand + g * k, G * k, nullptr, nullptr,
+                            sel_ws, st);
+      }
+      if (rc == RAGRAPH_OK)  // (scores decoded from the keys: a score's fmaf chain starts from +0, so it is never -0)
+        rc = large_select(nullptr, cand, nb, G * k, G * k, k, 0u, nullptr, 0, idx_base, nullptr, 0, out_scores + b0 * k,
+                          out_idx + b0 * k, sel_ws, st);
+    }
+    return rc;
+  }
   // A handful of queries against a bank of a few thousand keys (graph classification: 16 graphs x the training set's
   // 1113): every key is still a candidate for every list, and the streaming kernel's cooperative inserts -- one
   // (query, key) at a time -- were 45 us of a 150 us forward.  The slab path (dense kernel + topk_rows) has no lists.

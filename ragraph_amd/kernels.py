@@ -137,7 +137,8 @@ def topk_cosine(q: torch.Tensor, keys_normalized: torch.Tensor, k: int, idx_base
     SimilarityFunctions.py:6-16 + ToyGraphBase.py:66-67.  `keys_normalized` must come from normalize_rows();
     `keys_packed` (optional) from pack_keys(keys_normalized) -- same bits out, faster key stream for B > 128.
     Any D >= 1: widths other than 64 / 128 / 256 take materialised score slabs (dense kernel + row top-k, same bits);
-    KeyIndex pads banks narrower than 256 once and keeps them on the fused kernels."""
+    KeyIndex pads banks narrower than 256 once and keeps them on the fused kernels.
+    1 <= k <= min(N, TOPK_ORDERED_MAX): k > TOPK_MAX always takes exact fp32 score slabs and the ordered large-k selection."""
     L = _ready()
     q = _f32c(q, "topk_cosine.q")
     kn = _f32c(keys_normalized, "topk_cosine.keys")
@@ -965,7 +966,9 @@ def axpby_dev(a: torch.Tensor, b: torch.Tensor, w: torch.Tensor, ia: int, ib: in
 
 def topk_rows(scores: torch.Tensor, k: int):
     """torch.topk(scores, k) over a materialised [B,N] matrix, canonical tie order -- few-shot retrieve
-    (RAGraph_node_fewshot/.../ToyGraphBase.py:64), edge evaluation (RAGraph_edge/utils/metrics.py:116)."""
+    (RAGraph_node_fewshot/.../ToyGraphBase.py:64), edge evaluation (RAGraph_edge/utils/metrics.py:116).
+    1 <= k <= min(N, TOPK_ORDERED_MAX): k <= TOPK_MAX takes the wave-list kernel, larger k the ordered large-k kernel
+    (ragraph_topk_rows_large_f32; NaN is never selected, rows short of k other scores pad with -inf / INT64_MAX)."""
     L = _ready()
     s = _f32c(scores, "topk_rows.scores")
     if s.dim() != 2:
@@ -973,6 +976,11 @@ def topk_rows(scores: torch.Tensor, k: int):
     B, Nn = s.shape
     out_s = torch.empty((B, k), dtype=torch.float32, device=s.device)
     out_i = torch.empty((B, k), dtype=torch.int64, device=s.device)
+    if k > N.TOPK_MAX:
+        ws = _workspace(L.ragraph_topk_rows_large_workspace_bytes(B, Nn, k), s.device)
+        N.check(L.ragraph_topk_rows_large_f32(s.data_ptr(), B, Nn, Nn, k, out_s.data_ptr(), out_i.data_ptr(), ws.data_ptr(),
+                                              ws.numel(), _stream()), "topk_rows")
+        return out_s, out_i
     N.check(L.ragraph_topk_rows_f32(s.data_ptr(), B, Nn, Nn, k, out_s.data_ptr(), out_i.data_ptr(), _stream()),
             "topk_rows")
     return out_s, out_i

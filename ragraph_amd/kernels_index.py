@@ -5,6 +5,8 @@ import os
 
 import torch
 
+from ._native import TOPK_MAX
+
 
 class KeyIndex:
     """One bank version on the device: the normalised keys plus the copies the faster kernels stream (packed fp32 for
@@ -343,6 +345,12 @@ class KeyIndex:
         ops, kn = self.ops, self.keys_normalized
         if q.shape[1] != self.dim:
             raise ValueError(f"KeyIndex.topk: queries of {q.shape[1]} columns against a bank of {self.dim}")
+        if k > TOPK_MAX and exchange is None:
+            # ordered large k (exact fp32 score slabs) over the full bank: duplicate rows score alike and the lower row wins,
+            # so no collapse is needed; the prior, counters and pending overflow word are left as they are
+            if self._width is not None and self._width != self.dim:
+                q = ops.pad_cols(q, self._width)
+            return ops.topk_cosine(q, kn, k, idx_base=idx_base)
         if self._width is None:   # wider than every fused kernel: exact score slabs, this shard's own top-k (no exchange needed)
             return ops.topk_cosine(q, kn, k, idx_base=idx_base)
         if self._width != self.dim:

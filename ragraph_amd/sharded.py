@@ -18,6 +18,8 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
+from ._native import TOPK_MAX, RagraphNativeError
+
 
 # ---- collectives ------------------------------------------------------------------------------------------------------
 # RCCL ("nccl") moves device tensors directly.  Under "gloo" (CPU tests; two ranks sharing ONE GPU in
@@ -441,9 +443,18 @@ class ShardedToyGraphBase:
             self._suppress = True
         return ok
 
+    @staticmethod
+    def _check_k(k: int) -> None:
+        """The sharded merge (exchanges, topk_merge of the gathered lists) is written for the fused kernels' lists.  k is the
+        same on every rank, so every rank raises here, before any collective."""
+        if k > TOPK_MAX:
+            raise RagraphNativeError(f"ShardedToyGraphBase: k={k} exceeds the sharded top-k limit of {TOPK_MAX} "
+                                     "(TOPK_MAX); larger k needs an unsharded ToyGraphBase")
+
     def topk(self, search_keys, k=None):
         """Global canonical top-k: (scores [B,k], idx [B,k]) identical on every rank."""
         k = self.retrieve_num if k is None else k
+        self._check_k(k)
         q = search_keys.reshape(1, -1) if search_keys.dim() == 1 else search_keys
         n_local = self.keys_normalized.shape[0]
         kl = min(k, n_local)
@@ -494,6 +505,7 @@ class ShardedToyGraphBase:
         defer_verify: the caller enqueues more work first and calls confirm() itself before it hands out anything -- when that
         returns False it repeats this call (RAGraph._forward_key_shard / _forward_hybrid)."""
         k = self.retrieve_num if k is None else k
+        self._check_k(k)
         q = search_keys.reshape(1, -1) if search_keys.dim() == 1 else search_keys
         B = q.shape[0]
         lo, hi = self.tail_bounds(B)
