@@ -398,6 +398,22 @@ size_t ragraph_sparse_workspace_bytes(int64_t nnz, int D);
 int ragraph_spmm_csr_ws_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n, const float* X, int D,
                             const float* bias, int act, float alpha, float beta, const float* Y_in, float* Y, int64_t nnz,
                             void* ws, size_t ws_bytes, void* stream);
+/* Fine-tuning a GCN layer whose PReLU slope is a trained parameter (RAGraph_node_fewshot/RAGraph.py:69 through
+ * layers/gcn.py:36-40) without reading the slope on the host: a kernel argument would freeze the slope into a captured
+ * HIP graph, and reading it costs a synchronisation per step.
+ *   spmm_csr_prelu_dev:  Y = PReLU(A X + bias) with the slope alpha[0] read on the device; Z (nullable) receives the
+ *     pre-activation A X + bias.  ws / nnz as ragraph_spmm_csr_ws_f32 (ws = NULL: no hub-row workspace).  Y and Z are
+ *     bit-identical to ragraph_spmm_csr_ws_f32 with act = RAGRAPH_ACT_PRELU, alpha = alpha[0] (resp. RAGRAPH_ACT_NONE).
+ *   act_grad_prelu_dev:  from Z (not the output), gy and the device slope: gz = gy * PReLU'(z) and, when alpha_terms is
+ *     not NULL, the slope's gradient terms gy * min(z, 0) (their column sums, then their sum, are the slope gradient).
+ *     For alpha[0] > 0 the bits of ragraph_act_grad_f32 on the output y = PReLU(z); for alpha[0] <= 0 those of
+ *     ragraph_act_grad_f32 on z itself with the terms gy * (z * 1 + relu(z) * -1) (ragraph_mul_cols_act_f32 +
+ *     ragraph_axpby_f32 + ragraph_mul_f32) -- the arithmetic the host-scalar training path uses for that sign. */
+int ragraph_spmm_csr_prelu_dev_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n, const float* X,
+                                   int D, const float* bias, const float* alpha, float* Y, float* Z, int64_t nnz, void* ws,
+                                   size_t ws_bytes, void* stream);
+int ragraph_act_grad_prelu_dev_f32(const float* z, const float* gy, int64_t n, const float* alpha, float* gz,
+                                   float* alpha_terms, void* stream);
 
 /* Integer bookkeeping primitives of ingestion (edge list -> CSR) and of the duplicate grouping: a stable LSD radix sort of
  * 64-bit keys by their low `bits` bits (8 bits per pass) with optional 4- or 8-byte values, and int32 prefix sums (totals

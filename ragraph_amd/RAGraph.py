@@ -64,6 +64,9 @@ class RAGraph(nn.Module):
                 return sliced
         pretrain_embedddings = self.pretrain_model.inference(features, g)                      # RAGraph.py:40
         add_noise = self.training and self.noise_finetune
+        if add_noise and torch.cuda.is_current_stream_capturing():
+            raise K.RagraphNativeError("noisy fine-tuning draws its noise on the host generator, as the reference does: "
+                                       "its step cannot be captured in a HIP graph (train it eagerly)")
         queries = self._queries(pretrain_embedddings, g)
         if self.query_shard is not None and not self.training and self.flavour == "node":
             if (getattr(tgb, "values_replicated", False) and hasattr(tgb, "retrieve_reduced_rows")

@@ -90,9 +90,17 @@ class ToyGraphBaseFewShot(ToyGraphBase):
         return rag_embeddings, rag_labels
 
 
+def _reject_noise_under_capture(add_noise: bool):
+    if add_noise and torch.cuda.is_current_stream_capturing():
+        raise K.RagraphNativeError("noisy fine-tuning draws new noise rows every step (on the host generator in the graph "
+                                   "flavour, as the reference does): its step is not captured in a HIP graph (train it eagerly)")
+
+
 class RAGraph(nn.Module):
-    """RAGraph_node_fewshot/RAGraph.py:7-83.  Forward only: the reference fine-tunes the second GCN layer through
-    decode(); that backward is outside the inference path."""
+    """RAGraph_node_fewshot/RAGraph.py:7-83.  In training mode the second GCN layer trains through decode()
+    (autograd.spmm_csr, slope on the device) and the label mix (:77): a whole step can be captured
+    (ragraph_amd.capture.CapturedTrainStep) when the anchors of the position codes are passed in (the reference draws
+    them from the host generator every forward)."""
 
     def __init__(self, pretrain_model, resource_dataset, mean_fewshot_logits, emb_size, finetune=True,
                  noise_finetune=False, query_graph_hop=3, retrieve_num=5, device="cuda", dataset_name=None):
@@ -113,6 +121,10 @@ class RAGraph(nn.Module):
         g = as_csr(adj)
         emb = self.pretrain_model.encode(features, g)                                           # :48
         add_noise = self.training and self.noise_finetune
+        _reject_noise_under_capture(add_noise)
+        if anchors is None and torch.cuda.is_current_stream_capturing():
+            raise K.RagraphNativeError("RAGraph_fewshot.RAGraph: pass `anchors` to a captured forward (drawn on the host "
+                                       "generator otherwise: PositionAwareEncoder.py:11)")
         rag_embeddings, rag_labels = self.toy_graph_base.retrieve(emb, g, add_noise, anchors)    # :51
         label_ids = torch.argmax(rag_labels, dim=-1)                                             # :54 (integer lookup)
         k = label_ids.shape[1]
@@ -126,7 +138,8 @@ class RAGraph(nn.Module):
         query = Propagation.aggregate_k_hop_features(g, emb, self.query_graph_hop)               # :65
         hidden = K.axpby(query, 1 - self.retrieve_weight, rag_embedding, self.retrieve_weight)   # :67
         decode_logits = self.pretrain_model.decode(hidden, g)                                    # :69
-        return K.axpby(decode_logits, 1 - self.label_weight, rag_logits, self.label_weight)      # :77
+        from . import autograd as A   # (differentiable when decode() trains; the same kernel otherwise)
+        return A.axpby(decode_logits, 1 - self.label_weight, rag_logits, self.label_weight)      # :77
 
 
 class RAGraphGraphFewShot(nn.Module):
@@ -161,6 +174,7 @@ class RAGraphGraphFewShot(nn.Module):
         tgb = self.toy_graph_base
         emb = self.pretrain_model.encode(features, g)                                            # :47
         add_noise = self.training and self.noise_finetune
+        _reject_noise_under_capture(add_noise)
         idx = tgb.retrieve_indices(emb, add_noise)                                               # :51 (k' = 2k with noise)
         k = idx.shape[1]
         label_ids = torch.argmax(K.gather_rows(tgb.resource_labels, idx), dim=-1)                # :55 (integer lookup)

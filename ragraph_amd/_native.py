@@ -114,6 +114,8 @@ SIGNATURES = {
     "ragraph_position_code_f32": (_i32, [_vp, _i32, _vp, _i32, _f32, _vp, _vp]),
     "ragraph_position_codes_csr_f32": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _f32, _vp, _vp, _vp]),
     "ragraph_act_grad_f32": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
+    "ragraph_spmm_csr_prelu_dev_f32": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "ragraph_act_grad_prelu_dev_f32": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "ragraph_sigmoid_gate_grad_f32": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "ragraph_softmax_grad_f32": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp]),
     "ragraph_mul_cols_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),

@@ -103,10 +103,23 @@ class _SpmmCsr(torch.autograd.Function):
     Backward: gz = gy * act'(z); gx = A^T gz (the same kernel over the transposed CSR, cached on the graph); gbias =
     column sums of gz; PReLU slope: sum of gy * z over z < 0.  The fused epilogue keeps only y, from which the
     pre-activation's sign and value follow while the slope is positive (sign(y) = sign(z), z = y / alpha on the negative
-    side).  A trained PReLU slope is unconstrained: for alpha <= 0 the forward runs unfused and keeps z itself."""
+    side).  A trained PReLU slope is unconstrained: for alpha <= 0 the forward runs unfused and keeps z itself.
+    Device-slope mode (alpha = None, act = PReLU, alpha_t its weight): the slope is never read on the host -- one launch
+    writes y and z (K.spmm_csr_prelu_dev), and backward takes gz and the slope terms from z and the device slope
+    (K.act_grad_prelu_dev), which picks the arithmetic above by the slope's sign on the device: the same bits for every
+    slope, and nothing a captured HIP graph would freeze."""
 
     @staticmethod
     def forward(ctx, g, x, bias, act, alpha_t, alpha):
+        ctx.dev = alpha is None
+        if ctx.dev:
+            if act != K.ACT_PRELU or alpha_t is None:
+                raise ValueError("spmm_csr: the device-slope mode (alpha=None) is PReLU with its weight tensor")
+            y, z = K.spmm_csr_prelu_dev(g.rowptr, g.col, g.val, x, bias, alpha_t, want_z=True, long_rows=g.has_long_rows)
+            ctx.save_for_backward(z, alpha_t)
+            ctx.g, ctx.act, ctx.alpha, ctx.keeps_z = g, act, None, True
+            ctx.has_bias, ctx.has_alpha = bias is not None, True
+            return y
         ctx.keeps_z = act == K.ACT_PRELU and alpha <= 0.0
         if ctx.keeps_z:
             z = K.spmm_csr(g.rowptr, g.col, g.val, x, bias=bias, act=K.ACT_NONE, long_rows=g.has_long_rows)
@@ -121,12 +134,20 @@ class _SpmmCsr(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        (y,) = ctx.saved_tensors          # (z itself when keeps_z: act_grad's sign test is then on the pre-activation)
+        if ctx.dev:
+            z, alpha_t = ctx.saved_tensors
+        else:
+            (y,) = ctx.saved_tensors      # (z itself when keeps_z: act_grad's sign test is then on the pre-activation)
         gy = gy.contiguous()
         galpha = None
         if ctx.act != K.ACT_NONE:
             want_alpha = ctx.has_alpha and ctx.needs_input_grad[4]
-            if ctx.keeps_z:
+            if ctx.dev:
+                if want_alpha:
+                    gz, terms = K.act_grad_prelu_dev(z, gy, alpha_t, want_alpha_terms=True)
+                else:
+                    gz = K.act_grad_prelu_dev(z, gy, alpha_t)
+            elif ctx.keeps_z:
                 gz = K.act_grad(y, gy, ctx.act, ctx.alpha)
                 if want_alpha:             # sum of gy * min(z, 0): min(z, 0) = z - relu(z)
                     neg = K.axpby(y, 1.0, K.mul_cols(y, torch.ones(y.shape[-1], device=y.device), K.ACT_RELU), -1.0)
@@ -150,11 +171,13 @@ class _SpmmCsr(torch.autograd.Function):
 
 def spmm_csr(g, x, bias=None, act=K.ACT_NONE, alpha_param=None, alpha=0.0):
     """Differentiable act(A @ x + bias); alpha_param = the PReLU weight tensor (its gradient is produced when it requires
-    one), alpha = its value as a host scalar."""
+    one), alpha = its value as a host scalar -- or None: PReLU with the slope read from alpha_param on the device."""
     need = torch.is_grad_enabled() and (x.requires_grad or (bias is not None and bias.requires_grad) or
                                         (alpha_param is not None and alpha_param.requires_grad))
     if need:
         return _SpmmCsr.apply(g, x, bias, act, alpha_param, alpha)
+    if alpha is None:
+        return K.spmm_csr_prelu_dev(g.rowptr, g.col, g.val, x, bias, alpha_param.detach(), long_rows=g.has_long_rows)
     return K.spmm_csr(g.rowptr, g.col, g.val, x, bias=bias, act=act, alpha=alpha, long_rows=g.has_long_rows)
 
 

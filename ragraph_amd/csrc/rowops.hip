@@ -220,6 +220,34 @@ __global__ void __launch_bounds__(256) act_grad_kernel(const float* __restrict__
   }
 }
 
+// The same from the PRE-activation z with the PReLU slope read on the device (a trained slope never leaves it):
+// ragraph_act_grad_prelu_dev_f32.  The slope's sign picks the arithmetic the host-scalar training path uses for it, so
+// every output keeps its bits:
+//   a > 0:  y = apply_act(z) -- the forward's output, recomputed -- then act_grad_kernel's expressions on y;
+//   a <= 0: act_grad_kernel's expressions on z itself, and t = gy * (z * 1 + relu(z) * -1): the mul / axpby / mul
+//           chain that builds min(z, 0) from z.
+__global__ void __launch_bounds__(256) act_grad_prelu_dev_kernel(const float* __restrict__ z, const float* __restrict__ gy,
+                                                                 int64_t n, const float* __restrict__ alpha,
+                                                                 float* __restrict__ gz, float* __restrict__ t) {
+  const float a = alpha[0];
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const float zv = z[i], g = gy[i];
+    if (a > 0.f) {
+      const float yv = apply_act(zv, RAGRAPH_ACT_PRELU, a);
+      gz[i] = g * (yv >= 0.f ? 1.f : a);
+      if (t) t[i] = yv < 0.f ? g * (yv / a) : 0.f;
+    } else {
+      gz[i] = g * (zv >= 0.f ? 1.f : a);
+      if (t) {
+        const float z1 = __fmul_rn(zv, 1.f);
+        const float r = apply_act(z1, RAGRAPH_ACT_RELU, 0.f);
+        t[i] = __fmul_rn(g, __fadd_rn(__fmul_rn(zv, 1.f), __fmul_rn(r, -1.f)));
+      }
+    }
+  }
+}
+
 // emb_gate backward: out = x * s, s = sigmoid(z):  gx = g * s,  gz = g * x * s * (1 - s)
 __global__ void __launch_bounds__(256) sigmoid_gate_grad_kernel(const float* __restrict__ x, const float* __restrict__ z,
                                                                 const float* __restrict__ g, int64_t n, float* __restrict__ gx,
@@ -686,6 +714,16 @@ extern "C" int ragraph_act_grad_f32(const float* y, const float* gy, int64_t n, 
   hipLaunchKernelGGL(act_grad_kernel, dim3(ew_blocks(n)), dim3(256), 0, as_stream(stream), y, gy, n, act, alpha, gz,
                      alpha_terms);
   RG_CHECK_LAUNCH("act_grad");
+  return RAGRAPH_OK;
+}
+
+extern "C" int ragraph_act_grad_prelu_dev_f32(const float* z, const float* gy, int64_t n, const float* alpha, float* gz,
+                                              float* alpha_terms, void* stream) {
+  RG_REQUIRE(z && gy && alpha && gz, RAGRAPH_EINVAL, "act_grad_prelu_dev: null pointer");
+  if (n <= 0) return RAGRAPH_OK;
+  hipLaunchKernelGGL(act_grad_prelu_dev_kernel, dim3(ew_blocks(n)), dim3(256), 0, as_stream(stream), z, gy, n, alpha, gz,
+                     alpha_terms);
+  RG_CHECK_LAUNCH("act_grad_prelu_dev");
   return RAGRAPH_OK;
 }
 

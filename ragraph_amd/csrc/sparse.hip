@@ -69,8 +69,10 @@ __device__ __forceinline__ float4 add4(float4 a, float4 b) {
 // panel of their column block): the layout the column-panel hops below read.
 __device__ __forceinline__ void spmm_epilogue_store(float4 acc, const float* __restrict__ bias, int act, float alpha,
                                                     float beta, const float* __restrict__ Yin, float* __restrict__ Y,
-                                                    int64_t row, int D4, int c4, int64_t panel_n = 0) {
+                                                    int64_t row, int D4, int c4, int64_t panel_n = 0,
+                                                    float* __restrict__ Z = nullptr) {
   if (bias) acc = add4(acc, reinterpret_cast<const float4*>(bias)[c4]);
+  if (Z) reinterpret_cast<float4*>(Z)[row * D4 + c4] = acc;   // the pre-activation (device-slope training entry only)
   acc.x = apply_act(acc.x, act, alpha); acc.y = apply_act(acc.y, act, alpha);
   acc.z = apply_act(acc.z, act, alpha); acc.w = apply_act(acc.w, act, alpha);
   if (Yin) {
@@ -82,15 +84,20 @@ __device__ __forceinline__ void spmm_epilogue_store(float4 acc, const float* __r
 }
 
 // skip_long != 0: rows longer than ROW_BLOCK are left to the long-row kernels.
-template <int LPR>
+// DEV: the PReLU slope is read from alpha_dev[0] (a trained parameter that stays on the device) instead of `alpha`, and Z,
+// when not null, receives the pre-activation A x + bias -- ragraph_spmm_csr_prelu_dev_f32.  Same arithmetic otherwise.
+template <int LPR, bool DEV = false>
 __global__ void __launch_bounds__(256) spmm_csr_kernel(const int64_t* __restrict__ rowptr,
                                                        const int32_t* __restrict__ col,
                                                        const float* __restrict__ val, int64_t n,
                                                        const float* __restrict__ X, int D,
                                                        const float* __restrict__ bias, int act, float alpha, float beta,
                                                        const float* __restrict__ Yin, float* __restrict__ Y,
-                                                       int skip_long, unsigned RUN, int64_t panel_n = 0) {
+                                                       int skip_long, unsigned RUN, int64_t panel_n = 0,
+                                                       const float* __restrict__ alpha_dev = nullptr,
+                                                       float* __restrict__ Z = nullptr) {
   constexpr int RPB = 256 / LPR;  // rows per block
+  if constexpr (DEV) alpha = alpha_dev[0];
   const int lr = threadIdx.x % LPR;
   const int gbase = (threadIdx.x & 63) - lr;  // first lane of this row's group inside the wave
   // Workgroup b runs on XCD b % 8, each with its own L2.  Inside every group of 8 x 32 consecutive workgroups an XCD gets
@@ -132,7 +139,7 @@ __global__ void __launch_bounds__(256) spmm_csr_kernel(const int64_t* __restrict
       }
     }
     if (!live || !colok) continue;
-    spmm_epilogue_store(acc, bias, act, alpha, beta, Yin, Y, row, D4, c4, panel_n);
+    spmm_epilogue_store(acc, bias, act, alpha, beta, Yin, Y, row, D4, c4, panel_n, DEV ? Z : nullptr);
   }
 }
 
@@ -361,13 +368,16 @@ __global__ void __launch_bounds__(256) spmm_long_blocks_kernel(const int64_t* __
   }
 }
 
-// One lane group per long row: its block sums in block order, then the epilogue.
-template <int LPR>
+// One lane group per long row: its block sums in block order, then the epilogue (DEV: as spmm_csr_kernel).
+template <int LPR, bool DEV = false>
 __global__ void __launch_bounds__(256) spmm_long_finish_kernel(const int64_t* __restrict__ rowptr, int D,
                                                                const float* __restrict__ bias, int act, float alpha,
                                                                float beta, const float* __restrict__ Yin,
-                                                               float* __restrict__ Y, LongRows w) {
+                                                               float* __restrict__ Y, LongRows w,
+                                                               const float* __restrict__ alpha_dev = nullptr,
+                                                               float* __restrict__ Z = nullptr) {
   constexpr int RPB = 256 / LPR;
+  if constexpr (DEV) alpha = alpha_dev[0];
   const int lr = threadIdx.x % LPR;
   const int64_t li = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
   if (li >= w.ctr[0]) return;
@@ -380,7 +390,7 @@ __global__ void __launch_bounds__(256) spmm_long_finish_kernel(const int64_t* __
   for (int c4 = lr; c4 < D4; c4 += LPR) {
     float4 acc = P4[p * D4 + c4];
     for (int b = 1; b < nb; ++b) acc = add4(acc, P4[(p + b) * D4 + c4]);
-    spmm_epilogue_store(acc, bias, act, alpha, beta, Yin, Y, row, D4, c4);
+    spmm_epilogue_store(acc, bias, act, alpha, beta, Yin, Y, row, D4, c4, 0, DEV ? Z : nullptr);
   }
 }
 
@@ -564,16 +574,23 @@ static int find_long_rows(const int64_t* rowptr, int64_t n, const LongRows& w, h
   return RAGRAPH_OK;
 }
 
-extern "C" int ragraph_spmm_csr_ws_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n,
-                                       const float* X, int D, const float* bias, int act, float alpha, float beta,
-                                       const float* Y_in, float* Y, int64_t nnz, void* ws, size_t ws_bytes,
-                                       void* stream) {
+// The launcher of ragraph_spmm_csr_ws_f32 (DEV = false) and ragraph_spmm_csr_prelu_dev_f32 (DEV = true: slope from
+// alpha_dev[0], optional pre-activation Z).
+template <bool DEV>
+static int spmm_csr_launch(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n, const float* X, int D,
+                           const float* bias, int act, float alpha, float beta, const float* Y_in, float* Y, int64_t nnz,
+                           void* ws, size_t ws_bytes, const float* alpha_dev, float* Z, void* stream) {
   RG_REQUIRE(rowptr && X && Y, RAGRAPH_EINVAL, "spmm_csr: null pointer");
   RG_REQUIRE(n >= 0 && D >= 4 && (D & 3) == 0, RAGRAPH_EINVAL, "spmm_csr: D=%d must be a positive multiple of 4", D);
   RG_REQUIRE(aligned16(X) && aligned16(Y) && (!bias || aligned16(bias)) && (!Y_in || aligned16(Y_in)), RAGRAPH_EINVAL,
              "spmm_csr: X, Y, bias, Y_in must be 16-B aligned");
   RG_REQUIRE(X != Y, RAGRAPH_EINVAL, "spmm_csr: Y must not alias X");
   RG_REQUIRE(act >= RAGRAPH_ACT_NONE && act <= RAGRAPH_ACT_ELU, RAGRAPH_EINVAL, "spmm_csr: bad act %d", act);
+  if (DEV) {
+    RG_REQUIRE(alpha_dev, RAGRAPH_EINVAL, "spmm_csr_prelu_dev: null slope pointer");
+    RG_REQUIRE(!Z || (aligned16(Z) && Z != X && Z != Y), RAGRAPH_EINVAL,
+               "spmm_csr_prelu_dev: Z must be 16-B aligned and alias neither X nor Y");
+  }
   if (n == 0) return RAGRAPH_OK;
   hipStream_t st = as_stream(stream);
   LongRows w{};
@@ -595,13 +612,13 @@ extern "C" int ragraph_spmm_csr_ws_f32(const int64_t* rowptr, const int32_t* col
 #define RG_SPMM(LPR_)                                                                                                  \
   do {                                                                                                                 \
     constexpr int RPB_ = 256 / (LPR_);                                                                                 \
-    hipLaunchKernelGGL(spmm_csr_kernel<LPR_>, dim3((unsigned)cdiv(n, RPB_)), dim3(256), 0, st, rowptr, col, val, n, X, \
-                       D, bias, act, alpha, beta, Y_in, Y, skip, xcd_run);                                             \
+    hipLaunchKernelGGL((spmm_csr_kernel<LPR_, DEV>), dim3((unsigned)cdiv(n, RPB_)), dim3(256), 0, st, rowptr, col, val,\
+                       n, X, D, bias, act, alpha, beta, Y_in, Y, skip, xcd_run, (int64_t)0, alpha_dev, Z);             \
     if (par) {                                                                                                         \
       hipLaunchKernelGGL(spmm_long_blocks_kernel<LPR_>, dim3((unsigned)cdiv(w.max_tasks, RPB_)), dim3(256), 0, st,     \
                          rowptr, col, val, X, D, w);                                                                   \
-      hipLaunchKernelGGL(spmm_long_finish_kernel<LPR_>, dim3((unsigned)cdiv(w.max_rows, RPB_)), dim3(256), 0, st,      \
-                         rowptr, D, bias, act, alpha, beta, Y_in, Y, w);                                               \
+      hipLaunchKernelGGL((spmm_long_finish_kernel<LPR_, DEV>), dim3((unsigned)cdiv(w.max_rows, RPB_)), dim3(256), 0,   \
+                         st, rowptr, D, bias, act, alpha, beta, Y_in, Y, w, alpha_dev, Z);                             \
     }                                                                                                                  \
   } while (0)
   if (D4 <= 16) RG_SPMM(16);
@@ -610,6 +627,21 @@ extern "C" int ragraph_spmm_csr_ws_f32(const int64_t* rowptr, const int32_t* col
 #undef RG_SPMM
   RG_CHECK_LAUNCH("spmm_csr");
   return RAGRAPH_OK;
+}
+
+extern "C" int ragraph_spmm_csr_ws_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n,
+                                       const float* X, int D, const float* bias, int act, float alpha, float beta,
+                                       const float* Y_in, float* Y, int64_t nnz, void* ws, size_t ws_bytes,
+                                       void* stream) {
+  return spmm_csr_launch<false>(rowptr, col, val, n, X, D, bias, act, alpha, beta, Y_in, Y, nnz, ws, ws_bytes, nullptr,
+                                nullptr, stream);
+}
+
+extern "C" int ragraph_spmm_csr_prelu_dev_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n,
+                                              const float* X, int D, const float* bias, const float* alpha, float* Y,
+                                              float* Z, int64_t nnz, void* ws, size_t ws_bytes, void* stream) {
+  return spmm_csr_launch<true>(rowptr, col, val, n, X, D, bias, RAGRAPH_ACT_PRELU, 0.f, 0.f, nullptr, Y, nnz, ws,
+                               ws_bytes, alpha, Z, stream);
 }
 
 extern "C" int ragraph_spmm_csr_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n,

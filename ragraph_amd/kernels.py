@@ -681,10 +681,25 @@ def column_sums(x: torch.Tensor) -> torch.Tensor:
     x = _f32c(x, "column_sums.x")
     n = x.shape[0]
     if n <= COLSUM_SINGLE_MAX:   # (a batch of a few hundred nodes: one launch beats ranges + their pointer bookkeeping)
-        return segment_reduce(x, torch.tensor([0, n], dtype=torch.int64, device=x.device)).reshape(-1)
+        return segment_reduce(x, _whole_segment(n, x.device)).reshape(-1)
     ptr = torch.arange(0, n + COLSUM_ROWS, COLSUM_ROWS, dtype=torch.int64, device=x.device).clamp_(max=n)
     part = segment_reduce(x, ptr)
-    return segment_reduce(part, torch.tensor([0, part.shape[0]], dtype=torch.int64, device=x.device)).reshape(-1)
+    return segment_reduce(part, _whole_segment(part.shape[0], x.device)).reshape(-1)
+
+
+_whole_seg: dict = {}
+
+
+def _whole_segment(n: int, device) -> torch.Tensor:
+    """The segment pointer [0, n] on `device`, made once per (device, n) and kept for the life of the process: a host list
+    copied to the device is a synchronising copy, which a HIP graph capture (ragraph_amd.capture.CapturedTrainStep) does
+    not allow, and a captured graph keeps reading the entry's address -- so entries are never dropped (16 bytes each, one
+    per distinct row count).  Read-only."""
+    key = (torch.device(device), n)
+    t = _whole_seg.get(key)
+    if t is None:
+        t = _whole_seg[key] = torch.tensor([0, n], dtype=torch.int64, device=device)
+    return t
 
 
 COLSUM_ROWS = 256
@@ -1269,6 +1284,49 @@ def act_grad(y: torch.Tensor, gy: torch.Tensor, act: int, alpha: float = 0.0, wa
     t = torch.empty_like(y) if want_alpha_terms else None
     N.check(L.ragraph_act_grad_f32(y.data_ptr(), gy.data_ptr(), y.numel(), act, float(alpha), gz.data_ptr(), _ptr(t), _stream()),
             "act_grad")
+    return (gz, t) if want_alpha_terms else gz
+
+
+def spmm_csr_prelu_dev(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, x: torch.Tensor, bias: torch.Tensor | None,
+                       alpha: torch.Tensor, want_z: bool = False, long_rows: bool = False):
+    """PReLU(A @ x + bias) with the slope read on the DEVICE from alpha[0] (a trained nn.PReLU weight: no host read, so a
+    captured HIP graph follows the slope as the optimizer moves it).  want_z: also the pre-activation A @ x + bias ->
+    (y, z).  Bit-identical to spmm_csr(..., act=ACT_PRELU, alpha=float(alpha[0])) (and z to act=ACT_NONE)."""
+    L = _ready()
+    rowptr = _idxc(rowptr, "spmm_csr_prelu_dev.rowptr")
+    col = _idxc(col, "spmm_csr_prelu_dev.col", torch.int32)
+    val = _f32c(val, "spmm_csr_prelu_dev.val")
+    x = _f32c(x, "spmm_csr_prelu_dev.x")
+    a = _f32c(alpha, "spmm_csr_prelu_dev.alpha")
+    if a.numel() != 1:
+        raise ValueError(f"spmm_csr_prelu_dev: one slope expected (nn.PReLU(num_parameters=1)), got {a.numel()}")
+    b = None if bias is None else _f32c(bias, "spmm_csr_prelu_dev.bias")
+    n, D = rowptr.numel() - 1, x.shape[1]
+    y = torch.empty((n, D), dtype=torch.float32, device=x.device)
+    z = torch.empty((n, D), dtype=torch.float32, device=x.device) if want_z else None
+    nnz, ws, wsn = 0, None, 0
+    if long_rows:
+        nnz = col.numel()
+        ws = _workspace(L.ragraph_sparse_workspace_bytes(nnz, D), x.device)
+        wsn = ws.numel()
+    N.check(L.ragraph_spmm_csr_prelu_dev_f32(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), n, x.data_ptr(), D, _ptr(b),
+                                             a.data_ptr(), y.data_ptr(), _ptr(z), nnz, _ptr(ws), wsn, _stream()),
+            "spmm_csr_prelu_dev")
+    return (y, z) if want_z else y
+
+
+def act_grad_prelu_dev(z: torch.Tensor, gy: torch.Tensor, alpha: torch.Tensor, want_alpha_terms: bool = False):
+    """gz = gy * PReLU'(z) from the PRE-activation z, slope read on the device; with want_alpha_terms also gy * min(z, 0)
+    (the slope's gradient terms).  The bits of the host-scalar training path for the slope's sign (include/ragraph_hip.h)."""
+    L = _ready()
+    z, gy = _f32c(z, "act_grad_prelu_dev.z"), _f32c(gy, "act_grad_prelu_dev.gy")
+    a = _f32c(alpha, "act_grad_prelu_dev.alpha")
+    if gy.shape != z.shape:
+        raise ValueError(f"act_grad_prelu_dev: gy {tuple(gy.shape)} vs z {tuple(z.shape)}")
+    gz = torch.empty_like(z)
+    t = torch.empty_like(z) if want_alpha_terms else None
+    N.check(L.ragraph_act_grad_prelu_dev_f32(z.data_ptr(), gy.data_ptr(), z.numel(), a.data_ptr(), gz.data_ptr(), _ptr(t),
+                                             _stream()), "act_grad_prelu_dev")
     return (gz, t) if want_alpha_terms else gz
 
 

@@ -119,10 +119,12 @@ class GCN(nn.Module):
         g = as_csr(adj)
         x = seq.squeeze(0) if seq.dim() == 3 else seq
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            # fine-tuning (the few-shot flavours train this layer through decode()): the same kernels, with backward
+            # fine-tuning (the few-shot flavours train this layer through decode()): the same kernels, with backward.  The
+            # trained PReLU slope stays on the device (alpha=None): no read-back per step, and a captured training step
+            # (ragraph_amd.capture.CapturedTrainStep) follows the slope Adam moves -- the same bits as the host scalar.
             from .. import autograd as A
             seq_fts = A.linear(x, self.fc.weight)
-            return A.spmm_csr(g, seq_fts, self.bias, K.ACT_PRELU, self.act.weight, self._alpha())
+            return A.spmm_csr(g, seq_fts, self.bias, K.ACT_PRELU, self.act.weight, None)
         xs = sparse_features(x, probe=False)
         if xs is None and aggregate_first(x.shape[1], self.fc.weight.shape[0]):
             # narrow features (c2: 128 -> 256): A_hat (X W^T) = (A_hat X) W^T, and the gathers of the aggregation -- what a
@@ -140,5 +142,8 @@ class GCN(nn.Module):
             seq_fts = K.spmm_csr(xs[0], xs[1], xs[2], self._weight_t())
         else:
             seq_fts = K.linear(x, self.fc.weight)                                                # :32
-        return K.spmm_csr(g.rowptr, g.col, g.val, seq_fts, bias=self.bias, act=K.ACT_PRELU,      # :36-40 fused
-                          alpha=self._alpha(), long_rows=g.has_long_rows)
+        # :36-40 fused, the slope read on the device: the few-shot step runs this layer's inference on the support set
+        # (finetune-rag.py:96) while training it, so the slope changes every step (same bits as the host scalar)
+        # ([:1]: element 0 of the slope, as _alpha() takes it, also for an nn.PReLU with several)
+        return K.spmm_csr_prelu_dev(g.rowptr, g.col, g.val, seq_fts, self.bias, self.act.weight.detach().reshape(-1)[:1],
+                                    long_rows=g.has_long_rows)

@@ -33,7 +33,11 @@ class _Bank:
         self.n = need
 
     def view(self) -> Tensor:
+        if _Bank.reads is not None:   # (a training step being prepared for capture: ragraph_amd.capture)
+            _Bank.reads[id(self)] = self
         return self.buf[:self.n]
+
+    reads = None   # dict id -> _Bank while ragraph_amd.capture.CapturedTrainStep records which banks a step reads
 
 
 class ToyGraphBase:
