@@ -9,7 +9,10 @@ ships no dataset and no pre-trained weights, .MISSING_LARGE_BLOBS).  Same steps,
     rag_model.toy_graph_base.build_toy_graph(val_dataset)          # :97
     test accuracy                                                  # :103-112
 
-Usage: python examples/finetune_rag.py [--epochs 5] [--graphs 120]
+--pretrained PATH loads a state dict that examples/pretrain.py wrote (the reference's modelset/model_<ds>.pkl) into the
+encoder before the bank is built; without it the encoder keeps its random initialisation.
+
+Usage: python examples/finetune_rag.py [--epochs 5] [--graphs 120] [--pretrained modelset/model_SYNTH.pkl]
 """
 import argparse
 import os
@@ -29,6 +32,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--graphs", type=int, default=120)
+    ap.add_argument("--pretrained", default=None, help="state dict written by examples/pretrain.py")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     seed_everything(0)
@@ -38,6 +42,8 @@ def main():
     n_train, n_val = int(0.5 * len(dataset)), int(0.2 * len(dataset))
     train_ds, val_ds, test_ds = dataset[:n_train], dataset[n_train:n_train + n_val], dataset[n_train + n_val:]
     pretrain_model = PrePrompt(F_attr, 256, "prelu", 1, 0.3).to(dev)
+    if args.pretrained:
+        pretrain_model.load_state_dict(torch.load(args.pretrained, map_location=dev))
     t0 = time.perf_counter()
     rag_model = RAGraph(pretrain_model, train_ds, F_attr, C, 256, finetune=True, noise_finetune=False, device=dev)
     torch.cuda.synchronize()

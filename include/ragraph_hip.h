@@ -720,6 +720,38 @@ size_t ragraph_rank_metrics_workspace_bytes(int64_t U, int nks, int64_t batch);
 int ragraph_rank_metrics_f64(const int64_t* idx, int64_t U, int kmax, const int64_t* gt_rowptr, const int64_t* gt_items,
                              const int* ks, int nks, int64_t batch, double* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * LP  link-prediction pre-training -- RAGraph_node/preprompt.py:80-126 (compareloss, prompt_pretrain_sample; the graph
+ *     flavour's copy differs only in its 50 negatives, RAGraph_graph/pretrain.py:86)
+ *
+ * Both index-taking entries check their indices first (one 4-byte read-back per call, so not capturable) and return
+ * RAGRAPH_EINVAL before anything is written.  ws: ragraph_lp_workspace_bytes() bytes (the check's flag).
+ *
+ * ragraph_lp_sample_i64: preprompt.py:106-126 over the CSR pattern (rowptr [n+1], col [nnz]) of A, columns strictly
+ *   ascending per row; a diagonal entry is ignored (A_hat with self loops may be passed as it is).  out [n, 1+n_neg]
+ *   int64: column 0 a uniformly random neighbour of i, or i when i has none; columns 1..n_neg n_neg DISTINCT nodes drawn
+ *   uniformly from the complement of i's neighbour set (i itself included), in unspecified order.  Randomness is a
+ *   splitmix64 hash of (seed[0], row, draw), seed[0] read from device memory.  0 <= n_neg <= min(n, 4096).  A row with
+ *   neighbours and fewer than n_neg non-neighbours -- where the reference fails -- returns RAGRAPH_EINVAL. */
+size_t ragraph_lp_workspace_bytes(void);
+int ragraph_lp_sample_i64(const int64_t* rowptr, const int32_t* col, int64_t n, int64_t nnz, int n_neg, const int64_t* seed,
+                          int64_t* out, void* ws, size_t ws_bytes, void* stream);
+
+/* ragraph_lp_compare_loss_fwd_f32: preprompt.py:80-103 for h [n, D] and the sample t [n, S] (S = 1 + n_neg, 2 <= S <= 4097),
+ *   without the [n, S, D] gathers: nrm[i] = ||h_i|| (the fixed tree of the row norms), hhat [n, D] = h / max(nrm, 1e-8)
+ *   (F.cosine_similarity's eps), sim = hhat_i . hhat_t (one fmaf chain per 16-lane quarter, quarters added by a fixed tree),
+ *   e = expf(sim) / T, L[i] = -log(e_0 / sum_{s>=1} e_s), coef[i, s] = dL_i/dsim (-1 for s = 0, e_s / sum for s >= 1),
+ *   csim = coef * sim, loss[0] = mean of L (fixed order).  Any D >= 1; every output is written. */
+int ragraph_lp_compare_loss_fwd_f32(const float* h, int64_t n, int D, const int64_t* t, int S, float temperature,
+                                    float* loss, float* L, float* coef, float* csim, float* hhat, float* nrm, void* ws,
+                                    size_t ws_bytes, void* stream);
+
+/* ragraph_lp_combine_f32: the epilogue of compareloss's backward.  out [n, D] = s * (X / N_r - beta_r * h / (N_r nrm_r)),
+ *   N_r = max(nrm_r, 1e-8), the second term 0 where nrm_r = 0 (ATen's norm backward), s = go[0] * inv_rows read on the
+ *   device.  X = the SpMM of hhat over the own + transposed sample pattern with values coef, beta = its row sums of csim. */
+int ragraph_lp_combine_f32(const float* X, const float* h, const float* nrm, const float* beta, const float* go,
+                           float inv_rows, int64_t n, int D, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,10 @@ SIGNATURES = {
                                           _sz, _vp]),
     "ragraph_rank_metrics_workspace_bytes": (_sz, [_i64, _i32, _i64]),
     "ragraph_rank_metrics_f64": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _vp, _sz, _vp]),
+    "ragraph_lp_workspace_bytes": (_sz, []),
+    "ragraph_lp_sample_i64": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ragraph_lp_compare_loss_fwd_f32": (_i32, [_vp, _i64, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ragraph_lp_combine_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i64, _i32, _vp, _vp]),
 }
 
 

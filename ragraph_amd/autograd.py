@@ -345,3 +345,41 @@ def mix2(a, b, w):
     if torch.is_grad_enabled() and (a.requires_grad or b.requires_grad or w.requires_grad):
         return _Mix2.apply(a, b, w)
     return K.axpby_dev(a, b, w, 0, 1)
+
+
+class _CompareLoss(torch.autograd.Function):
+    """compareloss (preprompt.py:80-103): mean_i -log(e_i0 / sum_{s>=1} e_is), e = exp(cos(h_i, h_t[i,s])) / T, the cosine
+    with F.cosine_similarity's eps (x / max(||x||, 1e-8)).  Forward: one sampled dense-dense pass (K.lp_compare_loss_fwd),
+    which leaves c = dL_i/dsim and c * sim.  Backward, with hhat = h / N, N = max(||h||, 1e-8), per row r over every slot
+    (i, s) that r takes part in -- its own slots (partners t[i,s]) and the transposed ones (the rows i that drew r):
+        grad_r = go / n * (sum c hhat_partner / N_r - (sum c sim) h_r / (N_r ||h_r||)),
+    i.e. one SpMM of the existing kernels over the pattern own + transposed (made by the stable COO -> CSR sort: hub rows
+    are summed in blocks, deterministically), the row sums of c * sim over the same pattern, and a combine epilogue.
+    No atomics: two runs give the same bits."""
+
+    @staticmethod
+    def forward(ctx, h, tuples, temperature):
+        loss, _, coef, csim, hhat, nrm = K.lp_compare_loss_fwd(h, tuples, temperature)
+        ctx.save_for_backward(h, tuples, coef, csim, hhat, nrm)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, go):
+        from .graph import CSRGraph
+        h, t, coef, csim, hhat, nrm = ctx.saved_tensors
+        n, S = t.shape
+        own = torch.arange(n, device=t.device).repeat_interleave(S)
+        tf = t.reshape(-1)
+        # own slots first, transposed after them: the stable sort keeps that order inside every row
+        g, perm = CSRGraph.from_coo(torch.cat([own, tf]), torch.cat([tf, own]), torch.cat([coef.reshape(-1)] * 2), n)
+        x = K.spmm_csr(g.rowptr, g.col, g.val, hhat, long_rows=g.has_long_rows)
+        beta = K.csr_row_sums(g.rowptr, torch.cat([csim.reshape(-1)] * 2)[perm].contiguous())
+        gh = K.lp_combine(x, h, nrm, beta, go.reshape(1).float().contiguous(), 1.0 / n)
+        return gh, None, None
+
+
+def compare_loss(h, tuples, temperature):
+    """Differentiable in h (the sample is an index)."""
+    if torch.is_grad_enabled() and h.requires_grad:
+        return _CompareLoss.apply(h, tuples, temperature)
+    return K.lp_compare_loss_fwd(h, tuples, temperature)[0].reshape(())

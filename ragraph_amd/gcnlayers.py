@@ -19,13 +19,18 @@ class GcnLayers(nn.Module):
         self.dropout = nn.Dropout(p=dropout)
 
     def forward(self, seq, adj, sparse, LP=False):
-        """models/gcnlayers.py:40-67.  LP=True (pre-training: BatchNorm + dropout between layers) is outside the
-        inference path and not provided."""
-        if LP:
-            raise NotImplementedError("GcnLayers(LP=True) is the pre-training branch (BatchNorm+dropout); out of scope")
+        """models/gcnlayers.py:40-67.  LP=True is the pre-training branch: every layer's GCN output goes through bns[i]
+        (training statistics in train mode) and the dropout, as the reference's; those two stay torch's own modules, so
+        their running statistics and random masks are the reference's."""
         out = torch.squeeze(seq, dim=0)
+        if LP:
+            from .graph import as_csr
+            adj = as_csr(adj)  # (a dense adjacency is converted once, not per layer)
         for i in range(self.num_layers_num):
             out = self.convs[i]((out, adj))
+            if LP:
+                out = self.bns[i](out)
+                out = self.dropout(out)
         return out.unsqueeze(dim=0)
 
     @torch.no_grad()

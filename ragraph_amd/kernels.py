@@ -1436,3 +1436,64 @@ def rank_metrics(idx: torch.Tensor, gt_rowptr: torch.Tensor, gt_items: torch.Ten
     N.check(L.ragraph_rank_metrics_f64(ix.data_ptr(), U, kmax, rp.data_ptr(), gi.data_ptr() if gi.numel() else None, karr,
                                        len(ks), batch, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "rank_metrics")
     return out.cpu().numpy().reshape(3, len(ks))
+
+
+# ---- link-prediction pre-training (csrc/pretrain.hip) -----------------------------------------------------------------
+LP_NEG_MAX = 4096   # negatives per row the sampler and the compare loss take
+
+
+def lp_sample(rowptr: torch.Tensor, col: torch.Tensor, n_neg: int, seed: torch.Tensor) -> torch.Tensor:
+    """prompt_pretrain_sample (preprompt.py:106-126) over a CSR pattern with strictly ascending columns (a diagonal entry is
+    ignored): int64 [n, 1 + n_neg], column 0 a neighbour (or i when isolated), then n_neg distinct non-neighbours.  `seed` is
+    a one-element int64 device tensor (read on the device).  A row with neighbours and fewer than n_neg non-neighbours
+    raises ValueError, as the reference fails on it; any other bad pattern raises RagraphNativeError."""
+    L = _ready()
+    rp = _idxc(rowptr, "lp_sample.rowptr")
+    c = _idxc(col, "lp_sample.col", torch.int32)
+    sd = _idxc(seed, "lp_sample.seed")
+    n = rp.numel() - 1
+    out = torch.empty((n, 1 + n_neg), dtype=torch.int64, device=rp.device)
+    ws = _workspace(L.ragraph_lp_workspace_bytes(), rp.device)
+    rc = L.ragraph_lp_sample_i64(rp.data_ptr(), c.data_ptr() if c.numel() else None, n, c.numel(), int(n_neg), sd.data_ptr(),
+                                 out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    if rc == N.EINVAL and "non-neighbours" in N.last_error():
+        raise ValueError(N.last_error())
+    N.check(rc, "lp_sample")
+    return out
+
+
+def lp_compare_loss_fwd(h: torch.Tensor, t: torch.Tensor, temperature: float):
+    """compareloss (preprompt.py:80-103) forward: (loss [1], L [n], coef [n, S], csim [n, S], hhat [n, D], nrm [n]) -- coef the
+    backward's dL_i/dsim, csim = coef * sim, hhat = h / max(||h||, 1e-8) and nrm = ||h|| (what the backward needs)."""
+    L = _ready()
+    h = _f32c(h, "lp_compare_loss.h")
+    t = _idxc(t, "lp_compare_loss.tuples")
+    n, D = h.shape
+    if t.dim() != 2 or t.shape[0] != n:
+        raise RagraphNativeError(f"lp_compare_loss: tuples must be [{n}, 1 + n_neg], got {tuple(t.shape)}")
+    S = t.shape[1]
+    dev = h.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    Li = torch.empty(n, dtype=torch.float32, device=dev)
+    coef = torch.empty((n, S), dtype=torch.float32, device=dev)
+    csim = torch.empty((n, S), dtype=torch.float32, device=dev)
+    hhat = torch.empty((n, D), dtype=torch.float32, device=dev)
+    nrm = torch.empty(n, dtype=torch.float32, device=dev)
+    ws = _workspace(L.ragraph_lp_workspace_bytes(), dev)
+    N.check(L.ragraph_lp_compare_loss_fwd_f32(h.data_ptr(), n, D, t.data_ptr(), S, float(temperature), loss.data_ptr(),
+                                              Li.data_ptr(), coef.data_ptr(), csim.data_ptr(), hhat.data_ptr(), nrm.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), _stream()), "lp_compare_loss")
+    return loss, Li, coef, csim, hhat, nrm
+
+
+def lp_combine(x: torch.Tensor, h: torch.Tensor, nrm: torch.Tensor, beta: torch.Tensor, go: torch.Tensor,
+               inv_rows: float) -> torch.Tensor:
+    """go[0] * inv_rows * (x / N - beta * h / (N ||h||)) per row, N = max(||h||, 1e-8) (ragraph_lp_combine_f32)."""
+    L = _ready()
+    x, h = _f32c(x, "lp_combine.x"), _f32c(h, "lp_combine.h")
+    nrm, beta, go = _f32c(nrm, "lp_combine.nrm"), _f32c(beta, "lp_combine.beta"), _f32c(go, "lp_combine.go")
+    n, D = h.shape
+    out = torch.empty_like(h)
+    N.check(L.ragraph_lp_combine_f32(x.data_ptr(), h.data_ptr(), nrm.data_ptr(), beta.data_ptr(), go.data_ptr(),
+                                     float(inv_rows), n, D, out.data_ptr(), _stream()), "lp_combine")
+    return out
