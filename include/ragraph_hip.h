@@ -752,6 +752,30 @@ int ragraph_lp_compare_loss_fwd_f32(const float* h, int64_t n, int D, const int6
 int ragraph_lp_combine_f32(const float* X, const float* h, const float* nrm, const float* beta, const float* go,
                            float inv_rows, int64_t n, int D, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * EP  edge (link-prediction) flavour pre-training -- RAGraph_edge/utils/dataloader.py:140-167 (get_train_batch)
+ *
+ * The training history H(u) of user u is a CSR over users: rowptr [num_users+1] int64, items [nnz] int64, item ids strictly
+ * ascending per user (train_user_dict, the LAST line of a user winning, dataloader.py:61, repeats removed).
+ *
+ * ragraph_edge_hist_check_i64: checks such a CSR once, when it is built (one 4-byte read-back): rowptr from 0 to nnz without
+ *   decreasing, ids in [0, num_items), strictly ascending rows, and deg(u) < num_items for every u (a user whose history
+ *   covers every item makes the reference's rejection loop run forever).  RAGRAPH_EINVAL otherwise; the last case's message
+ *   says "covers every item".  ws: ragraph_lp_workspace_bytes() bytes.
+ *
+ * ragraph_edge_neg_sample_i64: negative_sampling (dataloader.py:142-152) -- it replaces the host loop that redraws
+ *   np.random.randint(0, num_items) until the item is not in train_user_dict[user].  out [B * n_negs] int64, slot
+ *   s = b * n_negs + j (triple-major, the reference's list order): an independent draw, uniform over
+ *   [0, num_items) \ H(users[b]).  r = splitmix64 hash of (seed[0], s, 0) reduced to [0, num_items - deg), mapped to the r-th
+ *   item outside H by binary search; seed[0] is read from device memory.  The history must have passed
+ *   ragraph_edge_hist_check_i64.  With check_users = 0 there is no read-back and ws may be NULL; with check_users != 0 a user
+ *   id outside [0, num_users) returns RAGRAPH_EINVAL before anything is written (one 4-byte read-back, ws as above). */
+int ragraph_edge_hist_check_i64(const int64_t* rowptr, const int64_t* items, int64_t num_users, int64_t num_items, int64_t nnz,
+                                void* ws, size_t ws_bytes, void* stream);
+int ragraph_edge_neg_sample_i64(const int64_t* rowptr, const int64_t* items, int64_t num_users, int64_t num_items,
+                                const int64_t* users, int64_t B, int n_negs, int check_users, const int64_t* seed, int64_t* out,
+                                void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

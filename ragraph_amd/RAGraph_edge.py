@@ -20,7 +20,10 @@ class RAGraph(nn.Module):
                  batch_size=4096, device="cuda", num_augment_scale=0, num_inverse_sample=0):
         """dataset: .num_users, .num_items, .edges [2E,2] int64 (src,dst, both directions), .edge_norm [2E] fp32,
         .edge_times [2E] int64 (the tensors modules/RAGraph.py:22-27 derives from the scipy graph).
-        pretrained_model: .generate() -> (user_emb, item_emb)."""
+        pretrained_model: .generate() -> (user_emb, item_emb); not used (may be None) in the phases "pretrain" and
+        "for_tune" (:93-101), whose tables are xavier-initialised -- "pretrain" trains them without a gate, "for_tune" takes
+        a pre-training checkpoint (load_state_dict) and gates every forward with a freshly drawn random gate (:177-183), as
+        the pretrained_model of "finetune" / "vanilla".  Neither builds a bank nor retrieves (:286)."""
         super().__init__()
         self.use_LoRA = bool(use_LoRA) and phase == "finetune"
         self.edge_dropout, self.weight_decay, self.emb_dropout = 0.5, 1e-4, 0.0   # utils/parse_args.py:22,27,35 defaults
@@ -39,9 +42,13 @@ class RAGraph(nn.Module):
         self.resource_keys = self.resource_values = None
         self._keys_normalized = self._index = None
         self._csr_cache = None
-        ue, ie = pretrained_model.generate()
-        self.user_embedding = nn.Parameter(ue.detach().clone().to(device))
-        self.item_embedding = nn.Parameter(ie.detach().clone().to(device))
+        if phase in ("pretrain", "for_tune"):   # :93-95: the user table, then the item table, drawn on the CPU generator
+            self.user_embedding = nn.Parameter(nn.init.xavier_uniform_(torch.empty(self.num_users, emb_size)).to(device))
+            self.item_embedding = nn.Parameter(nn.init.xavier_uniform_(torch.empty(self.num_items, emb_size)).to(device))
+        else:
+            ue, ie = pretrained_model.generate()
+            self.user_embedding = nn.Parameter(ue.detach().clone().to(device))
+            self.item_embedding = nn.Parameter(ie.detach().clone().to(device))
         if phase == "finetune":   # :163-168
             self.gating_weight = nn.Parameter(nn.init.xavier_uniform_(torch.empty(emb_size, emb_size, device=device)))
             self.gating_bias = nn.Parameter(nn.init.xavier_uniform_(torch.empty(1, emb_size, device=device)))
@@ -52,7 +59,7 @@ class RAGraph(nn.Module):
                 U, S, V = torch.svd(emb.detach())
                 setattr(self, f"{name}_embedding_A", nn.Parameter((U[:, :LoRA_rank] @ torch.diag(S[:LoRA_rank])).contiguous()))
                 setattr(self, f"{name}_embedding_B", nn.Parameter(V[:, :LoRA_rank].t().contiguous()))
-        if use_RAG:
+        if use_RAG and phase in ("vanilla", "finetune"):
             self._make_resource_graph(pretrained_model)
 
     # ---- helpers ---------------------------------------------------------------------------------------------------
@@ -76,7 +83,10 @@ class RAGraph(nn.Module):
         return self._gate_cache[1]
 
     def emb_gate(self, x):
-        """modules/RAGraph.py:168: x * sigmoid(x @ W + b) (emb_dropout p = 0 by default)."""
+        """modules/RAGraph.py:168: x * sigmoid(x @ W + b) (emb_dropout p = 0 by default); the identity in "pretrain" and
+        "vanilla", the random gate in "for_tune"."""
+        if self.phase == "for_tune":
+            return self.random_gate(x)
         if self.gating_weight is None:
             return x
         if torch.is_grad_enabled() and (x.requires_grad or self.gating_weight.requires_grad):
@@ -85,6 +95,16 @@ class RAGraph(nn.Module):
             return torch.nn.functional.dropout(out, self.emb_dropout, self.training) if self.emb_dropout > 0 else out
         z = K.linear(x, self._gate_wt(), self.gating_bias.reshape(-1))
         return K.sigmoid_gate(x, z)
+
+    def random_gate(self, x):
+        """modules/RAGraph.py:177-183: x * sigmoid(x @ W + b) with W = F.normalize(randn(D, D)), b = F.normalize(randn(1, D))
+        drawn afresh on the CPU generator at every call (W first), normalised and applied on the device."""
+        D = x.shape[1]
+        w = K.normalize_rows(torch.randn(D, D).to(x.device)).t().contiguous()   # (nn.Linear layout: x @ W = x @ (W^T)^T)
+        b = K.normalize_rows(torch.randn(1, D).to(x.device)).reshape(-1)
+        if torch.is_grad_enabled() and x.requires_grad:
+            return A.sigmoid_gate(x, A.linear(x, w, b))
+        return K.sigmoid_gate(x, K.linear(x, w, b))
 
     def _embeddings(self):
         """:269-275: the tables, plus the LoRA product A @ B when fine-tuning with LoRA."""

@@ -142,6 +142,8 @@ SIGNATURES = {
     "ragraph_lp_sample_i64": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
     "ragraph_lp_compare_loss_fwd_f32": (_i32, [_vp, _i64, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ragraph_lp_combine_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i64, _i32, _vp, _vp]),
+    "ragraph_edge_hist_check_i64": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
+    "ragraph_edge_neg_sample_i64": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -10,6 +10,14 @@
 //   * ragraph_lp_combine_f32: the backward's epilogue, s * (X / N_r - beta_r h_r / (N_r ||h_r||)), after the SpMMs of the
 //     existing kernels (own and transposed sample pattern) have made X and beta.
 // Both entries that take indices check them first (one 4-byte read-back) and return RAGRAPH_EINVAL before writing.
+//
+// Edge (link-prediction) flavour pre-training (RAGraph_edge/utils/dataloader.py:140-152, negative_sampling):
+//   * ragraph_edge_hist_check_i64: the training-history CSR (item ids strictly ascending per user) is checked once, when it
+//     is built: ids in range, order, and no user whose history covers every item (the reference's loop never ends there).
+//   * ragraph_edge_neg_sample_i64: one lane per output slot.  The reference redraws np.random.randint until the item is not
+//     in the user's history; the same law without a loop is a rank r uniform in [0, num_items - deg(u)) mapped to the r-th
+//     item outside the history by the binary search of the LP sampler.  No read-back unless the caller asks for the user
+//     ids to be checked.
 #include "common.h"
 
 namespace ragraph {
@@ -29,6 +37,18 @@ __device__ __forceinline__ uint64_t lp_draw(uint64_t seed, uint64_t row, uint64_
 }
 // uniform in [0, m) (the high half of the 128-bit product; bias < m / 2^64)
 __device__ __forceinline__ uint64_t lp_below(uint64_t h, uint64_t m) { return __umul64hi(h, m); }
+
+// rank r -> the r-th id that is not in the strictly ascending list at(0) .. at(deg - 1): r + #{j : at(j) - j <= r}
+// (at(j) - j never decreases, so a binary search counts them)
+template <class At>
+__device__ __forceinline__ int64_t lp_rank_to_id(At at, int64_t deg, int64_t r) {
+  int64_t a = 0, b = deg;
+  while (a < b) {
+    const int64_t mid = (a + b) >> 1;
+    if (at(mid) - mid <= r) a = mid + 1; else b = mid;
+  }
+  return r + a;
+}
 
 // ---- sampler ----------------------------------------------------------------------------------------------------------
 // Per row: columns in [0, n), strictly ascending; deg' = entries other than the diagonal; a row with neighbours needs
@@ -97,16 +117,54 @@ __global__ void __launch_bounds__(64) lp_sample_kernel(const int64_t* __restrict
     if (lane == 0) chosen[s] = any ? (uint32_t)j : r;
     __syncthreads();
   }
-  // rank r -> the r-th non-neighbour: r + #{j : N'(j) - j <= r} (N'(j) - j never decreases)
   for (int s = lane; s < n_neg; s += 64) {
-    const int64_t r = chosen[s];
-    int64_t a = 0, b = deg;
-    while (a < b) {
-      const int64_t mid = (a + b) >> 1;
-      if (lp_neighbour(c, pd, mid) - mid <= r) a = mid + 1; else b = mid;
-    }
-    o[1 + s] = r + a;
+    o[1 + s] = lp_rank_to_id([=](int64_t j) { return lp_neighbour(c, pd, j); }, deg, (int64_t)chosen[s]);
   }
+}
+
+// ---- edge flavour: negatives outside the user's training history -----------------------------------------------------
+// Per user: rowptr runs from 0 to nnz without decreasing, items in [0, num_items) strictly ascending, deg < num_items.
+// bad: 1 = ids / rowptr, 2 = order, 4 = a history covers every item.
+__global__ void __launch_bounds__(256) edge_hist_check_kernel(const int64_t* __restrict__ rowptr,
+                                                              const int64_t* __restrict__ items, int64_t num_users,
+                                                              int64_t num_items, int64_t nnz, int* __restrict__ bad) {
+  const int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (u >= num_users) return;
+  const int64_t e0 = rowptr[u], e1 = rowptr[u + 1];
+  if (e0 < 0 || e1 < e0 || e1 > nnz || (u == 0 && e0 != 0) || (u == num_users - 1 && e1 != nnz)) {
+    atomicOr(bad, 1);
+    return;
+  }
+  int flags = 0;
+  int64_t prev = -1;
+  for (int64_t e = e0; e < e1; ++e) {
+    const int64_t v = items[e];
+    if (v < 0 || v >= num_items) {
+      flags |= 1;
+      break;
+    }
+    if (v <= prev) flags |= 2;
+    prev = v;
+  }
+  if (!flags && e1 - e0 >= num_items) flags |= 4;
+  if (flags) atomicOr(bad, flags);
+}
+
+// Slot s = b * n_negs + j (triple-major, the reference's list order): r = lp_below(lp_draw(seed, s, 0), num_items - deg),
+// then the r-th item not in H(users[b]).
+__global__ void __launch_bounds__(256) edge_neg_sample_kernel(const int64_t* __restrict__ rowptr,
+                                                              const int64_t* __restrict__ items, int64_t num_items,
+                                                              const int64_t* __restrict__ users, int64_t total, int n_negs,
+                                                              const int64_t* __restrict__ seed_p, int64_t* __restrict__ out) {
+  const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s >= total) return;
+  const uint64_t seed = (uint64_t)seed_p[0];
+  const int64_t u = users[s / n_negs];
+  const int64_t e0 = rowptr[u];
+  const int64_t deg = rowptr[u + 1] - e0;
+  const int64_t* h = items + e0;
+  const int64_t r = (int64_t)lp_below(lp_draw(seed, (uint64_t)s, 0), (uint64_t)(num_items - deg));
+  out[s] = lp_rank_to_id([=](int64_t j) { return h[j]; }, deg, r);
 }
 
 // ---- compare loss -------------------------------------------------------------------------------------------------------
@@ -265,6 +323,67 @@ extern "C" int ragraph_lp_sample_i64(const int64_t* rowptr, const int32_t* col, 
   RG_REQUIRE(!(bad_h & 4), RAGRAPH_EINVAL, "lp_sample: a row with neighbours has fewer than n_neg=%d non-neighbours", n_neg);
   hipLaunchKernelGGL(lp_sample_kernel, dim3((unsigned)n), dim3(64), 0, st, rowptr, col, n, n_neg, seed, out);
   RG_CHECK_LAUNCH("lp_sample");
+  return RAGRAPH_OK;
+}
+
+extern "C" int ragraph_edge_hist_check_i64(const int64_t* rowptr, const int64_t* items, int64_t num_users, int64_t num_items,
+                                           int64_t nnz, void* ws, size_t ws_bytes, void* stream) {
+  RG_REQUIRE(rowptr && ws, RAGRAPH_EINVAL, "edge_hist_check: null pointer");
+  RG_REQUIRE(nnz == 0 || items, RAGRAPH_EINVAL, "edge_hist_check: null items");
+  RG_REQUIRE(num_users >= 1 && num_items >= 1 && nnz >= 0, RAGRAPH_EINVAL, "edge_hist_check: num_users=%lld num_items=%lld nnz=%lld",
+             (long long)num_users, (long long)num_items, (long long)nnz);
+  RG_REQUIRE(ws_bytes >= 256, RAGRAPH_EWORKSPACE, "edge_hist_check: workspace too small");
+  hipStream_t st = as_stream(stream);
+  int* bad = reinterpret_cast<int*>(ws);
+  if (hipMemsetAsync(bad, 0, sizeof(int), st) != hipSuccess) {
+    set_error("edge_hist_check: memset failed");
+    return RAGRAPH_EDEVICE;
+  }
+  hipLaunchKernelGGL(edge_hist_check_kernel, dim3((unsigned)cdiv(num_users, 256)), dim3(256), 0, st, rowptr, items, num_users,
+                     num_items, nnz, bad);
+  RG_CHECK_LAUNCH("edge_hist_check");
+  int bad_h = 0;
+  const int rc = lp_read_flag(bad, st, &bad_h, "edge_hist_check");
+  if (rc != RAGRAPH_OK) return rc;
+  RG_REQUIRE(!(bad_h & 1), RAGRAPH_EINVAL, "edge_hist_check: rowptr / items is not a CSR over %lld users and %lld items",
+             (long long)num_users, (long long)num_items);
+  RG_REQUIRE(!(bad_h & 2), RAGRAPH_EINVAL, "edge_hist_check: the items of a history are not strictly ascending");
+  RG_REQUIRE(!(bad_h & 4), RAGRAPH_EINVAL, "edge_hist_check: a user's history covers every item (%lld): no negative exists",
+             (long long)num_items);
+  return RAGRAPH_OK;
+}
+
+extern "C" int ragraph_edge_neg_sample_i64(const int64_t* rowptr, const int64_t* items, int64_t num_users, int64_t num_items,
+                                           const int64_t* users, int64_t B, int n_negs, int check_users, const int64_t* seed,
+                                           int64_t* out, void* ws, size_t ws_bytes, void* stream) {
+  RG_REQUIRE(rowptr && seed, RAGRAPH_EINVAL, "edge_neg_sample: null pointer");
+  RG_REQUIRE(num_users >= 1 && num_items >= 1 && B >= 0 && n_negs >= 1, RAGRAPH_EINVAL,
+             "edge_neg_sample: num_users=%lld num_items=%lld B=%lld n_negs=%d", (long long)num_users, (long long)num_items,
+             (long long)B, n_negs);
+  RG_REQUIRE(B <= ((int64_t)1 << 38) / n_negs, RAGRAPH_EUNSUPPORTED, "edge_neg_sample: B * n_negs = %lld * %d slots",
+             (long long)B, n_negs);
+  if (B == 0) return RAGRAPH_OK;
+  RG_REQUIRE(users && out, RAGRAPH_EINVAL, "edge_neg_sample: null users / out");
+  hipStream_t st = as_stream(stream);
+  if (check_users) {
+    RG_REQUIRE(ws && ws_bytes >= 256, RAGRAPH_EWORKSPACE, "edge_neg_sample: workspace too small");
+    int* bad = reinterpret_cast<int*>(ws);
+    if (hipMemsetAsync(bad, 0, sizeof(int), st) != hipSuccess) {
+      set_error("edge_neg_sample: memset failed");
+      return RAGRAPH_EDEVICE;
+    }
+    const int64_t cb = cdiv(B, 256) < 4096 ? cdiv(B, 256) : 4096;
+    hipLaunchKernelGGL(lp_index_check_kernel, dim3((unsigned)cb), dim3(256), 0, st, users, B, num_users, bad);
+    RG_CHECK_LAUNCH("edge_neg_sample(check)");
+    int bad_h = 0;
+    const int rc = lp_read_flag(bad, st, &bad_h, "edge_neg_sample");
+    if (rc != RAGRAPH_OK) return rc;
+    RG_REQUIRE(!bad_h, RAGRAPH_EINVAL, "edge_neg_sample: a user id is outside [0, %lld)", (long long)num_users);
+  }
+  const int64_t total = B * (int64_t)n_negs;
+  hipLaunchKernelGGL(edge_neg_sample_kernel, dim3((unsigned)cdiv(total, 256)), dim3(256), 0, st, rowptr, items, num_items,
+                     users, total, n_negs, seed, out);
+  RG_CHECK_LAUNCH("edge_neg_sample");
   return RAGRAPH_OK;
 }
 

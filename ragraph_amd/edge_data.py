@@ -35,10 +35,34 @@ def _read(path, has_time=True):
 
 
 class EdgeListData:
+    """The interactions of one training file.  Besides the graph tensors above, for pre-training (dataloader.py:140-167):
+    edgelist [num_edges, 2] int64 (user, item) and edge_time [num_edges] int64 -- every line's pairs in file order, repeats
+    included (the reference's self.edgelist / self.edge_time) -- and the training-history CSR hist_rowptr / hist_items of
+    train_user_dict (the negative sampler's exclusion sets), all on `device`; shuffle() and get_train_batch()."""
+
     def __init__(self, train_file, test_file=None, hour_interval=1, has_time=True, num_users=None, num_items=None,
                  device="cuda"):
-        u, i, t, self.train_user_dict = _read(train_file, has_time)
-        self.test_user_dict = _read(test_file, False)[3] if test_file else {}
+        u, i, t, train_user_dict = _read(train_file, has_time)
+        self._setup(u, i, t, train_user_dict, _read(test_file, False)[3] if test_file else {}, hour_interval, num_users,
+                    num_items, device)
+
+    @classmethod
+    def from_interactions(cls, users, items, times, test_user_dict=None, hour_interval=1, num_users=None, num_items=None,
+                          device="cuda"):
+        """The same object from interaction arrays (numpy, file order) instead of a file: each user's history is every item
+        it has (as if all of a user's pairs stood on one line)."""
+        u, i = np.asarray(users, np.int64), np.asarray(items, np.int64)
+        t = np.asarray(times, np.int64)
+        order = np.argsort(u, kind="stable")
+        us, starts = np.unique(u[order], return_index=True)
+        train_user_dict = dict(zip(us.tolist(), (x.tolist() for x in np.split(i[order], starts[1:])))) if u.size else {}
+        obj = cls.__new__(cls)
+        obj._setup(u, i, t, train_user_dict, dict(test_user_dict or {}), hour_interval, num_users, num_items, device)
+        return obj
+
+    def _setup(self, u, i, t, train_user_dict, test_user_dict, hour_interval, num_users, num_items, device):
+        self.train_user_dict = train_user_dict
+        self.test_user_dict = test_user_dict
         tu = max(self.test_user_dict) + 1 if self.test_user_dict else 0
         ti = max(max(v) for v in self.test_user_dict.values()) + 1 if self.test_user_dict else 0
         self.num_users = int(num_users or max(u.max() + 1, tu))          # dataloader.py:100-101
@@ -56,6 +80,34 @@ class EdgeListData:
             self.edges = torch.from_numpy(edges).to(device)
             self.edge_norm = torch.from_numpy(norm).to(device)
             self.edge_times = torch.from_numpy(times).to(device)
+        # pre-training (dataloader.py:140-167): the interactions in file order, and the history CSR the sampler excludes
+        self.edgelist = torch.from_numpy(np.stack([u, i], 1).astype(np.int64)).to(device)
+        self.edge_time = torch.from_numpy(step.astype(np.int64)).to(device)
+        rowptr, items = flatten_history(self.train_user_dict, self.num_users, self.num_items)
+        self.hist_rowptr, self.hist_items = torch.from_numpy(rowptr).to(device), torch.from_numpy(items).to(device)
+        if torch.device(device).type == "cuda":   # checked once (one read-back): a later batch needs none
+            from . import kernels as K
+            K.edge_hist_check(self.hist_rowptr, self.hist_items, self.num_items)
+
+    def shuffle(self):
+        """dataloader.py:164-167: one permutation of the interactions (torch.randperm on the generator of their device)."""
+        perm = torch.randperm(self.num_edges, device=self.edgelist.device)
+        self.edgelist = self.edgelist[perm]
+        self.edge_time = self.edge_time[perm]
+
+    def get_train_batch(self, start, end, n_negs=1):
+        """dataloader.py:140-162: (users, pos_items, neg_items) of interactions [start, end) (slicing semantics), as device
+        int64; neg_items [B * n_negs] triple-major, each uniform over the items outside the user's train_user_dict entry
+        (kernels.edge_neg_sample; the seed drawn on the device generator, so torch.manual_seed reproduces a batch).  No
+        synchronisation: every user of the edge list is a key of train_user_dict, whose ids were checked when the history
+        was built.  There is no CPU sampler (RagraphNativeError)."""
+        from . import kernels as K
+        ui = self.edgelist[start:end]
+        users, pos_items = ui[:, 0].contiguous(), ui[:, 1].contiguous()
+        seed = torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=users.device)
+        neg_items = K.edge_neg_sample(self.hist_rowptr, self.hist_items, self.num_items, users, n_negs, seed,
+                                      check_users=False)
+        return users, pos_items, neg_items
 
     def history_csr(self, users, device="cuda"):
         """CSR of training-history items for `users` (the mask of metrics.py:210-214)."""
@@ -64,6 +116,21 @@ class EdgeListData:
         cols = (np.concatenate([np.asarray(self.user_hist_dict.get(int(x), []), dtype=np.int64) for x in users])
                 if sum(lens) else np.zeros(0, np.int64))
         return torch.from_numpy(rowptr).to(device), torch.from_numpy(cols).to(device)
+
+
+def flatten_history(train_user_dict, num_users, num_items):
+    """train_user_dict -> the negative sampler's exclusion sets as a CSR on the host: (rowptr int64 [num_users + 1], items
+    int64), each row u the set of train_user_dict[u] (the dict already holds a user's LAST line, dataloader.py:61) with its
+    repeats removed, ascending."""
+    lens = np.fromiter((len(v) for v in train_user_dict.values()), dtype=np.int64, count=len(train_user_dict))
+    users = np.repeat(np.fromiter(train_user_dict.keys(), dtype=np.int64, count=len(train_user_dict)), lens)
+    items = np.fromiter((x for v in train_user_dict.values() for x in v), dtype=np.int64, count=int(lens.sum()))
+    if users.size and (users.min() < 0 or users.max() >= num_users or items.min() < 0 or items.max() >= num_items):
+        raise ValueError(f"train_user_dict holds ids outside {num_users} users x {num_items} items")
+    key = np.unique(users * np.int64(num_items) + items)
+    rowptr = np.zeros(num_users + 1, dtype=np.int64)
+    np.cumsum(np.bincount(key // num_items, minlength=num_users), out=rowptr[1:])
+    return rowptr, (key % num_items).astype(np.int64)
 
 
 def binorm_edges(num_users, num_items, u, i, step):

@@ -1497,3 +1497,41 @@ def lp_combine(x: torch.Tensor, h: torch.Tensor, nrm: torch.Tensor, beta: torch.
     N.check(L.ragraph_lp_combine_f32(x.data_ptr(), h.data_ptr(), nrm.data_ptr(), beta.data_ptr(), go.data_ptr(),
                                      float(inv_rows), n, D, out.data_ptr(), _stream()), "lp_combine")
     return out
+
+
+# ---- edge flavour pre-training (csrc/pretrain.hip) --------------------------------------------------------------------
+def edge_hist_check(rowptr: torch.Tensor, items: torch.Tensor, num_items: int) -> None:
+    """Validate a training-history CSR (rowptr int64 [num_users + 1], items int64, strictly ascending per user) once, when it
+    is built (ragraph_edge_hist_check_i64, one read-back).  A user whose history covers every item raises ValueError (the
+    reference's rejection loop never ends there); any other bad CSR raises RagraphNativeError."""
+    L = _ready()
+    rp = _idxc(rowptr, "edge_hist_check.rowptr")
+    it = _idxc(items, "edge_hist_check.items")
+    ws = _workspace(L.ragraph_lp_workspace_bytes(), rp.device)
+    rc = L.ragraph_edge_hist_check_i64(rp.data_ptr(), it.data_ptr() if it.numel() else None, rp.numel() - 1, int(num_items),
+                                       it.numel(), ws.data_ptr(), ws.numel(), _stream())
+    if rc == N.EINVAL and "covers every item" in N.last_error():
+        raise ValueError(N.last_error())
+    N.check(rc, "edge_hist_check")
+
+
+def edge_neg_sample(rowptr: torch.Tensor, items: torch.Tensor, num_items: int, users: torch.Tensor, n_negs: int,
+                    seed: torch.Tensor, check_users: bool = True) -> torch.Tensor:
+    """negative_sampling (RAGraph_edge/utils/dataloader.py:142-152) on the device: int64 [len(users) * n_negs], slot
+    b * n_negs + j uniform over [0, num_items) minus the history of users[b], every slot an independent draw.  The history
+    (rowptr, items) must have passed edge_hist_check.  `seed` is a one-element int64 device tensor (read on the device).
+    check_users: user ids outside [0, num_users) raise RagraphNativeError before anything is written (one read-back);
+    without it the call makes no read-back (the caller vouches for the ids)."""
+    L = _ready()
+    rp = _idxc(rowptr, "edge_neg_sample.rowptr")
+    it = _idxc(items, "edge_neg_sample.items")
+    u = _idxc(users, "edge_neg_sample.users")
+    sd = _idxc(seed, "edge_neg_sample.seed")
+    B = u.numel()
+    out = torch.empty(B * int(n_negs), dtype=torch.int64, device=rp.device)
+    ws = _workspace(L.ragraph_lp_workspace_bytes(), rp.device) if check_users else None
+    N.check(L.ragraph_edge_neg_sample_i64(rp.data_ptr(), it.data_ptr() if it.numel() else None, rp.numel() - 1,
+                                          int(num_items), u.data_ptr() if B else None, B, int(n_negs), 1 if check_users else 0,
+                                          sd.data_ptr(), out.data_ptr() if B else None, _ptr(ws),
+                                          ws.numel() if ws is not None else 0, _stream()), "edge_neg_sample")
+    return out
