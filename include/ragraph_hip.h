@@ -101,6 +101,39 @@ int ragraph_topk_cosine_bank_f32(const float* Q, int64_t B, const float* Kn, con
                                  int64_t idx_base, float* out_scores, int64_t* out_idx, void* ws, size_t ws_bytes,
                                  void* stream);
 
+/* Structure-aware retrieval: top-k of  w_struct * cos(position codes) + w_sem * cos(embeddings)
+ *   -- RAGraph_node_fewshot/ragraph_utils/ToyGraphBase.py:47-65 (cosine_similarity on resource_positions and on
+ *   resource_keys, the weighted sum, torch.topk); the node and graph flavours carry the same lines commented out with
+ *   structure_weight = 0.0 (RAGraph_node/ragraph_utils/ToyGraphBase.py:28-29,114-119).  No B x N matrix is written on the
+ *   fused path.
+ *   Q   [B,D] raw queries, normalised inside as ragraph_topk_cosine_f32 does.   Kn [N,D] bank keys, row-normalised.
+ *   Pq  [B,A] raw position codes of the queries (PositionAwareEncoder.py:6-24), normalised inside by the
+ *       ragraph_normalize_rows_f32 tree.   Pn [N,A] the bank's codes ALREADY row-normalised by ragraph_normalize_rows_f32.
+ *   A   1 <= A <= 16 (the reference uses 10 anchors).  A zero code row stays zero: its structural term is 0, never NaN.
+ *   score[b,n] = s_struct * w_struct + s_sem * w_sem:  s_struct the natural-order fp32 fmaf chain from +0 over the A
+ *       columns, s_sem the same over the D columns (the bits of ragraph_linear_f32 on the normalised rows; zero padding
+ *       of A changes no bit); the mix is two multiplies and one add, never contracted (the bits of
+ *       ragraph_axpby_f32(s_struct, w_struct, s_sem, w_sem)).
+ *   Selection: canonical (score descending, index ascending), idx_base added; 1 <= k <= min(N, RAGRAPH_TOPK_ORDERED_MAX):
+ *       the bits of ragraph_topk_rows_f32 / ragraph_topk_rows_large_f32 on the materialised mixed matrix.
+ *   Fused path: D in {64,128,256}, k <= 32, and a shape ragraph_topk_cosine_f32 would stream too:
+ *       the wave-streaming kernel for B <= 128, the 256-queries-per-workgroup tile kernel above.  The semantic products
+ *       come off the MFMA stream; a key's codes are read, and its exact mixed score computed, only when
+ *       s_sem * w_sem + |w_struct| (rounded up) reaches the query's current k-th best score -- both code rows are unit or
+ *       zero rows, so no other key can be selected (ragraph_amd/csrc/topk_cosine.hip).  Its speed therefore depends on
+ *       the weights: a dominant structural term lets many keys through the bound (w_sem = 0: all of them).
+ *   Everything else (other widths, 32 < k, small score matrices, banks beyond one dense launch) takes
+ *       materialised slabs inside ~1 GiB of the workspace in key chunks: dense kernel x 2, mix, ordered selection,
+ *       canonical merge -- the same bits.  (Banks beyond one dense launch with 64 < k: a merged score of -0 reads +0.)
+ *   RAGRAPH_EINVAL before anything touches the device: null pointer, A outside 1..16, k outside its range, a weight that is not finite,
+ *   ws_bytes < ragraph_topk_cosine_mix_workspace_bytes().  RAGRAPH_EUNSUPPORTED: shards of >= 2^31 rows.  The call never
+ *   synchronises or reads back and can be captured into a HIP graph.
+ */
+size_t ragraph_topk_cosine_mix_workspace_bytes(int64_t B, int64_t N, int D, int A, int k);
+int ragraph_topk_cosine_mix_f32(const float* Q, int64_t B, const float* Kn, int64_t N, int D, const float* Pq,
+                                const float* Pn, int A, float w_struct, float w_sem, int k, int64_t idx_base,
+                                float* out_scores, int64_t* out_idx, void* ws, size_t ws_bytes, void* stream);
+
 /* a1, large batches: the same result through a bf16 MFMA filter (ragraph_amd/csrc/topk_filter.hip).
  *   Exact by construction: (1) a lower bound of every query's final k-th best score -- the k-th exact score over a sample
  *   of the bank, or, for banks of >= 8192 keys, min over k parts of a prefix of the best approximate score in the part,

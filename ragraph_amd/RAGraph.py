@@ -53,9 +53,16 @@ class RAGraph(nn.Module):
 
     query_shard = None  # ragraph_amd.sharded.QueryShard: answer only this rank's rows of the batch (inference)
 
-    def forward(self, features, adj):
+    def forward(self, features, adj, anchors=None):
+        """`anchors`: the anchor nodes of the query graph's position codes, used only when
+        toy_graph_base.structure_weight != 0 (drawn on the host generator when not given, PositionAwareEncoder.py:11 --
+        a captured forward must pass them)."""
         g = as_csr(adj)
         tgb = self.toy_graph_base
+        mixed = getattr(tgb, "structure_weight", 0.0) != 0
+        if mixed and (self.query_shard is not None or hasattr(tgb, "retrieve_reduced_rows")):
+            raise K.RagraphNativeError("structure-aware retrieval (structure_weight != 0) runs on one GPU with the whole "
+                                       "bank: the query-sharded and key-sharded forwards do not mix position codes")
         if self.query_shard is not None and not self.training and self.flavour == "node":
             hybrid = (getattr(tgb, "values_replicated", False) and hasattr(tgb, "retrieve_reduced_rows")
                       and (tgb.collective or tgb.emulate_world > 1))
@@ -68,6 +75,9 @@ class RAGraph(nn.Module):
             raise K.RagraphNativeError("noisy fine-tuning draws its noise on the host generator, as the reference does: "
                                        "its step cannot be captured in a HIP graph (train it eagerly)")
         queries = self._queries(pretrain_embedddings, g)
+        # structure-aware retrieval: the query rows' position codes (ToyGraphBase.py:49-50 of the few-shot flavour); raises
+        # here, before any retrieval kernel, when the bank holds no codes
+        pos = tgb.search_positions(g, None, anchors) if mixed else None
         if self.query_shard is not None and not self.training and self.flavour == "node":
             if (getattr(tgb, "values_replicated", False) and hasattr(tgb, "retrieve_reduced_rows")
                     and (tgb.collective or tgb.emulate_world > 1)):
@@ -97,14 +107,17 @@ class RAGraph(nn.Module):
                 and os.environ.get("RAGRAPH_GATHER_MIX", "1") != "0"):   # (=0: the separate entries, A/B)
             # a large inference forward: the winners' value sum goes straight into the prompt fusion (:48-49 + :53 in one
             # launch -- the [n, D] sum is never written, the axpby launch is gone); same bits as the separate entries below
-            _, idx = tgb.topk(queries, tgb.retrieve_num)                                       # :43
+            _, idx = tgb.topk(queries, tgb.retrieve_num, pos) if mixed else tgb.topk(queries, tgb.retrieve_num)   # :43
             main.wait_stream(side)
             query_embeddings.record_stream(main)
             hidden, rag_label = K.gather_reduce_mix(tgb.resource_values, tgb.resource_labels, idx, query_embeddings,
                                                     1 - self.retrieve_weight, self.retrieve_weight)
             return A.softmax_mix(self.decoder(hidden), rag_label, self.label_weight)           # :54-57
         if add_noise:
-            rag_embedding, rag_label = tgb.retrieve_reduced_noisy(queries)                     # :43,48-49 (noise branch)
+            rag_embedding, rag_label = (tgb.retrieve_reduced_noisy(queries, search_positions=pos) if mixed
+                                        else tgb.retrieve_reduced_noisy(queries))             # :43,48-49 (noise branch)
+        elif mixed:
+            rag_embedding, rag_label, _ = tgb.retrieve_reduced(queries, search_positions=pos)
         else:
             rag_embedding, rag_label, _ = tgb.retrieve_reduced(queries)                        # :43,48-49 fused
         if not self.finetune:

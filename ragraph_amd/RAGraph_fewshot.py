@@ -2,9 +2,10 @@
 shortest paths to random anchors) with the semantic cosine, the decoder is the encoder's second GCN layer, and the
 label term is a prototype-logit lookup.
 
-Scores are materialised here (B ~ 40 query nodes x a few thousand bank rows) exactly as the reference does
-(ToyGraphBase.py:47-61): two cosine matrices on the HIP linear kernel, mixed with the uncontracted axpby kernel, then
-the HIP top-k over rows.  Few-shot graphs are tiny; the fused streaming kernel is for the 1M-key regime.
+Retrieval is one call of the mixed top-k (K.topk_cosine_mix): small score matrices (B ~ 40 query nodes x a few thousand
+bank rows) are materialised inside it exactly as the reference does (ToyGraphBase.py:47-61: two cosine matrices on the
+HIP linear kernel, the uncontracted mix, the HIP top-k over rows), banks too large for that stream through the fused
+kernels -- the same bits.  `similarity_scores` keeps the materialised matrix for callers that want it.
 """
 from __future__ import annotations
 
@@ -78,8 +79,11 @@ class ToyGraphBaseFewShot(ToyGraphBase):
 
     def retrieve(self, search_keys, search_adj, add_noise: bool, anchors=None):
         retrieve_num = 2 * self.retrieve_num if add_noise else self.retrieve_num
-        scores = self.similarity_scores(search_keys, search_adj, anchors)
-        _, idx = K.topk_rows(scores, retrieve_num)                                   # :64
+        if self.structure_weight != 0:   # :49-64 in one call, no [B, N] matrix in this module
+            pos = self.search_positions(search_adj, None, anchors)
+            _, idx = self.topk(search_keys, retrieve_num, pos)
+        else:   # (a caller that zeroed the structural weight: the reference still scales the scores, :61)
+            _, idx = K.topk_rows(self.similarity_scores(search_keys, search_adj, anchors), retrieve_num)
         rag_embeddings = K.gather_rows(self.resource_values, idx)
         rag_labels = K.gather_rows(self.resource_labels, idx)
         if add_noise:                                                                # :70-76

@@ -110,10 +110,40 @@ struct TopkParams {
   const int64_t* hrp;
   const int* hcol;
   float mask_value;
+  // structure-aware mixed score (MIX instantiations only, ragraph_topk_cosine_mix_f32): score = s_struct * w_struct +
+  // s_sem * w_sem with s_struct the fmaf chain over the A columns of the two NORMALISED code rows.  The MFMA stream
+  // still produces s_sem alone; a key can only matter when  s_sem * w_sem + mix_slack >= (k-th best score), and only
+  // such keys have their code row read and their mixed score computed (see mix_bound / mix_score).
+  const float* Pq = nullptr;  // [B,A] normalised query codes
+  const float* Pn = nullptr;  // [N,A] normalised bank codes
+  int A = 0;
+  float w_struct = 0.f, w_sem = 0.f;
+  float mix_slack = 0.f;              // >= |s_struct * w_struct| for every pair of unit-or-zero rows
   int ablate;              // DIAGNOSTIC ONLY (env RAGRAPH_TOPK_ABLATE, results invalid when non-zero): bit0 skip the
                            // top-k epilogue, bit1 skip global loads + LDS writes, bit2 skip the stage barrier (both
                            // 2-slot variant); DMA ring: bit4 skip the DMA, bit5 skip the FULL / FREE counters
 };
+
+// MIX: an upper bound of the mixed score of a key whose semantic product is s.  fl(t + a) is monotone in a, and
+// |fl(s_struct * w_struct)| <= mix_slack, so  fl(fl(s * w_sem) + mix_slack) >= fl(fl(s * w_sem) + fl(s_struct * w_struct))
+// = the score, in floating point and not only in exact arithmetic; fl(s * w_sem) is monotone in s as well (rising for
+// w_sem >= 0, falling below), so the bound of a tile's largest (smallest) product bounds the whole tile.  Without MIX: the
+// product itself.
+template <bool MIX>
+__device__ __forceinline__ float mix_bound(float s, const TopkParams& p) {
+  if constexpr (MIX) return __fadd_rn(__fmul_rn(s, p.w_sem), p.mix_slack);
+  else return s;
+}
+
+// MIX: the mixed score of (query code row pq, key idx) given the semantic product: the natural-order fmaf chain from +0
+// over the A code columns (the bits of ragraph_linear_f32 on the normalised rows, and of an MFMA over zero-padded
+// columns), then two multiplies and one add that the compiler may not contract (the bits of ragraph_axpby_f32).
+__device__ __forceinline__ float mix_score(const float* __restrict__ pq, int idx, float sem, const TopkParams& p) {
+  const float* __restrict__ pn = p.Pn + (int64_t)idx * p.A;
+  float st = 0.f;
+  for (int a = 0; a < p.A; ++a) st = fmaf(pn[a], pq[a], st);
+  return __fadd_rn(__fmul_rn(st, p.w_struct), __fmul_rn(sem, p.w_sem));
+}
 
 template <int D>
 struct TopkCfg {
@@ -153,8 +183,9 @@ __device__ unsigned long long g_topk_timing[8];
 #define RG_T(var_)
 #endif
 
-template <int D, int RING, bool MASKED = false>
+template <int D, int RING, bool MASKED = false, bool MIX = false>
 __global__ void __launch_bounds__(512, 2) topk_stream_kernel(TopkParams p) {
+  static_assert(!(MASKED && MIX), "the masked kernels score raw inner products");
   using C = TopkCfg<D>;
   // ONE __shared__ object; everything below is an offset from it so every access stays a ds_* instruction.
   extern __shared__ float4 smem4[];
@@ -294,7 +325,14 @@ __global__ void __launch_bounds__(512, 2) topk_stream_kernel(TopkParams p) {
       // MASKED: while the k-th score is still at or below mask_value (list warm-up, or a query with fewer than k
       // unexcluded keys) every key is a candidate, since an excluded key would enter at mask_value
       const bool all_cand = MASKED && p.mask_value >= thr;
-      if (__any(m >= thr || all_cand)) {
+      if constexpr (MIX) {
+        if (p.w_sem < 0.f) {  // (wave-uniform) a negative semantic weight: the tile's SMALLEST product has the largest bound
+          m = acc[0];
+#pragma unroll
+          for (int r = 1; r < 16; ++r) m = fminf(m, acc[r]);
+        }
+      }
+      if (__any(mix_bound<MIX>(m, p) >= thr || all_cand)) {
         // rare path (~k ln(n/k) times per query over the stream): the wave inserts its candidates one at a time with
         // all 64 lanes cooperating on each insert (sorted list: one ballot for the position, one shuffle for the shift).
         const int key_base = (int)(n_begin + (int64_t)s * C::STAGE_KEYS + t * 32) + 4 * h;
@@ -302,7 +340,25 @@ __global__ void __launch_bounds__(512, 2) topk_stream_kernel(TopkParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int idx = key_base + (r & 3) + 8 * (r >> 2);
-          if ((acc[r] >= thr || all_cand) && idx < (int)n_end) mask |= 1u << r;
+          if ((mix_bound<MIX>(acc[r], p) >= thr || all_cand) && idx < (int)n_end) mask |= 1u << r;
+        }
+        if constexpr (MIX) {
+          // every lane replaces the semantic product of each of its candidates by the exact mixed score (A + A loads
+          // from the L2-resident code rows, lanes in parallel) and keeps the ones that reach the threshold: from here
+          // on acc[r] of a set mask bit IS the score, and the insert code below is the semantic kernel's
+          const float* pq = p.Pq + min(q0 + wave * 32 + j, p.B - 1) * p.A;
+          unsigned todo = mask;
+          while (todo) {
+            const int r0 = __ffs(todo) - 1;
+            float sem = acc[0];
+#pragma unroll
+            for (int r = 1; r < 16; ++r) sem = (r0 == r) ? acc[r] : sem;
+            const float sc = mix_score(pq, key_base + (r0 & 3) + 8 * (r0 >> 2), sem, p);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = (r0 == r) ? sc : acc[r];
+            if (sc < thr) mask &= ~(1u << r0);
+            todo &= todo - 1;
+          }
         }
         // lanes of query row qrow(j) drop candidates the (tightened) threshold excludes
 #define RG_TOPK_PRUNE()                                                                           \
@@ -541,8 +597,9 @@ struct SmallCfg {
   static size_t lds_bytes(int k) { return (size_t)WAVES * (sizeof(float) * TILE_FLOATS + (size_t)k * 16 * 8); }
 };
 
-template <int D, bool MASKED = false>
+template <int D, bool MASKED = false, bool MIX = false>
 __global__ void __launch_bounds__(512, 2) topk_smallb_kernel(TopkParams p) {
+  static_assert(!(MASKED && MIX), "the masked kernels score raw inner products");
   using C = SmallCfg<D>;
   extern __shared__ float4 smem4[];
   float* smem = reinterpret_cast<float*>(smem4);
@@ -637,16 +694,32 @@ __global__ void __launch_bounds__(512, 2) topk_smallb_kernel(TopkParams p) {
 #pragma unroll
       for (int m = 0; m < D / 4; ++m) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * m], breg[m], acc, 0, 0, 0);
 
-      const float mx = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3]));
+      float mx = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3]));
+      if constexpr (MIX) {
+        if (p.w_sem < 0.f) mx = fminf(fminf(acc[0], acc[1]), fminf(acc[2], acc[3]));  // see the tile kernel
+      }
       // MASKED: at or below mask_value every key is a candidate (an excluded one enters at mask_value)
       const bool all_cand = MASKED && p.mask_value >= thr;
-      if (__any(mx >= thr || all_cand)) {
+      if (__any(mix_bound<MIX>(mx, p) >= thr || all_cand)) {
         // rare path: the wave inserts the candidates one at a time, all 64 lanes cooperating on each insert
         const int key_base = (int)(t * C::TILE_KEYS) + sub * 16 + 4 * sl;
         unsigned mask = 0;
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if ((acc[r] >= thr || all_cand) && key_base + r < (int)p.N) mask |= 1u << r;
+          if ((mix_bound<MIX>(acc[r], p) >= thr || all_cand) && key_base + r < (int)p.N) mask |= 1u << r;
+        if constexpr (MIX) {  // candidates' products -> exact mixed scores, as in the tile kernel
+          const float* pq = p.Pq + min(qbase + j, p.B - 1) * p.A;
+          unsigned todo = mask;
+          while (todo) {
+            const int r0 = __ffs(todo) - 1;
+            const float sem = r0 == 1 ? acc[1] : r0 == 2 ? acc[2] : r0 == 3 ? acc[3] : acc[0];
+            const float sc = mix_score(pq, key_base + r0, sem, p);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[r] = (r0 == r) ? sc : acc[r];
+            if (sc < thr) mask &= ~(1u << r0);
+            todo &= todo - 1;
+          }
+        }
 #define RG_SMALL_PRUNE()                                                                          \
   do {                                                                                            \
     if (!(MASKED && p.mask_value >= thr)) {                                                       \
@@ -990,12 +1063,12 @@ static TopkPlan plan_topk(int64_t B, int64_t N, int D, int k) {
   return pl;
 }
 
-template <int D, int RING, bool MASKED = false>
+template <int D, int RING, bool MASKED = false, bool MIX = false>
 static int launch_topk_ring(const TopkParams& p, int64_t qtiles, hipStream_t st) {
   using C = TopkCfg<D>;
   const size_t lds = C::lds_bytes(p.k, RING);
   static DeviceOnce lds_once;  // per device (common.h)
-  if (hipError_t e = raise_dynamic_lds(lds_once, &topk_stream_kernel<D, RING, MASKED>, 160 * 1024); e != hipSuccess) {
+  if (hipError_t e = raise_dynamic_lds(lds_once, &topk_stream_kernel<D, RING, MASKED, MIX>, 160 * 1024); e != hipSuccess) {
     set_error("topk_cosine: cannot raise dynamic LDS limit: %s", hipGetErrorString(e));
     return RAGRAPH_EDEVICE;
   }
@@ -1004,7 +1077,7 @@ static int launch_topk_ring(const TopkParams& p, int64_t qtiles, hipStream_t st)
   unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_topk_timing), zero, sizeof(zero));
 #endif
-  hipLaunchKernelGGL((topk_stream_kernel<D, RING, MASKED>), dim3((unsigned)grid), dim3(C::THREADS), lds, st, p);
+  hipLaunchKernelGGL((topk_stream_kernel<D, RING, MASKED, MIX>), dim3((unsigned)grid), dim3(C::THREADS), lds, st, p);
   RG_CHECK_LAUNCH("topk_cosine");
 #ifdef RG_TOPK_TIMING
   (void)hipDeviceSynchronize();
@@ -1020,7 +1093,7 @@ static int launch_topk_ring(const TopkParams& p, int64_t qtiles, hipStream_t st)
   return RAGRAPH_OK;
 }
 
-template <int D, bool MASKED = false>
+template <int D, bool MASKED = false, bool MIX = false>
 static int launch_topk(const TopkParams& p, int64_t qtiles, hipStream_t st) {
   // the barrier-free 3-slot ring needs 3 x 33 KB of stages next to the 2 KB * k of lists in the 160 KB LDS
   static const int ring_env = [] {  // diagnostic override (read once): RAGRAPH_TOPK_RING = 2, 3 or 4
@@ -1029,24 +1102,24 @@ static int launch_topk(const TopkParams& p, int64_t qtiles, hipStream_t st) {
   }();
   const bool fits3 = TopkCfg<D>::lds_bytes(p.k, 3) <= 160 * 1024;
   const bool want3 = ring_env >= 3;
-  if constexpr (D == 256 && !MASKED) {  // (the masked kernels read raw item rows: no packed copy)
+  if constexpr (D == 256 && !MASKED && !MIX) {  // (the masked kernels read raw item rows: no packed copy; nor has the mixed call one)
     const bool fits4 = TopkCfg<D>::lds_bytes(p.k, 4) <= 160 * 1024;
     if (p.Kp && fits4 && ring_env != 2 && ring_env != 3 && !(p.ablate & 6)) return launch_topk_ring<D, 4>(p, qtiles, st);
   }
-  if (fits3 && want3 && !(p.ablate & 6)) return launch_topk_ring<D, 3, MASKED>(p, qtiles, st);
-  return launch_topk_ring<D, 2, MASKED>(p, qtiles, st);
+  if (fits3 && want3 && !(p.ablate & 6)) return launch_topk_ring<D, 3, MASKED, MIX>(p, qtiles, st);
+  return launch_topk_ring<D, 2, MASKED, MIX>(p, qtiles, st);
 }
 
-template <int D, bool MASKED = false>
+template <int D, bool MASKED = false, bool MIX = false>
 static int launch_smallb(const TopkParams& p, hipStream_t st) {
   using C = SmallCfg<D>;
   const size_t lds = C::lds_bytes(p.k);
   static DeviceOnce lds_once;  // per device (common.h)
-  if (hipError_t e = raise_dynamic_lds(lds_once, &topk_smallb_kernel<D, MASKED>, 160 * 1024); e != hipSuccess) {
+  if (hipError_t e = raise_dynamic_lds(lds_once, &topk_smallb_kernel<D, MASKED, MIX>, 160 * 1024); e != hipSuccess) {
     set_error("topk_cosine(small batch): cannot raise dynamic LDS limit: %s", hipGetErrorString(e));
     return RAGRAPH_EDEVICE;
   }
-  hipLaunchKernelGGL((topk_smallb_kernel<D, MASKED>), dim3((unsigned)(p.nsplit * p.ngroups)), dim3(512), lds, st, p);
+  hipLaunchKernelGGL((topk_smallb_kernel<D, MASKED, MIX>), dim3((unsigned)(p.nsplit * p.ngroups)), dim3(512), lds, st, p);
   RG_CHECK_LAUNCH("topk_cosine(small batch)");
   return RAGRAPH_OK;
 }
@@ -1345,6 +1418,238 @@ extern "C" int ragraph_topk_cosine_bank_f32(const float* Q, int64_t B, const flo
   if (streaming)  // per-workgroup partials of the streaming kernel are sorted
     return launch_merge_sorted<int>(part_s, part_i, pl.nsplit, B, k, (int64_t)k, (int64_t)pl.nsplit * k, idx_base,
                                     out_scores, out_idx, st);
+  return launch_select<int>(part_s, part_i, pl.nsplit, B, k, (int64_t)k, (int64_t)pl.nsplit * k, idx_base, out_scores,
+                            out_idx, st);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Structure-aware retrieval: top-k of  w_struct * cos(position codes) + w_sem * cos(embeddings)
+// (RAGraph_node_fewshot/ragraph_utils/ToyGraphBase.py:47-65) without the B x N matrices.
+//
+// Form of the fused path: the MIX instantiations of the two fp32 kernels above.  The MFMA stream is the semantic
+// kernel's, untouched: it produces s_sem.  Both code rows are unit or zero rows, so |s_struct| <= 1 (+ rounding) and
+//   score <= fl(fl(s_sem * w_sem) + mix_slack),   mix_slack >= |w_struct| (1 + 2^-10),
+// which holds in floating point because rounding is monotone (mix_bound).  A tile whose largest product cannot reach the
+// list's k-th score under that bound is skipped exactly as the semantic kernel skips it; for the keys that can, the lane
+// that holds the product reads the key's A codes, runs the A-step fmaf chain and the three-op mix (mix_score), and the
+// exact score replaces the product before the unchanged insert code runs.  Nothing approximate is ever compared with a
+// stored score, so the lists hold the bits of linear x 2 + axpby, and the selection is the canonical one.
+// Per key and query tile of 256: the D * 4 key bytes and D / 2 MFMA 32x32x2 steps per 32 keys of the semantic kernel, + 2
+// vector ops per score (multiply, add of the bound; the compare was there), + for a surviving candidate only 4 A bytes of
+// bank codes (an L2 hit: the N x A code table is 6 % of the bank at A = 16, D = 256), A fmaf and 3 ops.  No code bytes
+// and no matrix work for a key that cannot matter -- the MFMA alternative (16 padded code columns as a second
+// accumulator set) costs + 6.25 % key bytes and MFMA steps and 48 vector ops per tile for EVERY key.
+// What the bound costs: it is as tight as |w_struct| is small against the spread of w_sem * s_sem.  At the reference's
+// (0.001, 0.999) it is the semantic kernel's own threshold to three digits; when the structural term dominates, many keys
+// survive it and the call slows down towards one code-row read per (query, key) -- still exact; w_sem = 0 is that limit
+// (every key survives: a caller who wants the structural ranking alone has an A-column cosine top-k, not this call).
+// ------------------------------------------------------------------------------------------------------------------
+namespace ragraph {
+// S[i] = T[i] * wt + S[i] * ws: ragraph_axpby_f32(T, wt, S, ws) written over its second operand
+__global__ void __launch_bounds__(256) mix_slab_kernel(float* __restrict__ S, const float* __restrict__ T, float wt,
+                                                       float ws, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
+    S[i] = __fadd_rn(__fmul_rn(T[i], wt), __fmul_rn(S[i], ws));
+}
+
+static bool mix_fused(int64_t B, int64_t N, int D, int k) { return fused_width(D) && k <= 32 && !use_slab(B, N, D); }
+
+// materialised path: two score slabs of `rows` queries x one key chunk inside ~1 GiB; key chunks of at most one dense launch
+struct MixSlab {
+  int64_t rows, G, nc;
+  size_t qn, pqn, s, t, cand, part_s, part_i, sel, total;  // byte offsets / sizes
+};
+
+static MixSlab mix_slab_layout(int64_t B, int64_t N, int D, int A, int k) {
+  MixSlab m;
+  m.G = slab_large_chunks(N);
+  m.nc = cdiv(N, m.G);
+  int64_t rows = ((int64_t)1 << 29) / (4 * m.nc);  // two slabs of ~512 MiB
+  if (rows < 64) rows = 64;
+  m.rows = rows < B ? rows : B;
+  size_t o = 0;
+  m.qn = o;
+  o += align_up((size_t)B * D * sizeof(float), 256);
+  m.pqn = o;
+  o += align_up((size_t)B * A * sizeof(float), 256);
+  m.s = o;
+  o += align_up((size_t)m.rows * m.nc * sizeof(float), 256);
+  m.t = o;
+  o += align_up((size_t)m.rows * m.nc * sizeof(float), 256);
+  m.cand = m.part_s = m.part_i = m.sel = o;
+  if (k > RAGRAPH_TOPK_MAX) {
+    size_t sel = large_select_ws_bytes(m.rows, m.nc, k);
+    if (m.G > 1) {
+      o += align_up((size_t)m.rows * m.G * k * sizeof(unsigned long long), 256);
+      const size_t merge = large_select_ws_bytes(m.rows, m.G * k, k);
+      if (merge > sel) sel = merge;
+    }
+    m.sel = o;
+    o += sel;
+  } else if (m.G > 1) {
+    o += align_up((size_t)m.G * m.rows * k * sizeof(float), 256);
+    m.part_i = o;
+    o += align_up((size_t)m.G * m.rows * k * sizeof(int64_t), 256);
+  }
+  m.total = o;
+  return m;
+}
+}  // namespace ragraph
+
+extern "C" size_t ragraph_topk_cosine_mix_workspace_bytes(int64_t B, int64_t N, int D, int A, int k) {
+  if (B < 1 || N < 1 || k < 1 || D < 1 || A < 1 || A > 16 || k > RAGRAPH_TOPK_ORDERED_MAX) return 0;
+  if (!mix_fused(B, N, D, k)) return mix_slab_layout(B, N, D, A, k).total;
+  const TopkPlan pl = plan_topk(B, N, D, k);
+  return pl.qn_bytes + pl.part_s_bytes + pl.part_i_bytes + align_up((size_t)B * A * sizeof(float), 256);
+}
+
+extern "C" int ragraph_topk_cosine_mix_f32(const float* Q, int64_t B, const float* Kn, int64_t N, int D, const float* Pq,
+                                           const float* Pn, int A, float w_struct, float w_sem, int k, int64_t idx_base,
+                                           float* out_scores, int64_t* out_idx, void* ws, size_t ws_bytes, void* stream) {
+  RG_REQUIRE(Q && Kn && Pq && Pn && out_scores && out_idx && ws, RAGRAPH_EINVAL, "topk_cosine_mix: null pointer");
+  RG_REQUIRE(B >= 1 && N >= 1 && D >= 1, RAGRAPH_EINVAL, "topk_cosine_mix: B=%lld N=%lld D=%d must be >= 1", (long long)B,
+             (long long)N, D);
+  RG_REQUIRE(A >= 1 && A <= 16, RAGRAPH_EINVAL, "topk_cosine_mix: A=%d not in [1,16]", A);
+  RG_REQUIRE(k >= 1 && k <= N && k <= RAGRAPH_TOPK_ORDERED_MAX, RAGRAPH_EINVAL,
+             "topk_cosine_mix: k=%d out of range for N=%lld (1 <= k <= min(N, %d))", k, (long long)N, RAGRAPH_TOPK_ORDERED_MAX);
+  RG_REQUIRE(aligned16(Q) && aligned16(Kn) && aligned16(ws), RAGRAPH_EINVAL, "topk_cosine_mix: Q, Kn, ws must be 16-B aligned");
+  RG_REQUIRE(fabsf(w_struct) <= 3.0e38f && fabsf(w_sem) <= 3.0e38f, RAGRAPH_EINVAL, "topk_cosine_mix: a weight is not finite");
+  RG_REQUIRE(N < (int64_t)INT_MAX - 1024, RAGRAPH_EUNSUPPORTED, "topk_cosine_mix: shard rows must fit int32");
+  hipStream_t st = as_stream(stream);
+  char* w = static_cast<char*>(ws);
+
+  if (!mix_fused(B, N, D, k)) {
+    // materialised slabs: dense kernel x 2, mix, ordered selection, canonical merge over key chunks
+    const MixSlab m = mix_slab_layout(B, N, D, A, k);
+    RG_REQUIRE(ws_bytes >= m.total, RAGRAPH_EINVAL, "topk_cosine_mix: workspace %zu < %zu", ws_bytes, m.total);
+    RG_REQUIRE(k > RAGRAPH_TOPK_MAX || m.G * k <= 4096, RAGRAPH_EUNSUPPORTED,
+               "topk_cosine_mix: %lld key chunks x k=%d exceed the merge", (long long)m.G, k);
+    float* Qn = reinterpret_cast<float*>(w + m.qn);
+    float* Pqn = reinterpret_cast<float*>(w + m.pqn);
+    float* S = reinterpret_cast<float*>(w + m.s);
+    float* T = reinterpret_cast<float*>(w + m.t);
+    unsigned long long* cand = reinterpret_cast<unsigned long long*>(w + m.cand);
+    float* part_s = reinterpret_cast<float*>(w + m.part_s);
+    int64_t* part_i = reinterpret_cast<int64_t*>(w + m.part_i);
+    void* sel_ws = w + m.sel;
+    const bool large = k > RAGRAPH_TOPK_MAX;
+    int rc = ragraph_normalize_rows_f32(Q, B, D, Qn, stream);
+    if (rc == RAGRAPH_OK) rc = ragraph_normalize_rows_f32(Pq, B, A, Pqn, stream);
+    for (int64_t b0 = 0; rc == RAGRAPH_OK && b0 < B; b0 += m.rows) {
+      const int64_t nb = (B - b0 < m.rows) ? B - b0 : m.rows;
+      for (int64_t g = 0; rc == RAGRAPH_OK && g < m.G; ++g) {
+        const int64_t n0 = g * m.nc, nn = (N - n0 < m.nc) ? N - n0 : m.nc;
+        rc = ragraph_linear_f32(Qn + b0 * D, nb, D, Kn + n0 * D, nn, nullptr, RAGRAPH_ACT_NONE, 0.f, S, stream);
+        if (rc == RAGRAPH_OK)
+          rc = ragraph_linear_f32(Pqn + b0 * A, nb, A, Pn + n0 * A, nn, nullptr, RAGRAPH_ACT_NONE, 0.f, T, stream);
+        if (rc != RAGRAPH_OK) break;
+        {
+          int64_t blocks = cdiv(nb * nn, 256);
+          if (blocks > 2048) blocks = 2048;
+          hipLaunchKernelGGL(mix_slab_kernel, dim3((unsigned)blocks), dim3(256), 0, st, S, T, w_struct, w_sem, nb * nn);
+          RG_CHECK_LAUNCH("topk_cosine_mix(mix)");
+        }
+        float* os = out_scores + b0 * k;
+        int64_t* oi = out_idx + b0 * k;
+        if (large) {
+          if (m.G == 1)
+            rc = large_select(S, nullptr, nb, N, N, k, 0u, S, N, idx_base, nullptr, 0, os, oi, sel_ws, st);
+          else  // (a merged score is decoded from its key: a mixed score of -0 comes back as +0)
+            rc = large_select(S, nullptr, nb, nn, nn, k, (unsigned)n0, nullptr, 0, 0, cand + g * k, m.G * k, nullptr, nullptr,
+                              sel_ws, st);
+        } else if (m.G == 1) {
+          rc = ragraph_topk_rows_f32(S, nb, N, N, k, os, oi, stream);
+        } else {
+          rc = ragraph_topk_rows_f32(S, nb, nn, nn, k, part_s + g * nb * k, part_i + g * nb * k, stream);
+          if (rc == RAGRAPH_OK && n0 != 0) {
+            hipLaunchKernelGGL(add_idx_base_kernel, dim3((unsigned)cdiv(nb * k, 256)), dim3(256), 0, st, part_i + g * nb * k,
+                               nb * k, n0);
+            RG_CHECK_LAUNCH("topk_cosine_mix(chunk base)");
+          }
+        }
+      }
+      if (rc == RAGRAPH_OK && m.G > 1) {
+        if (large)
+          rc = large_select(nullptr, cand, nb, m.G * k, m.G * k, k, 0u, nullptr, 0, idx_base, nullptr, 0, out_scores + b0 * k,
+                            out_idx + b0 * k, sel_ws, st);
+        else
+          rc = launch_select<int64_t>(part_s, part_i, (int)m.G, nb, k, nb * k, (int64_t)k, (int64_t)0, out_scores + b0 * k,
+                                      out_idx + b0 * k, st);
+      }
+    }
+    if (rc == RAGRAPH_OK && !large && idx_base != 0) {
+      hipLaunchKernelGGL(add_idx_base_kernel, dim3((unsigned)cdiv(B * k, 256)), dim3(256), 0, st, out_idx, B * k, idx_base);
+      RG_CHECK_LAUNCH("topk_cosine_mix(add base)");
+    }
+    return rc;
+  }
+
+  const TopkPlan pl = plan_topk(B, N, D, k);
+  const size_t pqn_bytes = align_up((size_t)B * A * sizeof(float), 256);
+  RG_REQUIRE(ws_bytes >= pl.qn_bytes + pl.part_s_bytes + pl.part_i_bytes + pqn_bytes, RAGRAPH_EINVAL,
+             "topk_cosine_mix: workspace %zu < %zu", ws_bytes, pl.qn_bytes + pl.part_s_bytes + pl.part_i_bytes + pqn_bytes);
+  float* Qn = reinterpret_cast<float*>(w);
+  float* part_s = reinterpret_cast<float*>(w + pl.qn_bytes);
+  int* part_i = reinterpret_cast<int*>(w + pl.qn_bytes + pl.part_s_bytes);
+  float* Pqn = reinterpret_cast<float*>(w + pl.qn_bytes + pl.part_s_bytes + pl.part_i_bytes);
+  const bool streaming = use_streaming(B, k, D);
+  int rc = ragraph_normalize_rows_f32(Pq, B, A, Pqn, stream);
+  if (rc == RAGRAPH_OK && !streaming) rc = ragraph_normalize_rows_f32(Q, B, D, Qn, stream);  // (the streaming kernel normalises Q itself)
+  if (rc != RAGRAPH_OK) return rc;
+
+  TopkParams p;
+  memset(&p, 0, sizeof(p));
+  p.Qn = streaming ? Q : Qn;
+  p.Kn = Kn;
+  p.B = B;
+  p.N = N;
+  p.k = k;
+  p.nsplit = pl.nsplit;
+  p.ngroups = (int)cdiv(B, 16);
+  p.qtiles = cdiv(B, 256);
+  p.xcd_map = pl.xcd_map;
+  p.wgs_per_group = pl.wgs_per_group;
+  p.lb_min = pl.lb_min;
+  p.warm_stages = pl.warm_stages;
+  p.depth[0] = pl.depth[0];
+  p.depth[1] = pl.depth[1];
+  p.nstages_total = pl.nstages_total;
+  p.part_s = part_s;
+  p.part_i = part_i;
+  p.Pq = Pqn;
+  p.Pn = Pn;
+  p.A = A;
+  p.w_struct = w_struct;
+  p.w_sem = w_sem;
+  // |s_struct| <= |a||b| (1 + A 2^-23) for rows normalised to within a few ulp of 1: 2^-10 covers it many times over
+  p.mix_slack = nextafterf((float)(fabs((double)w_struct) * (1.0 + 1.0 / 1024)), __builtin_huge_valf());
+  if (streaming) {
+    // the pre-pass gives the k-th best MIXED score of a prefix of the bank: a lower bound of the final k-th best
+    const int64_t prefix = 4096;
+    if (B >= 4 && N >= 16 * prefix && k <= prefix) {
+      TopkParams pp = p;
+      pp.N = prefix;
+      pp.nsplit = (int)cdiv(cdiv(prefix, 16 * (256 / D)), 8);
+      if (pp.nsplit > pl.nsplit) pp.nsplit = pl.nsplit;
+      rc = D == 256 ? launch_smallb<256, false, true>(pp, st) : D == 128 ? launch_smallb<128, false, true>(pp, st)
+                                                                         : launch_smallb<64, false, true>(pp, st);
+      if (rc != RAGRAPH_OK) return rc;
+      rc = launch_merge_sorted<int>(part_s, part_i, pp.nsplit, B, k, (int64_t)k, (int64_t)pp.nsplit * k, 0, out_scores,
+                                    out_idx, st);
+      if (rc != RAGRAPH_OK) return rc;
+      p.thr_init = out_scores;
+    }
+    rc = D == 256 ? launch_smallb<256, false, true>(p, st) : D == 128 ? launch_smallb<128, false, true>(p, st)
+                                                                       : launch_smallb<64, false, true>(p, st);
+    if (rc != RAGRAPH_OK) return rc;
+    return launch_merge_sorted<int>(part_s, part_i, pl.nsplit, B, k, (int64_t)k, (int64_t)pl.nsplit * k, idx_base,
+                                    out_scores, out_idx, st);
+  }
+  const int64_t qtiles = cdiv(B, 256);
+  rc = D == 256 ? launch_topk<256, false, true>(p, qtiles, st) : D == 128 ? launch_topk<128, false, true>(p, qtiles, st)
+                                                                           : launch_topk<64, false, true>(p, qtiles, st);
+  if (rc != RAGRAPH_OK) return rc;
   return launch_select<int>(part_s, part_i, pl.nsplit, B, k, (int64_t)k, (int64_t)pl.nsplit * k, idx_base, out_scores,
                             out_idx, st);
 }

@@ -163,6 +163,43 @@ def topk_cosine(q: torch.Tensor, keys_normalized: torch.Tensor, k: int, idx_base
     return scores, idx
 
 
+def topk_cosine_mix_workspace_bytes(B: int, n_keys: int, D: int, A: int, k: int) -> int:
+    """Workspace of topk_cosine_mix (a host computation: no device needed)."""
+    return int(N.lib().ragraph_topk_cosine_mix_workspace_bytes(B, n_keys, D, A, k))
+
+
+def topk_cosine_mix(q: torch.Tensor, keys_normalized: torch.Tensor, pos_q: torch.Tensor, pos_normalized: torch.Tensor,
+                    w_struct: float, w_sem: float, k: int, idx_base: int = 0):
+    """Top-k of  w_struct * cos(position codes) + w_sem * cos(embeddings)  -- RAGraph_node_fewshot/ragraph_utils/
+    ToyGraphBase.py:47-65.  Returns (scores [B,k] f32, idx [B,k] i64), canonical order: the bits of linear x 2 + axpby +
+    topk_rows on the materialised matrices, which the fused kernels (D in 64 / 128 / 256, k <= 32, w_sem > 0) never write.
+
+    q [B,D] and pos_q [B,A] raw (normalised inside); keys_normalized [N,D] and pos_normalized [N,A] from normalize_rows();
+    1 <= A <= 16, 1 <= k <= min(N, TOPK_ORDERED_MAX).  No synchronisation, no read-back: the call can be captured."""
+    L = _ready()
+    q = _f32c(q, "topk_cosine_mix.q")
+    kn = _f32c(keys_normalized, "topk_cosine_mix.keys")
+    pq = _f32c(pos_q, "topk_cosine_mix.pos_q")
+    pn = _f32c(pos_normalized, "topk_cosine_mix.pos_normalized")
+    if q.dim() != 2 or kn.dim() != 2 or q.shape[1] != kn.shape[1]:
+        raise RagraphNativeError(f"topk_cosine_mix: bad shapes {tuple(q.shape)} x {tuple(kn.shape)}")
+    if pq.dim() != 2 or pn.dim() != 2 or pq.shape[1] != pn.shape[1] or pq.shape[0] != q.shape[0] or pn.shape[0] != kn.shape[0]:
+        raise RagraphNativeError(f"topk_cosine_mix: codes {tuple(pq.shape)} x {tuple(pn.shape)} do not match "
+                                 f"{tuple(q.shape)} x {tuple(kn.shape)}")
+    B, D = q.shape
+    Nk, A = pn.shape
+    scores = torch.empty((B, k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((B, k), dtype=torch.int64, device=q.device)
+    if B == 0:
+        return scores, idx
+    nbytes = L.ragraph_topk_cosine_mix_workspace_bytes(B, Nk, D, A, k)
+    ws = _workspace(nbytes, q.device)
+    N.check(L.ragraph_topk_cosine_mix_f32(q.data_ptr(), B, kn.data_ptr(), Nk, D, pq.data_ptr(), pn.data_ptr(), A,
+                                          float(w_struct), float(w_sem), k, idx_base, scores.data_ptr(), idx.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), _stream()), "topk_cosine_mix")
+    return scores, idx
+
+
 def keys_to_bf16(keys_normalized: torch.Tensor) -> torch.Tensor:
     """bf16 copy of the bank for topk_cosine_filtered, in MFMA fragment order (csrc/filter_common.h): rows zero-padded to
     a multiple of 256 + one row holding the largest rounding error; int16 storage, 2 D bytes per key."""

@@ -62,7 +62,13 @@ class ToyGraphBase:
         self.num_anchors, self.dis_q = 10, 10             # ToyGraphBase.py:27-28
         self._positions = _Bank(self.num_anchors, self.device)   # position-aware codes of the sampled toy graphs (:114,119)
         self._keys_normalized = None  # cache, invalidated by every append
+        self._positions_normalized = None   # the same for the codes (read only when structure_weight != 0)
         self._index = None            # K.KeyIndex of this bank version (packed / bf16 copies made on first use)
+        # RAGraph_node/ragraph_utils/ToyGraphBase.py:28-29.  With structure_weight == 0 retrieval is the semantic top-k and
+        # its scores are NOT scaled by semantic_weight, as in the reference's active code (:66-67); otherwise the score is
+        # structure_weight * cos(position codes) + semantic_weight * cos(embeddings) (RAGraph_node_fewshot/.../ToyGraphBase.py:47-65)
+        self.structure_weight = 0.0
+        self.semantic_weight = 0.999
 
     # ---- bank state (attribute names of the reference) ---------------------------------------------------------
     @property
@@ -90,19 +96,59 @@ class ToyGraphBase:
         if positions is not None:
             assert positions.shape[0] == keys.shape[0]
             self._positions.append(positions)
-        self._keys_normalized = self._index = None
+        self._keys_normalized = self._positions_normalized = self._index = None
 
-    def set_resources(self, keys: Tensor, values: Tensor, labels: Tensor) -> None:
-        """Adopt caller-owned device tensors as the bank without copying (e.g. a 1M-row synthetic bank)."""
-        for b, t in ((self._keys, keys), (self._values, values), (self._labels, labels)):
+    def set_resources(self, keys: Tensor, values: Tensor, labels: Tensor, positions: Tensor | None = None) -> None:
+        """Adopt caller-owned device tensors as the bank without copying (e.g. a 1M-row synthetic bank).  Without
+        `positions` the bank has no position codes (retrieval with structure_weight != 0 then raises)."""
+        stores = [(self._keys, keys), (self._values, values), (self._labels, labels)]
+        if positions is not None:
+            if positions.shape[0] != keys.shape[0]:
+                raise ValueError(f"set_resources: {positions.shape[0]} position rows for {keys.shape[0]} keys")
+            stores.append((self._positions, positions))
+        else:
+            self._positions = _Bank(self._positions.buf.shape[1], self.device)
+        for b, t in stores:
             b.buf, b.n = t.to(self.device, torch.float32).contiguous(), t.shape[0]
-        self._keys_normalized = self._index = None
+        self._keys_normalized = self._positions_normalized = self._index = None
 
     @property
     def keys_normalized(self) -> Tensor:
         if self._keys_normalized is None:
             self._keys_normalized = K.normalize_rows(self.resource_keys)
         return self._keys_normalized
+
+    @property
+    def positions_normalized(self) -> Tensor:
+        """F.normalize(resource_positions), once per bank version (cosine_similarity re-normalises them on every call,
+        RAGraph_node_fewshot/ragraph_utils/ToyGraphBase.py:51-53).  An all-zero code row stays zero."""
+        if self._positions_normalized is None:
+            self._positions_normalized = K.normalize_rows(self.resource_positions)
+        return self._positions_normalized
+
+    def _require_positions(self) -> None:
+        n_pos, n_keys = self._positions.n, self._keys.n
+        if n_pos != n_keys:
+            raise ValueError(f"structure_weight = {self.structure_weight}: the bank holds {n_pos} position rows for {n_keys} "
+                             "keys (resources added without positions, or a v1 bank file); retrieval by position codes "
+                             "needs one per key")
+
+    def search_positions(self, search_adj=None, search_positions: Tensor | None = None, anchors: Tensor | None = None):
+        """The query rows' position codes when retrieval uses them (structure_weight != 0), else None: ready codes, or
+        PositionAwareEncoder.py:6-24 on the query graph (`anchors`: drawn from the host generator when not given, as the
+        reference does -- which a stream capture cannot record).  Raises before any kernel when the bank has no codes."""
+        if self.structure_weight == 0:
+            return None
+        self._require_positions()
+        if search_positions is not None:
+            return search_positions
+        if search_adj is None:
+            raise ValueError("structure_weight != 0: retrieval needs the query graph (search_adj) or its position codes")
+        if anchors is None and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise K.RagraphNativeError("structure-aware retrieval: pass `anchors` to a captured call (drawn on the host "
+                                       "generator otherwise: PositionAwareEncoder.py:11)")
+        from ..RAGraph_fewshot import PositionAwareEncoder
+        return PositionAwareEncoder.encode_position_aware_code(search_adj, self.num_anchors, self.dis_q, anchors)
 
     # ---- build (the step before the hot path; deterministic part) -----------------------------------------------
     def build_toy_graph(self, resource_dataset):
@@ -112,33 +158,47 @@ class ToyGraphBase:
         build_toy_graph(self, resource_dataset)
 
     # ---- retrieve (hot path) -----------------------------------------------------------------------------------
-    def topk(self, search_keys: Tensor, k: int):
-        """(scores [B,k], idx [B,k]) of the fused cosine + top-k kernel; canonical tie order."""
+    def topk(self, search_keys: Tensor, k: int, search_positions: Tensor | None = None):
+        """(scores [B,k], idx [B,k]) of the fused cosine + top-k kernel; canonical tie order.  With structure_weight != 0:
+        of structure_weight * cos(search_positions, resource_positions) + semantic_weight * cos(search_keys, resource_keys)
+        (K.topk_cosine_mix; `search_positions` [B, num_anchors] raw codes of the query rows)."""
         q = search_keys.reshape(1, -1) if search_keys.dim() == 1 else search_keys
+        if self.structure_weight != 0:
+            self._require_positions()
+            if search_positions is None:
+                raise ValueError("structure_weight != 0: topk needs the query rows' position codes (search_positions)")
         if self.resource_keys.shape[0] < k:
             raise RuntimeError(f"selected index k out of range: bank has {self.resource_keys.shape[0]} rows, k={k}")
+        if self.structure_weight != 0:
+            pos = search_positions.reshape(1, -1) if search_positions.dim() == 1 else search_positions
+            return K.topk_cosine_mix(q, self.keys_normalized, pos, self.positions_normalized, self.structure_weight,
+                                     self.semantic_weight, k)
         if self._index is None:
             self._index = K.KeyIndex(self.keys_normalized)
         return self._index.topk(q, k)  # fp32 streaming / tile kernel or, for large batches, the bf16-filtered exact path
 
-    def retrieve_indices(self, search_keys: Tensor, add_noise: bool) -> Tensor:
+    def retrieve_indices(self, search_keys: Tensor, add_noise: bool, search_adj=None,
+                         search_positions: Tensor | None = None, anchors: Tensor | None = None) -> Tensor:
         """The rows retrieve() gathers: the top-k' indices (k' = 2 * retrieve_num with add_noise, :66) and, in the node
         flavour with add_noise, noise_retrieve_num uniformly random rows behind them (:73-79).  The reference draws the
         noise from torch's default CPU generator (no device argument) and only then moves it to the bank's device: drawn
         the same way here, so torch.manual_seed reproduces the reference's rows."""
         retrieve_num = 2 * self.retrieve_num if add_noise else self.retrieve_num
-        _, idx = self.topk(search_keys, retrieve_num)                              # :66-67
+        pos = self.search_positions(search_adj, search_positions, anchors)         # (None unless structure_weight != 0)
+        _, idx = self.topk(search_keys, retrieve_num, pos)                         # :66-67
         if add_noise and self.flavour == "node":
             noise_idx = torch.randint(0, self.resource_values.shape[0], (idx.shape[0], self.noise_retrieve_num))
             idx = torch.cat([idx, noise_idx.to(idx.device)], dim=1)
         return idx
 
-    def retrieve(self, search_keys: Tensor, search_adj, add_noise: bool, idx: Tensor | None = None):
+    def retrieve(self, search_keys: Tensor, search_adj, add_noise: bool, idx: Tensor | None = None,
+                 search_positions: Tensor | None = None, anchors: Tensor | None = None):
         """ToyGraphBase.py:47-81 -> (rag_embeddings [B,k',D], rag_labels [B,k',C]).  A 1-D query (graph flavour,
         RAGraph_graph/ragraph_utils/ToyGraphBase.py:56-87) gives B = 1.  `idx`: the rows, when the caller already
-        holds retrieve_indices(search_keys, add_noise) (one top-k per forward instead of two)."""
+        holds retrieve_indices(search_keys, add_noise) (one top-k per forward instead of two).  `search_adj` (the query
+        graph), or ready `search_positions`, and `anchors` matter only with structure_weight != 0."""
         if idx is None:
-            idx = self.retrieve_indices(search_keys, add_noise)
+            idx = self.retrieve_indices(search_keys, add_noise, search_adj, search_positions, anchors)
         rag_embeddings = K.gather_rows(self.resource_values, idx)                  # :70 (+ :76,78 noise rows)
         rag_labels = K.gather_rows(self.resource_labels, idx)                      # :71 (+ :77,79)
         if add_noise and self.flavour != "node":                                   # graph :84-85,131-134
@@ -146,12 +206,13 @@ class ToyGraphBase:
             rag_embeddings = K.axpby(rag_embeddings, 1.0, noise, 1.0)
         return rag_embeddings, rag_labels
 
-    def retrieve_reduced_noisy(self, search_keys: Tensor, idx: Tensor | None = None, want_labels: bool = True):
+    def retrieve_reduced_noisy(self, search_keys: Tensor, idx: Tensor | None = None, want_labels: bool = True,
+                               search_adj=None, search_positions: Tensor | None = None, anchors: Tensor | None = None):
         """What RAGraph.forward consumes in noisy fine-tuning (RAGraph.py:42-49 with add_noise): (sum_k' V, mean_k' L)
         over the top-2k rows plus the noise -- every reduction on the HIP kernels, ONE top-k per call (`idx`: the rows
         when the caller already holds retrieve_indices(search_keys, True); want_labels=False skips the label means)."""
         if idx is None:
-            idx = self.retrieve_indices(search_keys, True)
+            idx = self.retrieve_indices(search_keys, True, search_adj, search_positions, anchors)
         if self.flavour == "node":   # noise = extra rows: still a gather-reduce over an index matrix
             return K.gather_reduce(self.resource_values, self.resource_labels, idx)
         rag_embeddings, _ = self.retrieve(search_keys, None, True, idx=idx)   # noise is added to the gathered embeddings
@@ -161,27 +222,34 @@ class ToyGraphBase:
         mean_l = K.gather_reduce(self.resource_values, self.resource_labels, idx)[1] if want_labels else None
         return sum_v, mean_l
 
-    def retrieve_reduced(self, search_keys: Tensor, k: int | None = None):
+    def retrieve_reduced(self, search_keys: Tensor, k: int | None = None, search_adj=None,
+                         search_positions: Tensor | None = None, anchors: Tensor | None = None):
         """What RAGraph.forward consumes (RAGraph.py:48-49): (sum_k V[idx] [B,D], mean_k L[idx] [B,C], idx) without
         materialising the [B,k,D] gather."""
-        _, idx = self.topk(search_keys, self.retrieve_num if k is None else k)
+        pos = self.search_positions(search_adj, search_positions, anchors)
+        _, idx = self.topk(search_keys, self.retrieve_num if k is None else k, pos)
         sum_v, mean_l = K.gather_reduce(self.resource_values, self.resource_labels, idx)
         return sum_v, mean_l, idx
 
     # ---- persistence (the reference rebuilds its bank on every run; SURVEY.md section 8f row 1) -------------------
     def save(self, path: str) -> None:
-        """keys | values | labels as one .pt (the normalised-key cache is derived and rebuilt on load)."""
-        torch.save({"format": "ragraph_amd.bank.v1", "keys": self.resource_keys.cpu(), "values": self.resource_values.cpu(),
-                    "labels": self.resource_labels.cpu()}, path)
+        """keys | values | labels | positions as one .pt, format v2 (the normalised caches are derived and rebuilt on
+        load).  `positions` holds as many rows as the bank has codes for: all of them, or none."""
+        torch.save({"format": "ragraph_amd.bank.v2", "keys": self.resource_keys.cpu(), "values": self.resource_values.cpu(),
+                    "labels": self.resource_labels.cpu(), "positions": self.resource_positions.cpu()}, path)
 
     def load(self, path: str, append: bool = False) -> None:
+        """Reads v2 and v1 files (v1 has no position codes: such a bank retrieves with structure_weight == 0 only)."""
         blob = torch.load(path, map_location="cpu")
-        if blob.get("format") != "ragraph_amd.bank.v1":
+        if blob.get("format") not in ("ragraph_amd.bank.v1", "ragraph_amd.bank.v2"):
             raise ValueError(f"{path}: not a ragraph_amd bank file")
         if not append:  # fresh stores: the old ones may be tensors adopted from the caller (set_resources)
-            self._keys, self._values, self._labels = (_Bank(b.buf.shape[1], self.device)
-                                                      for b in (self._keys, self._values, self._labels))
-        self.add_resources(blob["keys"], blob["values"], blob["labels"])
+            self._keys, self._values, self._labels, self._positions = (
+                _Bank(b.buf.shape[1], self.device) for b in (self._keys, self._values, self._labels, self._positions))
+        positions = blob.get("positions")
+        if positions is not None and positions.shape[0] != blob["keys"].shape[0]:
+            positions = None   # a bank saved without codes
+        self.add_resources(blob["keys"], blob["values"], blob["labels"], positions)
 
     def show(self):
         print("resource_keys", self.resource_keys.shape)
