@@ -535,7 +535,7 @@ int ragraph_fuse_decode_f32(const float* query, const float* rag, int64_t n, int
 
 /* a8  torch.softmax(decode_label, dim=1) * (1-lambda) + rag_label * lambda  -- RAGraph_node/RAGraph.py:55-57.
  *     logits [B,C], rag_label [B,C] or NULL (then plain softmax; log_mode=1 gives log_softmax, downprompt.py:54).
- *     C <= 1024. */
+ *     1 <= C <= 1024; the normaliser is summed in blocks of 64 classes (C <= 64: one chain). */
 int ragraph_softmax_mix_f32(const float* logits, const float* rag_label, int64_t B, int C, float lambda, int log_mode,
                             float* out, void* stream);
 
@@ -635,10 +635,13 @@ int ragraph_position_codes_csr_f32(const int64_t* rowptr, const int32_t* col, co
  * few-shot flavour trains its decode layer through the SpMM, RAGraph_node_fewshot/RAGraph.py:69; the edge flavour trains
  * embeddings and gate through three propagation layers, RAGraph_edge/modules/RAGraph.py:280-283,335-355); these are the
  * element-wise derivatives of the fused epilogues.
- *   act_grad:  gz = gy * act'(z) written through the OUTPUT y (sign(y) = sign(z) for ReLU / PReLU / LeakyReLU); for PReLU
+ *   act_grad:  gz = gy * act'(z) written through the OUTPUT y (y > 0 exactly when z > 0 for ReLU, and for PReLU / LeakyReLU
+ *     with alpha > 0; for alpha <= 0 pass z itself).  At zero the derivative is the negative side's, as torch's: PReLU /
+ *     LeakyReLU z > 0 ? 1 : alpha, ReLU 0, ELU alpha.  For PReLU
  *     alpha_terms (optional) receives gy * z on z < 0 (z = y / alpha): its sum is the slope's gradient (layers/gcn.py:9).
  *   sigmoid_gate_grad:  out = x * sigmoid(z) (modules/RAGraph.py:168): gx = g * s, gz = g * x * s * (1 - s).
- *   softmax_grad:  RAGraph_node/RAGraph.py:55-57: out = p * (g - sum_c g_c p_c), g = go * scale (scale = 1 - label_weight).
+ *   softmax_grad:  RAGraph_node/RAGraph.py:55-57: out = p * (g - sum_c g_c p_c), g = go * scale (scale = 1 - label_weight);
+ *     C >= 1.
  *   mul_cols:  out[r,:] = x[r,:] * w  -- downstreamprompt.forward (RAGraph_graph/downprompt.py:164-168); its own backward.
  *   mul_cols_act:  out[r,:] = act(x[r,:] * w), act one of RAGRAPH_ACT_* -- the node flavour's downstreamprompt.forward,
  *     ELU(weight * h) (RAGraph_node/downprompt.py:118-130; alpha = 1); backward = act_grad through the output + mul_cols.

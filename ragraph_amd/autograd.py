@@ -19,21 +19,28 @@ from . import kernels as K
 
 
 class _Linear(torch.autograd.Function):
-    """y = act(x @ W^T + b), act in {none, leaky(alpha)}."""
+    """y = act(x @ W^T + b), act in {none, leaky(alpha)}.  The fused epilogue keeps only y, from which backward reads the
+    pre-activation's sign while the slope is positive (y > 0 exactly when z > 0).  For a leaky-family slope <= 0 the output
+    no longer determines it: the forward then runs unfused and keeps z itself, as _SpmmCsr does (the same bits: act(z * 1))."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, act, alpha):
-        y = K.linear(x, weight, bias, act=act, alpha=alpha)
-        ctx.save_for_backward(x, weight, y)
+        ctx.keeps_z = act in (K.ACT_LEAKY, K.ACT_PRELU) and alpha <= 0.0
+        if ctx.keeps_z:
+            s = K.linear(x, weight, bias)
+            y = K.mul_cols(s, torch.ones(s.shape[-1], device=s.device), act, alpha)     # act(z * 1)
+        else:
+            s = y = K.linear(x, weight, bias, act=act, alpha=alpha)
+        ctx.save_for_backward(x, weight, s)
         ctx.act, ctx.alpha, ctx.has_bias = act, alpha, bias is not None
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        x, w, y = ctx.saved_tensors
+        x, w, s = ctx.saved_tensors       # s: the output y, or z itself when keeps_z (act_grad's sign test is then on z)
         gy = gy.contiguous()
         if ctx.act != K.ACT_NONE:
-            gy = K.act_grad(y, gy, ctx.act, ctx.alpha)  # sign(y) == sign(pre-activation) for alpha > 0
+            gy = K.act_grad(s, gy, ctx.act, ctx.alpha)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = K.linear(gy, w.t().contiguous())                      # gy @ W

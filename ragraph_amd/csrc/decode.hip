@@ -95,7 +95,11 @@ __global__ void __launch_bounds__(256) fuse_decode_kernel(const float* __restric
     float m = x[0];
     for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
     float s = 0.f;
-    for (int c = 0; c < C; ++c) s = __fadd_rn(s, expf(x[c] - m));
+    for (int c0 = 0; c0 < C; c0 += 64) {   // (blocks of 64 classes, as softmax_mix_kernel)
+      float sb = 0.f;
+      for (int c = c0; c < c0 + 64 && c < C; ++c) sb = __fadd_rn(sb, expf(x[c] - m));
+      s = __fadd_rn(s, sb);
+    }
     const float one_m = 1.f - lambda;
     for (int c = 0; c < C; ++c) {
       float p = expf(x[c] - m) / s;

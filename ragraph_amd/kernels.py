@@ -1098,6 +1098,8 @@ def scatter_fill_(scores: torch.Tensor, rowptr: torch.Tensor, col: torch.Tensor,
     rowptr = _idxc(rowptr, "scatter_fill_.rowptr")
     col = _idxc(col, "scatter_fill_.col")
     B, Nn = scores.shape
+    if col.numel() == 0:   # nothing listed (every row empty, or no rows): an empty tensor has no address to pass
+        return scores
     N.check(L.ragraph_scatter_fill_f32(scores.data_ptr(), B, Nn, Nn, rowptr.data_ptr(), col.data_ptr(), float(value),
                                        _stream()), "scatter_fill")
     return scores
