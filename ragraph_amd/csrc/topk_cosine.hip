@@ -87,29 +87,29 @@ __device__ __forceinline__ bool hist_contains(const int64_t* __restrict__ rp, co
   return lo < end && col[lo] == idx;
 }
 
-struct TopkParams {
-  const float* Qn;   // [B,D] normalised queries (big kernel) / RAW queries (small-batch kernel)
-  const float* Kn;   // [N,D] normalised keys
-  const float* Kp;   // [N,D] the same rows packed [even k | odd k] (ragraph_pack_keys_f32) for the LDS-DMA ring, or NULL
-  int64_t B, N;
-  int k;
-  int nsplit;
-  int ngroups;             // small/mid-batch kernel: groups of 16 queries (workgroup b serves group b % ngroups)
-  int64_t qtiles;          // query tiles of 256 (big kernel)
-  int xcd_map;             // 1: XCD-aware block mapping (enough query tiles to give every XCD its own)
-  int wgs_per_group;       // big kernel: persistent workgroups per group (one group per XCD when xcd_map, else one group)
-  int lb_min;              // big kernel: shortest share of the leftover tiles a workgroup takes (stages)
-  int warm_stages;         // big kernel: cost of one list warm-up in stages (planning only)
-  int depth[2];            // big kernel: lockstep steps of the plan for groups with as many tiles as group 0 / one fewer
-  int64_t nstages_total;   // big kernel: stages in one full pass over the bank
-  float* part_s;           // [B][nsplit][k]
-  int* part_i;
-  const float* thr_init;   // small-batch kernel: per-query lower bound of the k-th best score at [q*k + k-1], or NULL
+struct TopkParams {   // every field has an initialiser: a caller sets what its flavour uses, nothing reaches a kernel unset
+  const float* Qn = nullptr;   // [B,D] normalised queries (big kernel) / RAW queries (small-batch kernel)
+  const float* Kn = nullptr;   // [N,D] normalised keys
+  const float* Kp = nullptr;   // [N,D] the same rows packed [even k | odd k] (ragraph_pack_keys_f32) for the LDS-DMA ring, or NULL
+  int64_t B = 0, N = 0;
+  int k = 0;
+  int nsplit = 0;
+  int ngroups = 0;             // small/mid-batch kernel: groups of 16 queries (workgroup b serves group b % ngroups)
+  int64_t qtiles = 0;          // query tiles of 256 (big kernel)
+  int xcd_map = 0;             // 1: XCD-aware block mapping (enough query tiles to give every XCD its own)
+  int wgs_per_group = 0;       // big kernel: persistent workgroups per group (one group per XCD when xcd_map, else one group)
+  int lb_min = 0;              // big kernel: shortest share of the leftover tiles a workgroup takes (stages)
+  int warm_stages = 0;         // big kernel: cost of one list warm-up in stages (planning only)
+  int depth[2] = {0, 0};       // big kernel: lockstep steps of the plan for groups with as many tiles as group 0 / one fewer
+  int64_t nstages_total = 0;   // big kernel: stages in one full pass over the bank
+  float* part_s = nullptr;     // [B][nsplit][k]
+  int* part_i = nullptr;
+  const float* thr_init = nullptr;   // small-batch kernel: per-query lower bound of the k-th best score at [q*k + k-1], or NULL
   // inner-product top-k with per-query exclusion lists (MASKED instantiations only, ragraph_topk_dot_masked_f32):
   // query b's excluded keys are hcol[hrp[b] .. hrp[b+1]), ascending; such a key scores mask_value instead of its product
-  const int64_t* hrp;
-  const int* hcol;
-  float mask_value;
+  const int64_t* hrp = nullptr;
+  const int* hcol = nullptr;
+  float mask_value = 0.f;
   // structure-aware mixed score (MIX instantiations only, ragraph_topk_cosine_mix_f32): score = s_struct * w_struct +
   // s_sem * w_sem with s_struct the fmaf chain over the A columns of the two NORMALISED code rows.  The MFMA stream
   // still produces s_sem alone; a key can only matter when  s_sem * w_sem + mix_slack >= (k-th best score), and only
@@ -119,7 +119,7 @@ struct TopkParams {
   int A = 0;
   float w_struct = 0.f, w_sem = 0.f;
   float mix_slack = 0.f;              // >= |s_struct * w_struct| for every pair of unit-or-zero rows
-  int ablate;              // DIAGNOSTIC ONLY (env RAGRAPH_TOPK_ABLATE, results invalid when non-zero): bit0 skip the
+  int ablate = 0;          // DIAGNOSTIC ONLY (env RAGRAPH_TOPK_ABLATE, results invalid when non-zero): bit0 skip the
                            // top-k epilogue, bit1 skip global loads + LDS writes, bit2 skip the stage barrier (both
                            // 2-slot variant); DMA ring: bit4 skip the DMA, bit5 skip the FULL / FREE counters
 };
@@ -1147,8 +1147,8 @@ static bool use_slab(int64_t B, int64_t N, int D) {
   return B >= 8 && N <= 131072 && B * N <= lim;
 }
 
-static int64_t slab_rows_for(int64_t B, int64_t N) {
-  int64_t rows = ((int64_t)1 << 30) / (4 * N);  // ~1 GiB of scores per slab
+static int64_t slab_rows_for(int64_t B, int64_t n, int64_t bytes) {  // query rows of a slab of ~bytes of scores, n per row
+  int64_t rows = bytes / (4 * n);
   if (rows < 64) rows = 64;
   return rows < B ? rows : B;
 }
@@ -1157,43 +1157,93 @@ static int64_t slab_rows_for(int64_t B, int64_t N) {
 // the dense kernel and the row top-k are written for any D -- the same fmaf chains, hence the same bits as the oracle.
 static bool fused_width(int D) { return D == 64 || D == 128 || D == 256; }
 
+// The one path rule of the three exact entry points (cosine, mixed, masked): materialised slabs or the fused kernels.
+static bool takes_slabs(int64_t B, int64_t N, int D, int k) { return !fused_width(D) || k > 32 || use_slab(B, N, D); }
+
+enum class Flavour { Plain, Mix, Masked };
+
+// ---- the slab workspace: one layout for the size queries and for the calls ------------------------------------------
+// Queries (PLAIN: Qn; MIX: Qn | Pqn; MASKED: none, its gathered rows lie in the MaskedWs prefix in front of this layout) |
+// S slab | T slab (MIX: the structural scores) | the key chunks' candidates (G > 1) | selection workspace (k > 64).
 // The dense kernel takes up to 65535 blocks of 64 columns per launch: longer banks are scored in key chunks whose
 // per-chunk lists are merged in canonical order.
+//   k <= RAGRAPH_TOPK_MAX: lists [G][nb][k] of float scores + int64 bank-relative indices, merged by launch_select
+//   (G * k <= 4096, see slab_merge_check).
+//   64 < k <= RAGRAPH_TOPK_ORDERED_MAX: selected by the ordered large-k kernel (csrc/topk_large.hip); every key chunk's
+//   sorted list is kept as packed candidates [rows][G * k] and merged with the same kernel (G * k exceeds what
+//   launch_select holds), over a selection workspace that serves both the selection and the merge.
+// Key chunks: 2^22 for the lists of PLAIN and MASKED; at most 65535 x 64 columns, the dense kernel's launch limit (2^22
+// itself is 64 columns over it), for MIX and for large k.  MASKED has no large-k selection (the call refuses k > 64): its
+// size query keeps the list layout at every k.
 constexpr int64_t SLAB_KEY_CHUNK = (int64_t)1 << 22;
+constexpr int64_t SLAB_LAUNCH_CHUNK = (int64_t)65535 * 64;
 
-static int64_t slab_chunks(int64_t N) { return cdiv(N, SLAB_KEY_CHUNK); }
+struct SlabLayout {
+  int64_t rows, G, nc;  // queries per slab, key chunks, keys per chunk (balanced chunks: each far longer than k)
+  bool large;           // ordered large-k selection and packed candidates
+  size_t qn, pqn, s, t, cand, part_s, part_i, sel, total;  // byte offsets / the size
+};
 
-static size_t slab_workspace_bytes(int64_t B, int64_t N, int D, int k) {
-  const int64_t rows = slab_rows_for(B, N), G = slab_chunks(N), nc = cdiv(N, G);
-  size_t bytes = align_up((size_t)B * D * sizeof(float), 256) + align_up((size_t)rows * nc * sizeof(float), 256);
-  if (G > 1) bytes += align_up((size_t)G * rows * k * sizeof(float), 256) + align_up((size_t)G * rows * k * sizeof(int64_t), 256);
-  return bytes;
+static SlabLayout slab_layout(int64_t B, int64_t N, int D, int k, Flavour f, int A = 0) {
+  SlabLayout m;
+  m.large = k > RAGRAPH_TOPK_MAX && f != Flavour::Masked;
+  m.G = cdiv(N, m.large || f == Flavour::Mix ? SLAB_LAUNCH_CHUNK : SLAB_KEY_CHUNK);
+  m.nc = cdiv(N, m.G);
+  // one slab of ~1 GiB, counted from the whole bank; MIX: two slabs of ~512 MiB, counted from the chunk
+  m.rows = f == Flavour::Mix ? slab_rows_for(B, m.nc, (int64_t)1 << 29) : slab_rows_for(B, N, (int64_t)1 << 30);
+  const size_t slab = align_up((size_t)m.rows * m.nc * sizeof(float), 256);
+  size_t o = 0;
+  m.qn = o;
+  if (f != Flavour::Masked) o += align_up((size_t)B * D * sizeof(float), 256);
+  m.pqn = o;
+  if (f == Flavour::Mix) o += align_up((size_t)B * A * sizeof(float), 256);
+  m.s = o;
+  o += slab;
+  m.t = o;
+  if (f == Flavour::Mix) o += slab;
+  m.cand = m.part_s = m.part_i = m.sel = o;
+  if (m.large) {
+    size_t sel = large_select_ws_bytes(m.rows, m.nc, k);
+    if (m.G > 1) {
+      o += align_up((size_t)m.rows * m.G * k * sizeof(unsigned long long), 256);
+      const size_t merge = large_select_ws_bytes(m.rows, m.G * k, k);
+      if (merge > sel) sel = merge;
+    }
+    m.sel = o;
+    o += sel;
+  } else if (m.G > 1) {
+    o += align_up((size_t)m.G * m.rows * k * sizeof(float), 256);
+    m.part_i = o;
+    o += align_up((size_t)m.G * m.rows * k * sizeof(int64_t), 256);
+  }
+  m.total = o;
+  return m;
 }
 
-// 64 < k <= RAGRAPH_TOPK_ORDERED_MAX: the same score slabs, selected by the ordered large-k kernel (csrc/topk_large.hip).
-// Banks beyond one dense launch keep every key chunk's sorted list as packed candidates [rows][G * k] and merge them with the
-// same kernel (G * k exceeds what launch_select holds).  Layout: Qn | S slab | candidates (G > 1) | selection workspace.
-// Key chunks of at most 65535 x 64 columns, the dense kernel's launch limit (2^22 itself is 64 columns over it).
-static int64_t slab_large_chunks(int64_t N) { return cdiv(N, (int64_t)65535 * 64); }
+// ---- the fused kernels' workspace: Qn (PLAIN, MIX) | partial scores | partial indices | Pqn (MIX) --------------------
+struct FusedLayout {
+  size_t qn, part_s, part_i, pqn, total;
+};
 
-static size_t slab_large_workspace_bytes(int64_t B, int64_t N, int D, int k) {
-  const int64_t rows = slab_rows_for(B, N), G = slab_large_chunks(N), nc = cdiv(N, G);
-  size_t bytes = align_up((size_t)B * D * sizeof(float), 256) + align_up((size_t)rows * nc * sizeof(float), 256);
-  size_t sel = large_select_ws_bytes(rows, nc, k);
-  if (G > 1) {
-    bytes += align_up((size_t)rows * G * k * sizeof(unsigned long long), 256);
-    const size_t merge = large_select_ws_bytes(rows, G * k, k);
-    if (merge > sel) sel = merge;
-  }
-  return bytes + sel;
+static FusedLayout fused_layout(const TopkPlan& pl, Flavour f, int64_t B = 0, int A = 0) {
+  FusedLayout m;
+  size_t o = 0;
+  m.qn = o;
+  if (f != Flavour::Masked) o += pl.qn_bytes;
+  m.part_s = o;
+  o += pl.part_s_bytes;
+  m.part_i = o;
+  o += pl.part_i_bytes;
+  m.pqn = o;
+  if (f == Flavour::Mix) o += align_up((size_t)B * A * sizeof(float), 256);
+  m.total = o;
+  return m;
 }
 
 extern "C" size_t ragraph_topk_cosine_workspace_bytes(int64_t B, int64_t N, int D, int k) {
-  if (B < 1 || N < 1 || k < 1 || D < 1) return 0;
-  if (k > RAGRAPH_TOPK_MAX) return k <= RAGRAPH_TOPK_ORDERED_MAX ? slab_large_workspace_bytes(B, N, D, k) : 0;
-  if (!fused_width(D) || k > 32 || use_slab(B, N, D)) return slab_workspace_bytes(B, N, D, k);
-  TopkPlan pl = plan_topk(B, N, D, k);
-  return pl.qn_bytes + pl.part_s_bytes + pl.part_i_bytes;
+  if (B < 1 || N < 1 || k < 1 || D < 1 || k > RAGRAPH_TOPK_ORDERED_MAX) return 0;
+  if (takes_slabs(B, N, D, k)) return slab_layout(B, N, D, k, Flavour::Plain).total;
+  return fused_layout(plan_topk(B, N, D, k), Flavour::Plain).total;
 }
 
 extern "C" int ragraph_topk_rows_f32(const float* S, int64_t B, int64_t N, int64_t ld, int k, float* out_scores,
@@ -1241,6 +1291,134 @@ extern "C" int ragraph_pack_keys_f32(const float* Kn, int64_t N, int D, float* K
   return RAGRAPH_OK;
 }
 
+// RG_CHECK_LAUNCH for a launch of a shared driver: the label reads "<entry>(<step>)", as the entry's own launches do
+#define RG_CHECK_STEP(entry_, step_)                                                                          \
+  do {                                                                                                        \
+    hipError_t e__ = hipGetLastError();                                                                       \
+    if (e__ != hipSuccess) {                                                                                  \
+      ::ragraph::set_error("%s(%s): launch failed: %s", (entry_), (step_), hipGetErrorString(e__));           \
+      return RAGRAPH_EDEVICE;                                                                                 \
+    }                                                                                                         \
+  } while (0)
+
+// The list merge of a chunked bank holds G * k <= 4096 candidates per query (launch_select); the ordered merge has no limit.
+static int slab_merge_check(const char* entry, const SlabLayout& m, int k) {
+  RG_REQUIRE(m.large || m.G * k <= 4096, RAGRAPH_EUNSUPPORTED, "%s: %lld key chunks x k=%d exceed the merge", entry,
+             (long long)m.G, k);
+  return RAGRAPH_OK;
+}
+
+// ---- the slab driver ----------------------------------------------------------------------------------------------
+// Query slabs of m.rows rows x key chunks of m.nc keys: the dense kernel writes the slab's scores S [nb, nn] of the query
+// rows Qn against the key rows Kn, `hook(b0, nb, n0, nn, S)` (an int status) makes them the flavour's scores (PLAIN:
+// nothing, MIX: the second product and the mix, MASKED: the fill of the history entries), and the row top-k (k <= 64) or
+// the ordered selection takes the chunk's k best.  One chunk: straight to the output.  Several: to the chunk's candidates
+// (list indices made bank-relative), merged per slab in canonical order.  `w` is the base of the layout m.
+template <typename Hook>
+static int slab_topk(const char* entry, const SlabLayout& m, char* w, const float* Qn, int64_t B, const float* Kn,
+                     int64_t N, int D, int k, int64_t idx_base, float* out_scores, int64_t* out_idx, void* stream,
+                     Hook hook) {
+  hipStream_t st = as_stream(stream);
+  float* S = reinterpret_cast<float*>(w + m.s);
+  unsigned long long* cand = reinterpret_cast<unsigned long long*>(w + m.cand);
+  float* part_s = reinterpret_cast<float*>(w + m.part_s);
+  int64_t* part_i = reinterpret_cast<int64_t*>(w + m.part_i);
+  void* sel_ws = w + m.sel;
+  int rc = RAGRAPH_OK;
+  for (int64_t b0 = 0; rc == RAGRAPH_OK && b0 < B; b0 += m.rows) {
+    const int64_t nb = (B - b0 < m.rows) ? B - b0 : m.rows;
+    float* os = out_scores + b0 * k;
+    int64_t* oi = out_idx + b0 * k;
+    for (int64_t g = 0; rc == RAGRAPH_OK && g < m.G; ++g) {
+      const int64_t n0 = g * m.nc, nn = (N - n0 < m.nc) ? N - n0 : m.nc;
+      rc = ragraph_linear_f32(Qn + b0 * D, nb, D, Kn + n0 * D, nn, nullptr, RAGRAPH_ACT_NONE, 0.f, S, stream);
+      if (rc == RAGRAPH_OK) rc = hook(b0, nb, n0, nn, S);
+      if (rc != RAGRAPH_OK) break;
+      if (m.G == 1) {  // (large k: the scores are read back from the slab, in place)
+        rc = m.large ? large_select(S, nullptr, nb, N, N, k, 0u, S, N, idx_base, nullptr, 0, os, oi, sel_ws, st)
+                     : ragraph_topk_rows_f32(S, nb, N, N, k, os, oi, stream);
+      } else if (m.large) {  // key chunk g -> candidates [nb][g * k, (g + 1) * k)
+        rc = large_select(S, nullptr, nb, nn, nn, k, (unsigned)n0, nullptr, 0, 0, cand + g * k, m.G * k, nullptr, nullptr,
+                          sel_ws, st);
+      } else {  // key chunk g -> lists [g][nb][k]
+        rc = ragraph_topk_rows_f32(S, nb, nn, nn, k, part_s + g * nb * k, part_i + g * nb * k, stream);
+        if (rc == RAGRAPH_OK && n0 != 0) {
+          hipLaunchKernelGGL(add_idx_base_kernel, dim3((unsigned)cdiv(nb * k, 256)), dim3(256), 0, st, part_i + g * nb * k,
+                             nb * k, n0);
+          RG_CHECK_STEP(entry, "chunk base");
+        }
+      }
+    }
+    if (rc == RAGRAPH_OK && m.G > 1) {
+      // (large k: scores decoded from the keys.  A score's fmaf chain starts from +0, so it is never -0; a mixed score of
+      // -0 comes back as +0)
+      rc = m.large ? large_select(nullptr, cand, nb, m.G * k, m.G * k, k, 0u, nullptr, 0, idx_base, nullptr, 0, os, oi, sel_ws, st)
+                   : launch_select<int64_t>(part_s, part_i, (int)m.G, nb, k, nb * k, (int64_t)k, (int64_t)0, os, oi, st);
+    }
+  }
+  if (rc == RAGRAPH_OK && !m.large && idx_base != 0) {  // (the ordered selection has added it)
+    hipLaunchKernelGGL(add_idx_base_kernel, dim3((unsigned)cdiv(B * k, 256)), dim3(256), 0, st, out_idx, B * k, idx_base);
+    RG_CHECK_STEP(entry, "add base");
+  }
+  return rc;
+}
+
+// ---- the fused launcher -------------------------------------------------------------------------------------------
+// The one D dispatch of each kernel family: the streaming kernel (groups of 16 queries) or the tile kernel.
+template <bool MASKED, bool MIX>
+static int launch_fused(const TopkParams& p, int D, bool streaming, hipStream_t st) {
+  if (streaming)
+    return D == 256 ? launch_smallb<256, MASKED, MIX>(p, st) : D == 128 ? launch_smallb<128, MASKED, MIX>(p, st)
+                                                                         : launch_smallb<64, MASKED, MIX>(p, st);
+  return D == 256 ? launch_topk<256, MASKED, MIX>(p, p.qtiles, st) : D == 128 ? launch_topk<128, MASKED, MIX>(p, p.qtiles, st)
+                                                                               : launch_topk<64, MASKED, MIX>(p, p.qtiles, st);
+}
+
+// `p` arrives with the caller's operands (Qn, Kn, Kp, B, N, k, part_s, part_i) and its flavour's fields; the plan, the
+// pre-pass, the kernel and the merge of the partial lists are the same for the three flavours.
+template <bool MASKED, bool MIX>
+static int fused_topk(TopkParams p, const TopkPlan& pl, int D, int64_t idx_base, float* out_scores, int64_t* out_idx,
+                      hipStream_t st) {
+  p.nsplit = pl.nsplit;
+  p.ngroups = (int)cdiv(p.B, 16);
+  p.qtiles = cdiv(p.B, 256);
+  p.xcd_map = pl.xcd_map;
+  p.wgs_per_group = pl.wgs_per_group;
+  p.lb_min = pl.lb_min;
+  p.warm_stages = pl.warm_stages;
+  p.depth[0] = pl.depth[0];
+  p.depth[1] = pl.depth[1];
+  p.nstages_total = pl.nstages_total;
+  p.thr_init = nullptr;
+  const bool streaming = use_streaming(p.B, p.k, D);
+  // >= 4 queries: each of the ~2000 waves sees only N/2000 keys, so its lists would stay in their warm-up for the
+  // whole stream.  A pre-pass over a 4096-key prefix (1/256 of a 1M bank) gives every query the k-th best score of
+  // that prefix -- a valid lower bound of the final k-th best (MASKED: the masked k-th best of the prefix bounds the
+  // final masked one, MIX: the mixed one the final mixed one) -- and the main pass then only ever inserts the
+  // ~k*N/4096 keys per query that beat it.  For 1-3 queries the two extra launches cost more than they save.
+  const int64_t prefix = 4096;
+  if (streaming && p.B >= 4 && p.N >= 16 * prefix && p.k <= prefix) {
+    TopkParams pp = p;
+    pp.N = prefix;
+    pp.nsplit = (int)cdiv(cdiv(prefix, 16 * (256 / D)), 8);  // one tile per wave ...
+    if (pp.nsplit > pl.nsplit) pp.nsplit = pl.nsplit;         // ... within the main pass's partial-list workspace
+    int rc = launch_fused<MASKED, MIX>(pp, D, true, st);
+    if (rc != RAGRAPH_OK) return rc;
+    rc = launch_merge_sorted<int>(p.part_s, p.part_i, pp.nsplit, p.B, p.k, (int64_t)p.k, (int64_t)pp.nsplit * p.k, 0,
+                                  out_scores, out_idx, st);
+    if (rc != RAGRAPH_OK) return rc;
+    p.thr_init = out_scores;  // read by the main pass, overwritten by the final merge after it (stream order)
+  }
+  const int rc = launch_fused<MASKED, MIX>(p, D, streaming, st);
+  if (rc != RAGRAPH_OK) return rc;
+  // partial layout [B][nsplit][k]: list g of query b at b*(nsplit*k) + g*k
+  if (streaming)  // per-workgroup partials of the streaming kernel are sorted
+    return launch_merge_sorted<int>(p.part_s, p.part_i, pl.nsplit, p.B, p.k, (int64_t)p.k, (int64_t)pl.nsplit * p.k, idx_base,
+                                    out_scores, out_idx, st);
+  return launch_select<int>(p.part_s, p.part_i, pl.nsplit, p.B, p.k, (int64_t)p.k, (int64_t)pl.nsplit * p.k, idx_base,
+                            out_scores, out_idx, st);
+}
+
 extern "C" int ragraph_topk_cosine_f32(const float* Q, int64_t B, const float* Kn, int64_t N, int D, int k,
                                        int64_t idx_base, float* out_scores, int64_t* out_idx, void* ws,
                                        size_t ws_bytes, void* stream) {
@@ -1260,103 +1438,32 @@ extern "C" int ragraph_topk_cosine_bank_f32(const float* Q, int64_t B, const flo
              RAGRAPH_TOPK_ORDERED_MAX);
   RG_REQUIRE(N < (int64_t)INT_MAX - 1024, RAGRAPH_EUNSUPPORTED, "topk_cosine: shard rows must fit int32");
   RG_REQUIRE(aligned16(Q) && aligned16(Kn) && aligned16(ws), RAGRAPH_EINVAL, "topk_cosine: Q, Kn, ws must be 16-B aligned");
-  if (k > RAGRAPH_TOPK_MAX) {  // ordered large k over exact fp32 score slabs (see slab_large_workspace_bytes)
-    RG_REQUIRE(ws_bytes >= slab_large_workspace_bytes(B, N, D, k), RAGRAPH_EWORKSPACE, "topk_cosine: workspace too small");
-    hipStream_t st = as_stream(stream);
-    const int64_t rows = slab_rows_for(B, N), G = slab_large_chunks(N), nc = cdiv(N, G);
-    char* w = static_cast<char*>(ws);
-    float* Qn = reinterpret_cast<float*>(w);
-    w += align_up((size_t)B * D * sizeof(float), 256);
-    float* S = reinterpret_cast<float*>(w);
-    w += align_up((size_t)rows * nc * sizeof(float), 256);
-    unsigned long long* cand = reinterpret_cast<unsigned long long*>(w);
-    if (G > 1) w += align_up((size_t)rows * G * k * sizeof(unsigned long long), 256);
-    void* sel_ws = w;
-    int rc = ragraph_normalize_rows_f32(Q, B, D, Qn, stream);
-    for (int64_t b0 = 0; rc == RAGRAPH_OK && b0 < B; b0 += rows) {
-      const int64_t nb = (B - b0 < rows) ? B - b0 : rows;
-      if (G == 1) {
-        rc = ragraph_linear_f32(Qn + b0 * D, nb, D, Kn, N, nullptr, RAGRAPH_ACT_NONE, 0.f, S, stream);
-        if (rc == RAGRAPH_OK)
-          rc = large_select(S, nullptr, nb, N, N, k, 0u, S, N, idx_base, nullptr, 0, out_scores + b0 * k, out_idx + b0 * k,
-                            sel_ws, st);
-        continue;
-      }
-      for (int64_t g = 0; rc == RAGRAPH_OK && g < G; ++g) {  // key chunk g -> candidates [nb][g * k, (g + 1) * k)
-        const int64_t n0 = g * nc, nn = (N - n0 < nc) ? N - n0 : nc;
-        rc = ragraph_linear_f32(Qn + b0 * D, nb, D, Kn + n0 * D, nn, nullptr, RAGRAPH_ACT_NONE, 0.f, S, stream);
-        if (rc == RAGRAPH_OK)
-          rc = large_select(S, nullptr, nb, nn, nn, k, (unsigned)n0, nullptr, 0, 0, cand + g * k, G * k, nullptr, nullptr,
-                            sel_ws, st);
-      }
-      if (rc == RAGRAPH_OK)  // (scores decoded from the keys: a score's fmaf chain starts from +0, so it is never -0)
-        rc = large_select(nullptr, cand, nb, G * k, G * k, k, 0u, nullptr, 0, idx_base, nullptr, 0, out_scores + b0 * k,
-                          out_idx + b0 * k, sel_ws, st);
-    }
-    return rc;
-  }
+  hipStream_t st = as_stream(stream);
+  char* w = static_cast<char*>(ws);
   // A handful of queries against a bank of a few thousand keys (graph classification: 16 graphs x the training set's
   // 1113): every key is still a candidate for every list, and the streaming kernel's cooperative inserts -- one
   // (query, key) at a time -- were 45 us of a 150 us forward.  The slab path (dense kernel + topk_rows) has no lists.
-  // Row widths other than 64 / 128 / 256 always take it (any D >= 1).
-  if (!fused_width(D) || k > 32 || use_slab(B, N, D)) {  // materialised slabs, see slab_rows_for()
-    const size_t qn_bytes = align_up((size_t)B * D * sizeof(float), 256);
-    const int64_t rows = slab_rows_for(B, N), G = slab_chunks(N), nc = cdiv(N, G);
-    const size_t s_bytes = align_up((size_t)rows * nc * sizeof(float), 256);
-    const size_t ps_bytes = G > 1 ? align_up((size_t)G * rows * k * sizeof(float), 256) : 0;
-    RG_REQUIRE(ws_bytes >= slab_workspace_bytes(B, N, D, k), RAGRAPH_EWORKSPACE, "topk_cosine: workspace too small");
-    RG_REQUIRE(G * k <= 4096, RAGRAPH_EUNSUPPORTED, "topk_cosine: %lld key chunks x k=%d exceed the merge", (long long)G, k);
-    hipStream_t st = as_stream(stream);
-    float* Qn = reinterpret_cast<float*>(ws);
-    float* S = reinterpret_cast<float*>(static_cast<char*>(ws) + qn_bytes);
-    float* part_s = reinterpret_cast<float*>(static_cast<char*>(ws) + qn_bytes + s_bytes);
-    int64_t* part_i = reinterpret_cast<int64_t*>(static_cast<char*>(ws) + qn_bytes + s_bytes + ps_bytes);
-    int rc = ragraph_normalize_rows_f32(Q, B, D, Qn, stream);
-    for (int64_t b0 = 0; rc == RAGRAPH_OK && b0 < B; b0 += rows) {
-      const int64_t nb = (B - b0 < rows) ? B - b0 : rows;
-      if (G == 1) {
-        rc = ragraph_linear_f32(Qn + b0 * D, nb, D, Kn, N, nullptr, RAGRAPH_ACT_NONE, 0.f, S, stream);
-        if (rc == RAGRAPH_OK) rc = ragraph_topk_rows_f32(S, nb, N, N, k, out_scores + b0 * k, out_idx + b0 * k, stream);
-        continue;
-      }
-      for (int64_t g = 0; rc == RAGRAPH_OK && g < G; ++g) {  // key chunks: lists [G][nb][k], indices made bank-relative
-        const int64_t n0 = g * nc, nn = (N - n0 < nc) ? N - n0 : nc;  // (balanced chunks: each far longer than k)
-        rc = ragraph_linear_f32(Qn + b0 * D, nb, D, Kn + n0 * D, nn, nullptr, RAGRAPH_ACT_NONE, 0.f, S, stream);
-        if (rc != RAGRAPH_OK) break;
-        rc = ragraph_topk_rows_f32(S, nb, nn, nn, k, part_s + g * nb * k, part_i + g * nb * k, stream);
-        if (rc == RAGRAPH_OK && n0 != 0) {
-          hipLaunchKernelGGL(add_idx_base_kernel, dim3((unsigned)cdiv(nb * k, 256)), dim3(256), 0, st, part_i + g * nb * k,
-                             nb * k, n0);
-          RG_CHECK_LAUNCH("topk_cosine(chunk base)");
-        }
-      }
-      if (rc == RAGRAPH_OK)
-        rc = launch_select<int64_t>(part_s, part_i, (int)G, nb, k, nb * k, (int64_t)k, (int64_t)0, out_scores + b0 * k,
-                                    out_idx + b0 * k, st);
-    }
-    if (rc == RAGRAPH_OK && idx_base != 0) {
-      hipLaunchKernelGGL(add_idx_base_kernel, dim3((unsigned)cdiv(B * k, 256)), dim3(256), 0, as_stream(stream), out_idx,
-                         B * k, idx_base);
-      RG_CHECK_LAUNCH("topk_cosine(add base)");
-    }
-    return rc;
-  }
-  TopkPlan pl = plan_topk(B, N, D, k);
-  RG_REQUIRE(ws_bytes >= pl.qn_bytes + pl.part_s_bytes + pl.part_i_bytes, RAGRAPH_EWORKSPACE,
-             "topk_cosine: workspace %zu < %zu", ws_bytes, pl.qn_bytes + pl.part_s_bytes + pl.part_i_bytes);
-  hipStream_t st = as_stream(stream);
-  char* w = static_cast<char*>(ws);
-  float* Qn = reinterpret_cast<float*>(w);
-  float* part_s = reinterpret_cast<float*>(w + pl.qn_bytes);
-  int* part_i = reinterpret_cast<int*>(w + pl.qn_bytes + pl.part_s_bytes);
-
-  int rc = RAGRAPH_OK;
-  const bool streaming = use_streaming(B, k, D);
-  if (!streaming) {  // the streaming kernel normalises its queries itself
+  // Row widths other than 64 / 128 / 256 always take it (any D >= 1), and so does k > 32 (k > 64: ordered selection).
+  if (takes_slabs(B, N, D, k)) {
+    const SlabLayout m = slab_layout(B, N, D, k, Flavour::Plain);
+    RG_REQUIRE(ws_bytes >= m.total, RAGRAPH_EWORKSPACE, "topk_cosine: workspace too small");
+    int rc = slab_merge_check("topk_cosine", m, k);
+    if (rc != RAGRAPH_OK) return rc;
+    float* Qn = reinterpret_cast<float*>(w + m.qn);
     rc = ragraph_normalize_rows_f32(Q, B, D, Qn, stream);
     if (rc != RAGRAPH_OK) return rc;
+    return slab_topk("topk_cosine", m, w, Qn, B, Kn, N, D, k, idx_base, out_scores, out_idx, stream,
+                     [](int64_t, int64_t, int64_t, int64_t, float*) -> int { return RAGRAPH_OK; });
   }
-
+  const TopkPlan pl = plan_topk(B, N, D, k);
+  const FusedLayout m = fused_layout(pl, Flavour::Plain);
+  RG_REQUIRE(ws_bytes >= m.total, RAGRAPH_EWORKSPACE, "topk_cosine: workspace %zu < %zu", ws_bytes, m.total);
+  float* Qn = reinterpret_cast<float*>(w + m.qn);
+  const bool streaming = use_streaming(B, k, D);
+  if (!streaming) {  // the streaming kernel normalises its queries itself
+    const int rc = ragraph_normalize_rows_f32(Q, B, D, Qn, stream);
+    if (rc != RAGRAPH_OK) return rc;
+  }
   TopkParams p;
   p.Qn = streaming ? Q : Qn;
   p.Kn = Kn;
@@ -1364,62 +1471,14 @@ extern "C" int ragraph_topk_cosine_bank_f32(const float* Q, int64_t B, const flo
   p.B = B;
   p.N = N;
   p.k = k;
-  p.nsplit = pl.nsplit;
-  p.ngroups = (int)cdiv(B, 16);
-  p.qtiles = cdiv(B, 256);
-  p.xcd_map = pl.xcd_map;
-  p.wgs_per_group = pl.wgs_per_group;
-  p.lb_min = pl.lb_min;
-  p.warm_stages = pl.warm_stages;
-  p.depth[0] = pl.depth[0];
-  p.depth[1] = pl.depth[1];
-  p.nstages_total = pl.nstages_total;
-  p.part_s = part_s;
-  p.part_i = part_i;
-  p.hrp = nullptr;
-  p.hcol = nullptr;
-  p.mask_value = 0.f;
+  p.part_s = reinterpret_cast<float*>(w + m.part_s);
+  p.part_i = reinterpret_cast<int*>(w + m.part_i);
   static const int ablate_env = [] {  // timing-only diagnostic switches (read once), see TopkParams::ablate
     const char* e = getenv("RAGRAPH_TOPK_ABLATE");
     return e ? atoi(e) : 0;
   }();
   p.ablate = ablate_env;
-  const int64_t qtiles = cdiv(B, 256);
-  p.thr_init = nullptr;
-  if (streaming) {
-    // >= 4 queries: each of the ~2000 waves sees only N/2000 keys, so its lists would stay in their warm-up for the
-    // whole stream.  A pre-pass over a 4096-key prefix (1/256 of a 1M bank) gives every query the k-th best score of
-    // that prefix -- a valid lower bound of the final k-th best -- and the main pass then only ever inserts the
-    // ~k*N/4096 keys per query that beat it.  For 1-3 queries the two extra launches cost more than they save.
-    const int64_t prefix = 4096;
-    if (B >= 4 && N >= 16 * prefix && k <= prefix) {
-      TopkParams pp = p;
-      pp.N = prefix;
-      pp.nsplit = (int)cdiv(cdiv(prefix, 16 * (256 / D)), 8);  // one tile per wave ...
-      if (pp.nsplit > pl.nsplit) pp.nsplit = pl.nsplit;         // ... within the main pass's partial-list workspace
-      rc = D == 256 ? launch_smallb<256>(pp, st) : D == 128 ? launch_smallb<128>(pp, st) : launch_smallb<64>(pp, st);
-      if (rc != RAGRAPH_OK) return rc;
-      rc = launch_merge_sorted<int>(part_s, part_i, pp.nsplit, B, k, (int64_t)k, (int64_t)pp.nsplit * k, 0, out_scores,
-                                    out_idx, st);
-      if (rc != RAGRAPH_OK) return rc;
-      p.thr_init = out_scores;  // read by the main pass, overwritten by the final merge after it (stream order)
-    }
-    rc = D == 256 ? launch_smallb<256>(p, st) : D == 128 ? launch_smallb<128>(p, st) : launch_smallb<64>(p, st);
-  } else if (D == 256) {
-    rc = launch_topk<256>(p, qtiles, st);
-  } else if (D == 128) {
-    rc = launch_topk<128>(p, qtiles, st);
-  } else {
-    rc = launch_topk<64>(p, qtiles, st);
-  }
-  if (rc != RAGRAPH_OK) return rc;
-
-  // partial layout [B][nsplit][k]: list g of query b at b*(nsplit*k) + g*k
-  if (streaming)  // per-workgroup partials of the streaming kernel are sorted
-    return launch_merge_sorted<int>(part_s, part_i, pl.nsplit, B, k, (int64_t)k, (int64_t)pl.nsplit * k, idx_base,
-                                    out_scores, out_idx, st);
-  return launch_select<int>(part_s, part_i, pl.nsplit, B, k, (int64_t)k, (int64_t)pl.nsplit * k, idx_base, out_scores,
-                            out_idx, st);
+  return fused_topk<false, false>(p, pl, D, idx_base, out_scores, out_idx, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1452,56 +1511,12 @@ __global__ void __launch_bounds__(256) mix_slab_kernel(float* __restrict__ S, co
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
     S[i] = __fadd_rn(__fmul_rn(T[i], wt), __fmul_rn(S[i], ws));
 }
-
-static bool mix_fused(int64_t B, int64_t N, int D, int k) { return fused_width(D) && k <= 32 && !use_slab(B, N, D); }
-
-// materialised path: two score slabs of `rows` queries x one key chunk inside ~1 GiB; key chunks of at most one dense launch
-struct MixSlab {
-  int64_t rows, G, nc;
-  size_t qn, pqn, s, t, cand, part_s, part_i, sel, total;  // byte offsets / sizes
-};
-
-static MixSlab mix_slab_layout(int64_t B, int64_t N, int D, int A, int k) {
-  MixSlab m;
-  m.G = slab_large_chunks(N);
-  m.nc = cdiv(N, m.G);
-  int64_t rows = ((int64_t)1 << 29) / (4 * m.nc);  // two slabs of ~512 MiB
-  if (rows < 64) rows = 64;
-  m.rows = rows < B ? rows : B;
-  size_t o = 0;
-  m.qn = o;
-  o += align_up((size_t)B * D * sizeof(float), 256);
-  m.pqn = o;
-  o += align_up((size_t)B * A * sizeof(float), 256);
-  m.s = o;
-  o += align_up((size_t)m.rows * m.nc * sizeof(float), 256);
-  m.t = o;
-  o += align_up((size_t)m.rows * m.nc * sizeof(float), 256);
-  m.cand = m.part_s = m.part_i = m.sel = o;
-  if (k > RAGRAPH_TOPK_MAX) {
-    size_t sel = large_select_ws_bytes(m.rows, m.nc, k);
-    if (m.G > 1) {
-      o += align_up((size_t)m.rows * m.G * k * sizeof(unsigned long long), 256);
-      const size_t merge = large_select_ws_bytes(m.rows, m.G * k, k);
-      if (merge > sel) sel = merge;
-    }
-    m.sel = o;
-    o += sel;
-  } else if (m.G > 1) {
-    o += align_up((size_t)m.G * m.rows * k * sizeof(float), 256);
-    m.part_i = o;
-    o += align_up((size_t)m.G * m.rows * k * sizeof(int64_t), 256);
-  }
-  m.total = o;
-  return m;
-}
 }  // namespace ragraph
 
 extern "C" size_t ragraph_topk_cosine_mix_workspace_bytes(int64_t B, int64_t N, int D, int A, int k) {
   if (B < 1 || N < 1 || k < 1 || D < 1 || A < 1 || A > 16 || k > RAGRAPH_TOPK_ORDERED_MAX) return 0;
-  if (!mix_fused(B, N, D, k)) return mix_slab_layout(B, N, D, A, k).total;
-  const TopkPlan pl = plan_topk(B, N, D, k);
-  return pl.qn_bytes + pl.part_s_bytes + pl.part_i_bytes + align_up((size_t)B * A * sizeof(float), 256);
+  if (takes_slabs(B, N, D, k)) return slab_layout(B, N, D, k, Flavour::Mix, A).total;
+  return fused_layout(plan_topk(B, N, D, k), Flavour::Mix, B, A).total;
 }
 
 extern "C" int ragraph_topk_cosine_mix_f32(const float* Q, int64_t B, const float* Kn, int64_t N, int D, const float* Pq,
@@ -1519,104 +1534,50 @@ extern "C" int ragraph_topk_cosine_mix_f32(const float* Q, int64_t B, const floa
   hipStream_t st = as_stream(stream);
   char* w = static_cast<char*>(ws);
 
-  if (!mix_fused(B, N, D, k)) {
-    // materialised slabs: dense kernel x 2, mix, ordered selection, canonical merge over key chunks
-    const MixSlab m = mix_slab_layout(B, N, D, A, k);
+  if (takes_slabs(B, N, D, k)) {
+    // materialised slabs: dense kernel x 2, mix, selection, canonical merge over key chunks
+    const SlabLayout m = slab_layout(B, N, D, k, Flavour::Mix, A);
     RG_REQUIRE(ws_bytes >= m.total, RAGRAPH_EINVAL, "topk_cosine_mix: workspace %zu < %zu", ws_bytes, m.total);
-    RG_REQUIRE(k > RAGRAPH_TOPK_MAX || m.G * k <= 4096, RAGRAPH_EUNSUPPORTED,
-               "topk_cosine_mix: %lld key chunks x k=%d exceed the merge", (long long)m.G, k);
+    int rc = slab_merge_check("topk_cosine_mix", m, k);
+    if (rc != RAGRAPH_OK) return rc;
     float* Qn = reinterpret_cast<float*>(w + m.qn);
     float* Pqn = reinterpret_cast<float*>(w + m.pqn);
-    float* S = reinterpret_cast<float*>(w + m.s);
     float* T = reinterpret_cast<float*>(w + m.t);
-    unsigned long long* cand = reinterpret_cast<unsigned long long*>(w + m.cand);
-    float* part_s = reinterpret_cast<float*>(w + m.part_s);
-    int64_t* part_i = reinterpret_cast<int64_t*>(w + m.part_i);
-    void* sel_ws = w + m.sel;
-    const bool large = k > RAGRAPH_TOPK_MAX;
-    int rc = ragraph_normalize_rows_f32(Q, B, D, Qn, stream);
+    rc = ragraph_normalize_rows_f32(Q, B, D, Qn, stream);
     if (rc == RAGRAPH_OK) rc = ragraph_normalize_rows_f32(Pq, B, A, Pqn, stream);
-    for (int64_t b0 = 0; rc == RAGRAPH_OK && b0 < B; b0 += m.rows) {
-      const int64_t nb = (B - b0 < m.rows) ? B - b0 : m.rows;
-      for (int64_t g = 0; rc == RAGRAPH_OK && g < m.G; ++g) {
-        const int64_t n0 = g * m.nc, nn = (N - n0 < m.nc) ? N - n0 : m.nc;
-        rc = ragraph_linear_f32(Qn + b0 * D, nb, D, Kn + n0 * D, nn, nullptr, RAGRAPH_ACT_NONE, 0.f, S, stream);
-        if (rc == RAGRAPH_OK)
-          rc = ragraph_linear_f32(Pqn + b0 * A, nb, A, Pn + n0 * A, nn, nullptr, RAGRAPH_ACT_NONE, 0.f, T, stream);
-        if (rc != RAGRAPH_OK) break;
-        {
-          int64_t blocks = cdiv(nb * nn, 256);
-          if (blocks > 2048) blocks = 2048;
-          hipLaunchKernelGGL(mix_slab_kernel, dim3((unsigned)blocks), dim3(256), 0, st, S, T, w_struct, w_sem, nb * nn);
-          RG_CHECK_LAUNCH("topk_cosine_mix(mix)");
-        }
-        float* os = out_scores + b0 * k;
-        int64_t* oi = out_idx + b0 * k;
-        if (large) {
-          if (m.G == 1)
-            rc = large_select(S, nullptr, nb, N, N, k, 0u, S, N, idx_base, nullptr, 0, os, oi, sel_ws, st);
-          else  // (a merged score is decoded from its key: a mixed score of -0 comes back as +0)
-            rc = large_select(S, nullptr, nb, nn, nn, k, (unsigned)n0, nullptr, 0, 0, cand + g * k, m.G * k, nullptr, nullptr,
-                              sel_ws, st);
-        } else if (m.G == 1) {
-          rc = ragraph_topk_rows_f32(S, nb, N, N, k, os, oi, stream);
-        } else {
-          rc = ragraph_topk_rows_f32(S, nb, nn, nn, k, part_s + g * nb * k, part_i + g * nb * k, stream);
-          if (rc == RAGRAPH_OK && n0 != 0) {
-            hipLaunchKernelGGL(add_idx_base_kernel, dim3((unsigned)cdiv(nb * k, 256)), dim3(256), 0, st, part_i + g * nb * k,
-                               nb * k, n0);
-            RG_CHECK_LAUNCH("topk_cosine_mix(chunk base)");
-          }
-        }
-      }
-      if (rc == RAGRAPH_OK && m.G > 1) {
-        if (large)
-          rc = large_select(nullptr, cand, nb, m.G * k, m.G * k, k, 0u, nullptr, 0, idx_base, nullptr, 0, out_scores + b0 * k,
-                            out_idx + b0 * k, sel_ws, st);
-        else
-          rc = launch_select<int64_t>(part_s, part_i, (int)m.G, nb, k, nb * k, (int64_t)k, (int64_t)0, out_scores + b0 * k,
-                                      out_idx + b0 * k, st);
-      }
-    }
-    if (rc == RAGRAPH_OK && !large && idx_base != 0) {
-      hipLaunchKernelGGL(add_idx_base_kernel, dim3((unsigned)cdiv(B * k, 256)), dim3(256), 0, st, out_idx, B * k, idx_base);
-      RG_CHECK_LAUNCH("topk_cosine_mix(add base)");
-    }
-    return rc;
+    if (rc != RAGRAPH_OK) return rc;
+    return slab_topk("topk_cosine_mix", m, w, Qn, B, Kn, N, D, k, idx_base, out_scores, out_idx, stream,
+                     [=](int64_t b0, int64_t nb, int64_t n0, int64_t nn, float* S) -> int {
+                       const int rc = ragraph_linear_f32(Pqn + b0 * A, nb, A, Pn + n0 * A, nn, nullptr, RAGRAPH_ACT_NONE,
+                                                         0.f, T, stream);
+                       if (rc != RAGRAPH_OK) return rc;
+                       int64_t blocks = cdiv(nb * nn, 256);
+                       if (blocks > 2048) blocks = 2048;
+                       hipLaunchKernelGGL(mix_slab_kernel, dim3((unsigned)blocks), dim3(256), 0, st, S, T, w_struct, w_sem,
+                                          nb * nn);
+                       RG_CHECK_LAUNCH("topk_cosine_mix(mix)");
+                       return RAGRAPH_OK;
+                     });
   }
 
   const TopkPlan pl = plan_topk(B, N, D, k);
-  const size_t pqn_bytes = align_up((size_t)B * A * sizeof(float), 256);
-  RG_REQUIRE(ws_bytes >= pl.qn_bytes + pl.part_s_bytes + pl.part_i_bytes + pqn_bytes, RAGRAPH_EINVAL,
-             "topk_cosine_mix: workspace %zu < %zu", ws_bytes, pl.qn_bytes + pl.part_s_bytes + pl.part_i_bytes + pqn_bytes);
-  float* Qn = reinterpret_cast<float*>(w);
-  float* part_s = reinterpret_cast<float*>(w + pl.qn_bytes);
-  int* part_i = reinterpret_cast<int*>(w + pl.qn_bytes + pl.part_s_bytes);
-  float* Pqn = reinterpret_cast<float*>(w + pl.qn_bytes + pl.part_s_bytes + pl.part_i_bytes);
+  const FusedLayout m = fused_layout(pl, Flavour::Mix, B, A);
+  RG_REQUIRE(ws_bytes >= m.total, RAGRAPH_EINVAL, "topk_cosine_mix: workspace %zu < %zu", ws_bytes, m.total);
+  float* Qn = reinterpret_cast<float*>(w + m.qn);
+  float* Pqn = reinterpret_cast<float*>(w + m.pqn);
   const bool streaming = use_streaming(B, k, D);
   int rc = ragraph_normalize_rows_f32(Pq, B, A, Pqn, stream);
   if (rc == RAGRAPH_OK && !streaming) rc = ragraph_normalize_rows_f32(Q, B, D, Qn, stream);  // (the streaming kernel normalises Q itself)
   if (rc != RAGRAPH_OK) return rc;
 
   TopkParams p;
-  memset(&p, 0, sizeof(p));
   p.Qn = streaming ? Q : Qn;
   p.Kn = Kn;
   p.B = B;
   p.N = N;
   p.k = k;
-  p.nsplit = pl.nsplit;
-  p.ngroups = (int)cdiv(B, 16);
-  p.qtiles = cdiv(B, 256);
-  p.xcd_map = pl.xcd_map;
-  p.wgs_per_group = pl.wgs_per_group;
-  p.lb_min = pl.lb_min;
-  p.warm_stages = pl.warm_stages;
-  p.depth[0] = pl.depth[0];
-  p.depth[1] = pl.depth[1];
-  p.nstages_total = pl.nstages_total;
-  p.part_s = part_s;
-  p.part_i = part_i;
+  p.part_s = reinterpret_cast<float*>(w + m.part_s);
+  p.part_i = reinterpret_cast<int*>(w + m.part_i);
   p.Pq = Pqn;
   p.Pn = Pn;
   p.A = A;
@@ -1624,34 +1585,7 @@ extern "C" int ragraph_topk_cosine_mix_f32(const float* Q, int64_t B, const floa
   p.w_sem = w_sem;
   // |s_struct| <= |a||b| (1 + A 2^-23) for rows normalised to within a few ulp of 1: 2^-10 covers it many times over
   p.mix_slack = nextafterf((float)(fabs((double)w_struct) * (1.0 + 1.0 / 1024)), __builtin_huge_valf());
-  if (streaming) {
-    // the pre-pass gives the k-th best MIXED score of a prefix of the bank: a lower bound of the final k-th best
-    const int64_t prefix = 4096;
-    if (B >= 4 && N >= 16 * prefix && k <= prefix) {
-      TopkParams pp = p;
-      pp.N = prefix;
-      pp.nsplit = (int)cdiv(cdiv(prefix, 16 * (256 / D)), 8);
-      if (pp.nsplit > pl.nsplit) pp.nsplit = pl.nsplit;
-      rc = D == 256 ? launch_smallb<256, false, true>(pp, st) : D == 128 ? launch_smallb<128, false, true>(pp, st)
-                                                                         : launch_smallb<64, false, true>(pp, st);
-      if (rc != RAGRAPH_OK) return rc;
-      rc = launch_merge_sorted<int>(part_s, part_i, pp.nsplit, B, k, (int64_t)k, (int64_t)pp.nsplit * k, 0, out_scores,
-                                    out_idx, st);
-      if (rc != RAGRAPH_OK) return rc;
-      p.thr_init = out_scores;
-    }
-    rc = D == 256 ? launch_smallb<256, false, true>(p, st) : D == 128 ? launch_smallb<128, false, true>(p, st)
-                                                                       : launch_smallb<64, false, true>(p, st);
-    if (rc != RAGRAPH_OK) return rc;
-    return launch_merge_sorted<int>(part_s, part_i, pl.nsplit, B, k, (int64_t)k, (int64_t)pl.nsplit * k, idx_base,
-                                    out_scores, out_idx, st);
-  }
-  const int64_t qtiles = cdiv(B, 256);
-  rc = D == 256 ? launch_topk<256, false, true>(p, qtiles, st) : D == 128 ? launch_topk<128, false, true>(p, qtiles, st)
-                                                                           : launch_topk<64, false, true>(p, qtiles, st);
-  if (rc != RAGRAPH_OK) return rc;
-  return launch_select<int>(part_s, part_i, pl.nsplit, B, k, (int64_t)k, (int64_t)pl.nsplit * k, idx_base, out_scores,
-                            out_idx, st);
+  return fused_topk<false, true>(p, pl, D, idx_base, out_scores, out_idx, st);
 }
 
 extern "C" int ragraph_topk_merge_f32(const float* scores, const int64_t* idx, int G, int64_t B, int k,
@@ -1715,21 +1649,13 @@ static MaskedWs masked_ws_layout(int64_t B, int64_t N, int D, int64_t nnz) {
   w.rest = w.coo + w.coo_bytes;
   return w;
 }
-
-static bool masked_slab(int64_t B, int64_t N, int D, int k) { return !fused_width(D) || k > 32 || use_slab(B, N, D); }
 }  // namespace ragraph
 
 extern "C" size_t ragraph_topk_dot_masked_workspace_bytes(int64_t B, int64_t N, int D, int k, int64_t nnz) {
   if (B < 1 || N < 1 || k < 1 || D < 1 || nnz < 0) return 0;
   const MaskedWs w = masked_ws_layout(B, N, D, nnz);
-  if (masked_slab(B, N, D, k)) {
-    const int64_t rows = slab_rows_for(B, N), G = slab_chunks(N), nc = cdiv(N, G);
-    size_t bytes = align_up((size_t)rows * nc * sizeof(float), 256);
-    if (G > 1) bytes += align_up((size_t)G * rows * k * sizeof(float), 256) + align_up((size_t)G * rows * k * sizeof(int64_t), 256);
-    return w.rest + bytes;
-  }
-  const TopkPlan pl = plan_topk(B, N, D, k);
-  return w.rest + pl.part_s_bytes + pl.part_i_bytes;
+  if (takes_slabs(B, N, D, k)) return w.rest + slab_layout(B, N, D, k, Flavour::Masked).total;
+  return w.rest + fused_layout(plan_topk(B, N, D, k), Flavour::Masked).total;
 }
 
 extern "C" int ragraph_topk_dot_masked_f32(const float* U, int64_t n_rows_U, const int64_t* users, int64_t B,
@@ -1796,93 +1722,33 @@ extern "C" int ragraph_topk_dot_masked_f32(const float* U, int64_t n_rows_U, con
   }
   char* rest = w0 + w.rest;
 
-  if (masked_slab(B, N, D, k)) {
-    const int64_t srows = slab_rows_for(B, N), G = slab_chunks(N), nc = cdiv(N, G);
-    const size_t s_bytes = align_up((size_t)srows * nc * sizeof(float), 256);
-    const size_t ps_bytes = G > 1 ? align_up((size_t)G * srows * k * sizeof(float), 256) : 0;
-    RG_REQUIRE(G * k <= 4096, RAGRAPH_EUNSUPPORTED, "topk_dot_masked: %lld key chunks x k=%d exceed the merge", (long long)G, k);
-    float* S = reinterpret_cast<float*>(rest);
-    float* part_s = reinterpret_cast<float*>(rest + s_bytes);
-    int64_t* part_i = reinterpret_cast<int64_t*>(rest + s_bytes + ps_bytes);
-    for (int64_t b0 = 0; rc == RAGRAPH_OK && b0 < B; b0 += srows) {
-      const int64_t nb = (B - b0 < srows) ? B - b0 : srows;
-      for (int64_t g = 0; rc == RAGRAPH_OK && g < G; ++g) {
-        const int64_t n0 = g * nc, nn = (N - n0 < nc) ? N - n0 : nc;
-        rc = ragraph_linear_f32(Ug + b0 * D, nb, D, I + n0 * D, nn, nullptr, RAGRAPH_ACT_NONE, 0.f, S, stream);
-        if (rc != RAGRAPH_OK) break;
-        if (nnz > 0) {
-          hipLaunchKernelGGL(masked_fill_slab_kernel, dim3((unsigned)cdiv(nnz, 256)), dim3(256), 0, st, S, nn, rows,
-                             hist_items, nnz, b0, nb, n0, nn, mask_value);
-          RG_CHECK_LAUNCH("topk_dot_masked(fill)");
-        }
-        if (G == 1) {
-          rc = ragraph_topk_rows_f32(S, nb, nn, nn, k, out_scores + b0 * k, out_idx + b0 * k, stream);
-          break;
-        }
-        rc = ragraph_topk_rows_f32(S, nb, nn, nn, k, part_s + g * nb * k, part_i + g * nb * k, stream);
-        if (rc == RAGRAPH_OK && n0 != 0) {
-          hipLaunchKernelGGL(add_idx_base_kernel, dim3((unsigned)cdiv(nb * k, 256)), dim3(256), 0, st, part_i + g * nb * k,
-                             nb * k, n0);
-          RG_CHECK_LAUNCH("topk_dot_masked(chunk base)");
-        }
-      }
-      if (rc == RAGRAPH_OK && G > 1)
-        rc = launch_select<int64_t>(part_s, part_i, (int)G, nb, k, nb * k, (int64_t)k, (int64_t)0, out_scores + b0 * k,
-                                    out_idx + b0 * k, st);
-    }
-    return rc;
+  if (takes_slabs(B, N, D, k)) {
+    const SlabLayout m = slab_layout(B, N, D, k, Flavour::Masked);
+    rc = slab_merge_check("topk_dot_masked", m, k);
+    if (rc != RAGRAPH_OK) return rc;
+    return slab_topk("topk_dot_masked", m, rest, Ug, B, I, N, D, k, 0, out_scores, out_idx, stream,
+                     [=](int64_t b0, int64_t nb, int64_t n0, int64_t nn, float* S) -> int {
+                       if (nnz > 0) {
+                         hipLaunchKernelGGL(masked_fill_slab_kernel, dim3((unsigned)cdiv(nnz, 256)), dim3(256), 0, st, S, nn,
+                                            rows, hist_items, nnz, b0, nb, n0, nn, mask_value);
+                         RG_CHECK_LAUNCH("topk_dot_masked(fill)");
+                       }
+                       return RAGRAPH_OK;
+                     });
   }
 
   const TopkPlan pl = plan_topk(B, N, D, k);
-  float* part_s = reinterpret_cast<float*>(rest);
-  int* part_i = reinterpret_cast<int*>(rest + pl.part_s_bytes);
+  const FusedLayout m = fused_layout(pl, Flavour::Masked);
   TopkParams p;
-  memset(&p, 0, sizeof(p));
-  p.Qn = Ug;
+  p.Qn = Ug;  // raw rows: an inner product, nothing is normalised
   p.Kn = I;
-  p.Kp = nullptr;
   p.B = B;
   p.N = N;
   p.k = k;
-  p.nsplit = pl.nsplit;
-  p.ngroups = (int)cdiv(B, 16);
-  p.qtiles = cdiv(B, 256);
-  p.xcd_map = pl.xcd_map;
-  p.wgs_per_group = pl.wgs_per_group;
-  p.lb_min = pl.lb_min;
-  p.warm_stages = pl.warm_stages;
-  p.depth[0] = pl.depth[0];
-  p.depth[1] = pl.depth[1];
-  p.nstages_total = pl.nstages_total;
-  p.part_s = part_s;
-  p.part_i = part_i;
-  p.thr_init = nullptr;
+  p.part_s = reinterpret_cast<float*>(rest + m.part_s);
+  p.part_i = reinterpret_cast<int*>(rest + m.part_i);
   p.hrp = hist_rowptr;  // the sorted lists keep the caller's row pointer
   p.hcol = hcol;
   p.mask_value = mask_value;
-  p.ablate = 0;
-  if (use_streaming(B, k, D)) {
-    const int64_t prefix = 4096;  // the masked k-th best of a prefix bounds the final masked k-th best from below
-    if (B >= 4 && N >= 16 * prefix && k <= prefix) {
-      TopkParams pp = p;
-      pp.N = prefix;
-      pp.nsplit = (int)cdiv(cdiv(prefix, 16 * (256 / D)), 8);
-      if (pp.nsplit > pl.nsplit) pp.nsplit = pl.nsplit;
-      rc = D == 256 ? launch_smallb<256, true>(pp, st) : D == 128 ? launch_smallb<128, true>(pp, st) : launch_smallb<64, true>(pp, st);
-      if (rc != RAGRAPH_OK) return rc;
-      rc = launch_merge_sorted<int>(part_s, part_i, pp.nsplit, B, k, (int64_t)k, (int64_t)pp.nsplit * k, 0, out_scores,
-                                    out_idx, st);
-      if (rc != RAGRAPH_OK) return rc;
-      p.thr_init = out_scores;
-    }
-    rc = D == 256 ? launch_smallb<256, true>(p, st) : D == 128 ? launch_smallb<128, true>(p, st) : launch_smallb<64, true>(p, st);
-    if (rc != RAGRAPH_OK) return rc;
-    return launch_merge_sorted<int>(part_s, part_i, pl.nsplit, B, k, (int64_t)k, (int64_t)pl.nsplit * k, 0, out_scores,
-                                    out_idx, st);
-  }
-  const int64_t qtiles = cdiv(B, 256);
-  rc = D == 256 ? launch_topk<256, true>(p, qtiles, st) : D == 128 ? launch_topk<128, true>(p, qtiles, st)
-                                                                   : launch_topk<64, true>(p, qtiles, st);
-  if (rc != RAGRAPH_OK) return rc;
-  return launch_select<int>(part_s, part_i, pl.nsplit, B, k, (int64_t)k, (int64_t)pl.nsplit * k, 0, out_scores, out_idx, st);
+  return fused_topk<true, false>(p, pl, D, 0, out_scores, out_idx, st);
 }
