@@ -33,7 +33,7 @@ constexpr int FILTER_FIX_SLICES = 16;   // at most (16 x 32 partial winners: eig
 
 // R rows per wave: one wave per query row is 100 000 waves of a microsecond of work at c2 -- the launch is bound by how fast waves
 // start, not by its 200 MB; with R = 4 a wave has its four row loads in flight at once and a quarter of the waves exist
-// (calls of FILTER_PREP_WIDE_B queries and more; small calls keep one row per wave: they want every CU at once).
+// (calls of 8192 queries and more: run_filtered; small calls keep one row per wave: they want every CU at once).
 template <int D, int R = 1>
 __global__ void __launch_bounds__(256) filter_prep_kernel(const float* __restrict__ Q, int64_t B, float* __restrict__ Qn,
                                                           float* __restrict__ eq, int* __restrict__ count,

@@ -16,58 +16,10 @@ __device__ __forceinline__ bool zero_query_level(unsigned char fl, int final_lev
   return true;
 }
 
-// One wave per query.  prev_* (the previous level's exact top-k, local indices) may alias out_*.  A query whose list
-// overflowed (now or at an earlier level: flag) is appended to overflow_idx by the final level.  Most queries hold far
-// fewer candidates than the capacity: the slot count is a wave-uniform choice among 1, 2, 4, 8 and CPL.
-template <int D, int CPL>
-__global__ void __launch_bounds__(256) topk_rescore_kernel(const float* __restrict__ Qn, const float* __restrict__ Kn,
-                                                           int* __restrict__ count, const int* __restrict__ cand,
-                                                           int64_t B, int cap, int cs, int k, int64_t idx_base,
-                                                           const float* prev_s, const int64_t* prev_i, int final_level,
-                                                           float* out_s, int64_t* out_i, int* __restrict__ overflow,
-                                                           int* __restrict__ overflow_list,
-                                                           unsigned char* __restrict__ flag, int* __restrict__ cstat) {
-  __shared__ float4 qs[4][D / 4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t b = (int64_t)blockIdx.x * 4 + w;
-  if (b >= B) return;  // whole wave
-  if (lane < D / 4) qs[w][lane] = reinterpret_cast<const float4*>(Qn + b * D)[lane];  // the query row
-  __builtin_amdgcn_wave_barrier();
-  int n = count[b * cs];
-  const unsigned char fl = flag[b];
-  bool over = fl != 0;
-  if (lane == 0 && n >= 0) count[b * cs] = 0;  // the next level starts from an empty list (ordered behind the read through n)
-  if (lane == 0) note_candidates(cstat, b, n);
-  if (zero_query_level(fl, final_level, k, idx_base, lane, out_s + b * k, out_i + b * k)) return;
-  if (n > cap) {  // slots reserved beyond the capacity: candidates were dropped
-    over = true;
-    n = cap;
-  }
-  if (lane == 0) {
-    if (final_level) {
-      if (over) {
-        const int pos = atomicAdd(overflow, 1);
-        overflow_list[pos] = (int)b;
-        flag[b] = 1;   // (listed: a speculative call's verify launch must not list it again)
-      }
-    } else if (over) {
-      flag[b] = 1;
-    }
-  }
-  const int64_t base = final_level ? idx_base : 0;
-  const float* ps = prev_s ? prev_s + b * k : nullptr;
-  const int64_t* pi = prev_i ? prev_i + b * k : nullptr;
-  const int* cb = cand + b * cap;
-#define RG_RESCORE(NS_) rescore_query<D, NS_>(qs[w], Kn, cb, n, lane, k, base, ps, pi, out_s + b * k, out_i + b * k)
-  if (n <= 64) RG_RESCORE(1);
-  else if (n <= 128) RG_RESCORE(2);
-  else if (n <= 256) RG_RESCORE(4);
-  else if (n <= 512) RG_RESCORE(8);
-  else RG_RESCORE(CPL);
-#undef RG_RESCORE
-}
-
-// Large batches: as topk_rescore_kernel, rows staged through LDS (coop_scores); two waves per workgroup.
+// Large batches: one wave per query, rows staged through LDS (coop_scores); two waves per workgroup.  prev_* (the previous
+// level's exact top-k, local indices) may alias out_*.  A query whose list overflowed (now or at an earlier level: flag) is
+// appended to overflow_idx by the final level.  Most queries hold far fewer candidates than the capacity: the slot count is
+// a wave-uniform choice among 1, 2, 4, 8 and CPL.
 // FEWTILE: the variant for levels that leave a query a handful of candidates (the later levels over a sharded bank,
 // whose bounds were sharpened across the shards): a 16-row tile instead of 64, so that four times as many waves fit a
 // CU -- such a level is a chain of memory latencies per query, and occupancy is what hides them; the rare longer list
@@ -462,8 +414,18 @@ __device__ __forceinline__ void exact_scan_query(const float4* qs /* LDS: the qu
 #ifdef RG_WIDE_TIMING
 __device__ unsigned long long g_wide_t[16];
 #define RG_WSTAMP(i_) if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) g_wide_t[i_] = wall_clock64()
+// host, behind the sliced launch: synchronises and prints block 0's stamps
+static void wide_timing_report() {
+  (void)hipDeviceSynchronize();
+  unsigned long long t[16];
+  (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_wide_t), sizeof(t));
+  fprintf(stderr, "[wide timing, block 0, 10 ns ticks]");
+  for (int i = 1; i < 10; ++i) fprintf(stderr, " %d:%lld", i, (long long)(t[i] - t[0]));
+  fprintf(stderr, "\n");
+}
 #else
 #define RG_WSTAMP(i_)
+static void wide_timing_report() {}
 #endif
 template <int D, bool SLICED, bool COOP>
 __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __restrict__ Qn, const float* __restrict__ Kn,

@@ -16,14 +16,51 @@ __device__ unsigned long long g_ring_max[2][8];    // [BOUND][phase]: the longes
     else atomicMax(&g_ring_max[BOUND][i_], now_ - rs_prev);                                               \
     rs_prev = now_;                                                                                       \
   }
+// host, behind a launch: synchronises, prints the stamps and clears them
+static void ring_stamps_report(bool BOUND, bool I8) {
+  (void)hipDeviceSynchronize();
+  unsigned long long t[2][2][8];
+  (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_ring_t), sizeof(t));
+  for (int b = 0; b < 2; ++b)
+    fprintf(stderr, "[ring stamps, %s%s launch, %s workgroup, 10 ns ticks] operands %lld thresholds %lld ring primed %lld stages %lld "
+            "flush %lld (entered %lld after workgroup 0)\n", BOUND ? "bound" : "filter", I8 ? " int8" : "", b ? "last" : "first",
+            (long long)(t[BOUND][b][1] - t[BOUND][b][0]), (long long)(t[BOUND][b][2] - t[BOUND][b][1]),
+            (long long)(t[BOUND][b][3] - t[BOUND][b][2]), (long long)(t[BOUND][b][4] - t[BOUND][b][3]),
+            (long long)(t[BOUND][b][5] - t[BOUND][b][4]), (long long)(t[BOUND][b][0] - t[BOUND][0][0]));
+  unsigned long long span[2][2], mx[2][8];
+  (void)hipMemcpyFromSymbol(span, HIP_SYMBOL(g_ring_span), sizeof(span));
+  (void)hipMemcpyFromSymbol(mx, HIP_SYMBOL(g_ring_max), sizeof(mx));
+  fprintf(stderr, "[ring stamps, all workgroups] first entry to last exit %lld; longest first-segment phases: operands %lld thresholds %lld "
+          "ring primed %lld stages %lld flush %lld\n", (long long)(span[BOUND][1] - span[BOUND][0]), (long long)mx[BOUND][1],
+          (long long)mx[BOUND][2], (long long)mx[BOUND][3], (long long)mx[BOUND][4], (long long)mx[BOUND][5]);
+  unsigned long long init_span[2][2] = {{~0ull, 0ull}, {~0ull, 0ull}}, zero[2][8] = {};
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ring_span), init_span, sizeof(init_span));
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ring_max), zero, sizeof(zero));
+}
 #else
 #define RG_RSTAMP(i_)
+static void ring_stamps_report(bool, bool) {}
 #endif
 #ifdef RG_TOPK_TIMING  // diagnostic build only: per-wave cycle totals of the ring's phases
 __device__ unsigned long long g_filter_timing[8];
 #define RG_FT(var_) const unsigned long long var_ = __builtin_amdgcn_s_memtime()
+// host, behind a launch: synchronises, prints the totals and clears them
+static void ring_timing_report(int prof_slot, int D) {
+  (void)hipDeviceSynchronize();
+  unsigned long long t[8];
+  (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_filter_timing), sizeof(t));
+  const double n = (double)t[5];
+  if (n > 0)
+    fprintf(stderr, "[filter timing] slot %d D=%d wave-stages=%.0f ticks/stage: wait_full %.1f compute %.1f signal+vmcnt "
+            "%.1f wait_free %.1f dma_issue %.1f total %.1f; flushes in the loop: %.0f, %.1f ticks each = %.1f per stage\n",
+            prof_slot, D, n, t[0] / n, t[1] / n, t[2] / n, t[3] / n, t[4] / n, (t[0] + t[1] + t[2] + t[3] + t[4]) / n, (double)t[7],
+            t[7] ? (double)t[6] / (double)t[7] : 0.0, t[6] / n);
+  unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_filter_timing), zero, sizeof(zero));
+}
 #else
 #define RG_FT(var_)
+static void ring_timing_report(int, int) {}
 #endif
 
 // QW = queries per wave: 64 (four groups of 16 sharing every A fragment; query tile = 512), 32 (tile = 256) or 128

@@ -1,4 +1,8 @@
-// Host side: the level schedule of a filtered call (filter_schedule; exported as ragraph_topk_cosine_filtered_plan).
+// Host side: what a filtered call decides before it launches anything -- the level schedule (filter_schedule; exported as
+// ragraph_topk_cosine_filtered_plan) and the call plan made from it (filter_call_plan).  Host functions without device
+// pointers or launches.  filter_call_plan is a pure function of its FilterShape; filter_schedule also reads seven schedule-
+// experiment switches, once per process as before (RAGRAPH_FILTER_I8_DIRECT, _I8_DIRECT_D64, _N0DIV, _FORCE_N0, _FORCE_L,
+// _I8_CANDF) or per call (_FRACS).
 // Part of csrc/topk_filter.hip (textually included there, inside its namespace / after its helpers): split out in round 6 so
 // that the ring, the candidate path and the launch plumbing can be read -- and changed -- apart.  No include guard on purpose:
 // these are not stand-alone headers.
@@ -35,20 +39,68 @@ constexpr int64_t FILTER_SLAB_MAX_B = 16384;
 constexpr int64_t FILTER_QB_MAX_B = 262144;
 constexpr int64_t FILTER_SLAB_MAX_SCORES = (int64_t)1 << 26;  // 256 MiB of scores
 
+// The switches a call's decisions read.  The first five are flipped BETWEEN calls by tests and A/B runs: read once per call,
+// at the entry, and handed down.  The last two are read once per process.
+struct FilterEnv {
+  int i8;            // RAGRAPH_FILTER_I8 = n: the last n levels run on the int8 copy (0: none); -1: the rule
+  int scored;        // RAGRAPH_FILTER_SCORED = 0 / 1: scored candidate lists off / on; -1: the rule
+  int pipe;          // RAGRAPH_FILTER_PIPE (filter_pass_variant; default 1)
+  int partner_lead;  // RAGRAPH_FILTER_PARTNER_LEAD (0 = equal priorities, the hardware's age order; default 1)
+  int i8_qw;         // RAGRAPH_FILTER_I8_QW: queries per wave of the int8 levels (0: the rule)
+  int scored_shards;    // RAGRAPH_FILTER_SCORED_SHARDS: sharded banks of up to this many shards keep scored lists (default 2)
+  int spec_two_shards;  // RAGRAPH_FILTER_SPEC_SHARDS_TWO_LEVELS: from this many shards a three-level plan runs two levels
+                        // under a prior (default 2: every sharded bank; 0 = never)
+};
+static int filter_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+static FilterEnv filter_env() {
+  static const int scored_shards = filter_env_int("RAGRAPH_FILTER_SCORED_SHARDS", 2);
+  static const int spec_two_shards = filter_env_int("RAGRAPH_FILTER_SPEC_SHARDS_TWO_LEVELS", 2);
+  return {filter_env_int("RAGRAPH_FILTER_I8", -1), filter_env_int("RAGRAPH_FILTER_SCORED", -1), filter_env_int("RAGRAPH_FILTER_PIPE", 1),
+          filter_env_int("RAGRAPH_FILTER_PARTNER_LEAD", 1), filter_env_int("RAGRAPH_FILTER_I8_QW", 0), scored_shards, spec_two_shards};
+}
+
+// Scored candidate lists for the int8 levels (topk_rescore_scored_kernel): calls whose rescoring is bound by the row
+// gathers, i.e. the ones that take the one-wave-per-query kernels.
+// D = 256 only: measured with / without (ms per call, profiles/r3_scored_ab.txt) 2048 x 1M x 256: 0.874 / 0.836, 16384:
+// 4.50 / 4.21, 100 000: 24.4 / 22.8; but 50 000 x 2M x 128: 12.71 / 12.63 and 65 536 x 4M x 64: 15.73 / 15.93 -- shorter rows
+// are cheaper to fetch and their scores spread wider against the same eps (fewer extra candidates to prune), so the
+// second round only adds latency.
+// k <= 16: round 1 is 16 rows and lists beyond 256 entries take the plain path -- 50 000 x 1M x 256 at k = 16: 14.5 / 13.7 ms,
+// k = 20: 15.6 / 15.8, k = 32: 18.7 / 20.3.
+static bool filter_scored_lists(int64_t B, int D, int k, const FilterEnv& env) {
+  // every call of the ring kernel (> 256 queries) ...: a scored list needs so few rows that ONE wave per query beats the
+  // four-wave workgroups of the wide kernels even at a few hundred queries, whose single level admits ~380 candidates per
+  // query and prunes 90 % of them (257 x 1M x 256: 0.214 -> 0.189 ms, 512: 0.267 -> 0.228, 1024: 0.436 -> 0.377, 1536: 0.580 ->
+  // 0.490)
+  // ... and the direct kernel's calls of 65 - 256 queries (entries carry ceil(I / 256)): 128 x 1M: 0.111 -> 0.106 ms, 256:
+  // 0.148 -> 0.136.  Up to 64 queries the direct kernel keeps several sub-lists per query and several workgroups rescore
+  // each: one wave per query measured slower there (one query 0.075 -> 0.080 ms).
+  if (B < 65) return false;
+  if (env.scored >= 0) return env.scored != 0;
+  return D == 256 && k <= 16;
+}
+
+// A handful of queries: S workgroups rescore a query (S k <= 256 partial winners for the merge launch), and the direct
+// kernel keeps S sub-lists per query, one per rescoring workgroup (filter_common.h: FILTER_COUNT_STRIDE).
+static int rescore_slices(int64_t B, int k) {
+  int S = B <= 16 ? 8 : (B <= 32 ? 4 : (B <= 64 ? 2 : 1));  // (part_s / part_i exist up to 64 queries)
+  while (S > 1 && S * k > 256) S >>= 1;
+  return S;
+}
+constexpr int FILTER_LIST_CAP = 2048;  // (ragraph_topk_cosine_filtered_cap)
+// slots of a query's candidate region: one list, or (<= 64 queries) one full-size list per rescoring slice
+static int filter_cap(int64_t B, int k) { return FILTER_LIST_CAP * (B <= 64 ? rescore_slices(B, k) : 1); }
+
 // Banks of >= 8192 keys (KeyIndex sends >= 16384) take their first bound from the BOUND pass instead of an
 // exact level 0: the filter kernel itself runs over the first bound_keys keys and records, per query, the best approximate
 // score of each of k consecutive parts; the smallest of the k maxima, minus eps, bounds the final k-th best from below
 // (filter_prepare_kernel).  As a bound it is worth the exact k-th best of ~bound_keys / (ln k + 1) keys, and it costs a
 // bf16 pass with no lists, no inserts and no fp32 matrix work: 0.7 ms instead of the tile kernel's 3.2 ms for the
-// bench's 100 k queries, 40 us instead of the slab's 110 us for 256.  RAGRAPH_FILTER_EXACT_LEVEL0=1 keeps the exact
-// level 0 (A/B).
-static bool filter_bound_pass_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("RAGRAPH_FILTER_EXACT_LEVEL0");
-    return !(e && atoi(e) != 0);
-  }();
-  return on;
-}
+// bench's 100 k queries, 40 us instead of the slab's 110 us for 256.
+constexpr int64_t FILTER_BOUND_MIN_KEYS = 8192;
 
 // Parts of the bound pass's prefix: 4 k (at most 128), as many as the prefix has stages (a part is at least one ring stage;
 // sub-tiles of the direct kernel are finer), never fewer than k.
@@ -81,39 +133,49 @@ static void filter_align_ends(FilterSchedule& sc, int D) {
   if (sc.bound_keys > sc.ends[0]) sc.bound_keys = sc.ends[0] / FILTER_PAD_KEYS * FILTER_PAD_KEYS;
 }
 
-// n_shards > 1 (row-sharded bank, N = the largest shard): the shards pool their first samples through the exchange, so
-// the sample is planned for the WHOLE bank and every shard scans its share of the prefix.
-static int rescore_slices(int64_t B, int k);
+// Everything the decisions of one call depend on.  The entry reads the calling thread's prior and int8 cap and the
+// per-call switches ONCE into this; the host queries fill it with what they are asked about.
+struct FilterShape {
+  int64_t B, N, plan_N;  // N = this shard's rows, plan_N = the largest shard's (one bank: N, up to 1024 rows of slack)
+  int D, k, n_shards;
+  bool exchange;         // a sharded call: the phases' bounds travel through the caller's exchange
+  float prior;           // the thread's speculative first bound (NaN: none)
+  int i8_cap;            // the thread's cap on int8 levels (-1: the rule)
+  bool exact_level0;     // size queries: the plan if the bound pass gives way to an exact level 0 (see filter_call_plan)
+  FilterEnv env;
+  int cus;               // filter_device_cus()
+};
+
 // Sharded banks of up to this many shards keep the SCORED lists on their int8 levels (and the schedule that goes with them):
 // a shard's own round-1 bound comes from 1 / G of the keys while the level's threshold was pooled over all shards' earlier
 // levels -- at G = 2 the shard's bound is still the sharper one (half of the bank against a quarter), from G = 4 it is not and
-// the second round only adds latency (profiles/r3_emul.txt).  RAGRAPH_FILTER_SCORED_SHARDS: A/B.
-static int filter_scored_shards() {
-  static const int v = [] { const char* e = getenv("RAGRAPH_FILTER_SCORED_SHARDS"); return e ? atoi(e) : 2; }();
-  return v;
-}
-static FilterSchedule filter_schedule(int64_t B, int64_t N, int D, int k, int n_shards = 1) {
+// the second round only adds latency (profiles/r3_emul.txt).  RAGRAPH_FILTER_SCORED_SHARDS (FilterEnv::scored_shards): A/B.
+// n_shards > 1 (row-sharded bank, N = the largest shard): the shards pool their first samples through the exchange, so
+// the sample is planned for the WHOLE bank and every shard scans its share of the prefix.  (The schedule of in.plan_N keys: in.N plays no part.)
+static FilterSchedule filter_schedule(const FilterShape& in) {
+  const int64_t B = in.B, N = in.plan_N;
+  const int D = in.D, k = in.k, n_shards = in.exchange ? in.n_shards : 1, cus = in.cus;
+  const FilterEnv& env = in.env;
   FilterSchedule sc{};
   const int cap = 2048;
   // scored lists (one bank, >= 2048 queries): an int8 level's rescoring fetches about a third of its candidates' rows, which
   // makes int8 pay on EVERY level (the bench step, 2 / 3 int8 levels: 24.3 / 23.85 ms; without the scores 26.9 / 27.7)
-  const bool scored = (n_shards == 1 || n_shards <= filter_scored_shards()) && B >= 2048 && filter_scored_lists(B, D, k);  // (below 2048 queries the plain lists' plans
+  const bool scored = (n_shards == 1 || n_shards <= env.scored_shards) && B >= 2048 && filter_scored_lists(B, D, k, env);  // (below 2048 queries the plain lists' plans
                                                                                    // stay: a smaller first sample measured slower)
   // (the model's price of an int8 candidate under scored lists, relative to the plain lists'; fitted: 0.6 moves 8192+ queries
   // x 1M keys from two levels to three, all int8 -- 8192: 2.37 -> 2.33 ms, 16384: 4.30 -> 4.13 -- while 0.45 also shrank the
-  // first sample of 2048 - 8192 queries, which measured 2 - 4 % slower; RAGRAPH_FILTER_SCORED_CAND: A/B)
-  static const double scored_cand = [] { const char* e = getenv("RAGRAPH_FILTER_SCORED_CAND"); return e ? atof(e) : 0.6; }();
-  const bool bound = N >= 8192 && filter_bound_pass_enabled();
+  // first sample of 2048 - 8192 queries, which measured 2 - 4 % slower)
+  constexpr double scored_cand = 0.6;
+  const bool bound = N >= FILTER_BOUND_MIN_KEYS;
   // int8 levels (filter_common.h): D = 128 / 256, the ring kernel's batch sizes, banks long enough to be matrix-bound (an
   // int8 level quantises its queries from the fp32 rows per segment where the bf16 levels of up to 16384 queries load a
   // prepared image -- Cora-sized 2708 x 10 000 x 128: 0.087 -> 0.100 ms)
-  static const bool i8_d64 = [] { const char* e = getenv("RAGRAPH_FILTER_I8_D64"); return !e || atoi(e) != 0; }();  // A/B
   // (D = 64, the edge flavour: one MFMA per 16-key half and query group, so the epilogue weighs more -- 65 536 x 4M x 64:
   // 22.5 -> 15.5 ms with eight groups per wave; eps is the same 0.02 but the scores' spread is 1/8: fewer extra candidates)
   // (with the prepared int8 operand image and the scored lists, D = 256 also pays on banks of 32 768+ keys from 2048 queries:
   // 4096 x 40 000: 0.189 -> 0.160 ms, 2100 x 60 000: 0.180 -> 0.150, 16 384 x 50 000: 0.64 -> 0.49; not at D = 128 -- 8192 x
   // 50 000: 0.237 -> 0.244 -- nor on shorter banks -- 8192 x 20 000 x 256: 0.221 -> 0.238)
-  const bool i8_ok = (D == 128 || D == 256 || (D == 64 && i8_d64)) && B > 256 &&
+  const bool i8_ok = (D == 64 || D == 128 || D == 256) && B > 256 &&
                      (N * n_shards >= 65536 || (D == 256 && B >= 2048 && N * n_shards >= 32768));
   const bool mid_i8 = i8_ok && N * n_shards < 65536;
   static const bool i8_direct_env = [] { const char* e = getenv("RAGRAPH_FILTER_I8_DIRECT"); return !e || atoi(e) != 0; }();  // A/B
@@ -276,14 +338,11 @@ static FilterSchedule filter_schedule(int64_t B, int64_t N, int D, int k, int n_
     // the direct kernel deals the prefix's 16-KiB units over all waves of the chip in contiguous runs: 2.4 units per wave take
     // as long as 3 -- a prefix of whole rounds (8 waves x CUs units) costs what it reads: 256 queries x 1M 0.1406 -> 0.1381 ms,
     // 192: 0.1198 -> 0.1180 (up to 128 queries, whose pass is cheaper per key, the shorter prefix loses more than it saves:
-    // 64 queries 0.110 -> 0.116).  RAGRAPH_FILTER_BOUND_ROUNDS=0: A/B
-    static const int align_env = [] { const char* e = getenv("RAGRAPH_FILTER_BOUND_ROUNDS"); return e ? atoi(e) : 1; }();
-    if (align_env) {
-      const int64_t round_keys = (int64_t)8 * filter_device_cus() * (16384 / (2 * D));
-      int64_t r = (sc.bound_keys + round_keys / 2) / round_keys;
-      if (r < 1) r = 1;
-      if (r * round_keys * 4 <= N && r * round_keys >= (int64_t)k * 4 * (FILTER_STAGE_BYTES / (2 * D))) sc.bound_keys = r * round_keys;
-    }
+    // 64 queries 0.110 -> 0.116).
+    const int64_t round_keys = (int64_t)8 * cus * (16384 / (2 * D));
+    int64_t r = (sc.bound_keys + round_keys / 2) / round_keys;
+    if (r < 1) r = 1;
+    if (r * round_keys * 4 <= N && r * round_keys >= (int64_t)k * 4 * (FILTER_STAGE_BYTES / (2 * D))) sc.bound_keys = r * round_keys;
   }
   sc.n0 = best_n0;
   sc.i8_levels = mid_i8 ? best_L : best_i8;
@@ -303,4 +362,163 @@ static FilterSchedule filter_schedule(int64_t B, int64_t N, int D, int k, int n_
   if (sc.bound_keys == 0 && B * sc.n0 > FILTER_SLAB_MAX_SCORES) sc.slab0 = 0;
   filter_align_ends(sc, D);
   return sc;
+}
+
+// Which levels run on the int8 copy: the LAST level of a large batch (D = 128 / 256).  Its threshold is the highest of the
+// call, so the ~4x wider eps costs ~100 extra candidates per query (1 KiB row gathers: ~2.5 ms at the bench shape) where
+// the matrix work of three quarters of the bank halves (25.6 -> ~13 ms).  Earlier levels and smaller batches stay on
+// bf16: a level of a few thousand queries is not matrix-bound enough to pay for the extra rescoring.
+// RAGRAPH_FILTER_I8 = n forces the last n levels (0: none) -- A/B runs and the tests of the int8 path on small shapes.
+// i8_cap: the calling thread's cap (ragraph_topk_cosine_filtered_max_i8_levels: -1 = the rule below, 0 = none).
+static int filter_i8_levels(const FilterSchedule& sc, int64_t B, int i8_cap, const FilterEnv& env) {
+  if (B <= 256) {  // the direct kernel's int8 form: every level or none, as the schedule planned
+    if (i8_cap == 0 || sc.i8_levels == 0) return 0;
+    return sc.nlev;
+  }
+  if (env.i8 >= 0) return env.i8 < sc.nlev ? env.i8 : sc.nlev;
+  if (i8_cap == 0) return 0;
+  // The schedule plans them (filter_schedule: sc.i8_levels -- the level STRUCTURE never depends on the per-thread cap, so
+  // the shards of a bank keep the same phases whatever each thinks of its rows).  Measured on the 1M x 256 bank (ms per
+  // call, 0 / 1 / 2 int8 levels on round 2's schedules; profiles/r3_i8_ab.txt): 1024 queries 0.538 / 0.519 / 0.505; 2048:
+  // 0.98 / 0.80 / 0.83; 4096: 1.75 / 1.34 / 1.28; 16384: 6.09 / 4.55 / 4.19; 100 000 (the bench step): 38.3 / 28.3 / 26.9
+  // (three: 27.7); with the schedule chosen for int8 (two levels, the second on int8): 512: 0.314 -> 0.276, 1024: 0.509 -> 0.426.
+  int n = sc.i8_levels < sc.nlev ? sc.i8_levels : sc.nlev;
+  if (i8_cap > 0 && n > i8_cap) n = i8_cap;
+  return n;
+}
+
+enum FilterLevel0 {
+  FILTER_L0_NONE,   // theta = the prior (the prepare launch writes it)
+  FILTER_L0_BOUND,  // the bound pass over keys [0, bound_keys) of the bf16 copy, `parts` part maxima per query
+  FILTER_L0_SLAB,   // exact top-k of the first n0 keys: dense kernel + topk_rows
+  FILTER_L0_TILE    // ... the fp32 tile kernel
+};
+struct FilterLevel {
+  int64_t key0, key1;
+  bool int8, scored;  // on the int8 copy; with {key, I} lists
+};
+// What a call does, in the order it does it.  run_filtered executes this and decides nothing itself; the size query and the
+// host queries read the same object.
+struct FilterCall {
+  int cap;                 // slots of a query's candidate region (filter_cap)
+  bool scored_slots;       // ... of 8 bytes: the call may keep scored lists (sharded calls of the same shape do not use them)
+  bool exact_participant;  // a shard too short for the plan's phases: its fp32 top-k, offered at every exchange (nlev,
+                           // spec and first_phase are all that is planned for it)
+  bool spec;               // speculative first bound: no bound pass, no phase 0, a verify launch behind the last level
+  FilterLevel0 level0;
+  size_t level0_bytes;     // level 0's scratch at the head of the workspace: the tile kernel's, or the score slab
+  int64_t n0, bound_keys;  // keys of an exact level 0 / of the bound pass (0: none)
+  int parts;               // part maxima per query of the bound pass (else k)
+  int nlev, i8_levels;
+  FilterLevel level[FILTER_MAX_LEVELS];
+  bool bf16_image;         // the prepare launch writes the queries' bf16 operand image: only launches on the bf16 copy read it -- a
+                           // call whose levels all run on the int8 copy and that has no bound pass, e.g. every call under a
+                           // prior, saves writing 2 D bytes per query
+  int first_phase;         // sharded calls: the exchange is called at phases first_phase .. nlev - 1
+};
+
+static void filter_drop_first_level(FilterSchedule& sc) {
+  for (int l = 0; l + 1 < sc.nlev; ++l) sc.ends[l] = sc.ends[l + 1];
+  --sc.nlev;
+  if (sc.i8_levels > sc.nlev) sc.i8_levels = sc.nlev;
+}
+
+// The plan of one call from the schedule of (B, plan_N, D, k, exchange ? n_shards : 1): every adjustment of that schedule
+// to the prior, to this shard's own length and to the sharing of the first sample happens here, once.
+static FilterCall filter_call_plan(const FilterShape& in, FilterSchedule sc) {
+  const int64_t B = in.B, N = in.N, plan_N = in.plan_N;
+  const int D = in.D, k = in.k, ns = in.exchange ? in.n_shards : 1;
+  const int stage_keys = FILTER_STAGE_BYTES / (2 * D);
+  FilterCall c{};
+  c.cap = filter_cap(B, k);
+  c.scored_slots = filter_scored_lists(B, D, k, in.env);
+  const bool prior_ok = in.prior == in.prior && in.prior > -2.f && in.prior < 2.f;
+  // Under the prior the first level goes.  A first level exists to give the second a tighter bound than the bound pass
+  // could; the prior already is one.  Measured with it (1M x 256, ms per call, two levels / one): 2048 queries 0.544 / 0.512,
+  // 4096: 0.920 / 0.898 -- but 16 384: 3.18 / 3.85, and the three levels of 100 000 queries stay (20.5 ms per step against 22.8
+  // with two): up to 4096 queries one level.
+  // Three levels under the prior, many shards: the first level (1 / 32 of the shard) exists to sharpen the bound pass's
+  // bound, and under the group's prior it passes about ONE candidate per query and shard (measured, 8 shards of the 1M bank) --
+  // a filter launch on the bf16 copy, a rescoring launch over every query and an exchange for nothing.  From
+  // RAGRAPH_FILTER_SPEC_SHARDS_TWO_LEVELS shards (default 2: every sharded bank; 0 = never) the call runs levels [0, N / 4) and
+  // [N / 4, N): emulated rank of 2 / 4 / 8, ms per step: 11.14 -> 10.83, 6.29 -> 5.92, 3.73 -> 3.46 (profiles/r6_multi_one_gpu.txt).
+  const int spec_two = in.env.spec_two_shards;
+  auto drop_first_level_under_prior = [&] {
+    if ((sc.nlev == 2 && B <= 4096) || (in.exchange && sc.nlev == 3 && spec_two > 0 && in.n_shards >= spec_two))
+      filter_drop_first_level(sc);
+  };
+  if (in.exchange) {
+    // Sharded banks: whether the call speculates must be the SAME decision on every rank -- it removes the bound pass AND its
+    // exchange (phase 0) --, so it is taken from what every rank shares: the prior (the caller derives it from pooled
+    // statistics and sets it on every rank alike) and the PLAN's bound pass (plan_N), before any adjustment to this shard's
+    // own length.  The proof is the caller's too: a query is exact iff the k-th best of the MERGED lists reaches the prior
+    // (ragraph_amd/sharded.py verifies at the rows' owner and re-runs without the prior).
+    c.spec = prior_ok && sc.bound_keys > 0;
+    if (c.spec) drop_first_level_under_prior();
+    // A shard SHORTER than the largest one (shards of a bank whose exact duplicates were collapsed per shard hold different
+    // numbers of unique rows): the same phases -- the exchanges must line up across the ranks -- over proportionally fewer
+    // keys; a shard too short for that structure takes part as an EXACT participant: its fp32 top-k once, offered at every
+    // exchange (exact scores of k distinct keys are valid lower bounds at every phase).
+    if (plan_N - N > 1024) {
+      int64_t prev = 0;
+      for (int l = 0; l + 1 < sc.nlev; ++l) {
+        int64_t e = (int64_t)((double)sc.ends[l] * (double)N / (double)plan_N) / 512 * 512;   // (512: whole int8 stages at any width)
+        if (e < prev + 512 || e + 512 > N) c.exact_participant = true;
+        sc.ends[l] = e;
+        prev = e;
+      }
+      sc.bound_keys = (int64_t)((double)sc.bound_keys * (double)N / (double)plan_N) / FILTER_PAD_KEYS * FILTER_PAD_KEYS;
+      if (sc.nlev > 1 && sc.bound_keys > sc.ends[0]) sc.bound_keys = sc.ends[0];
+      if (sc.bound_keys / stage_keys < (int64_t)filter_bound_parts(k, sc.bound_keys, D, B, in.n_shards)) sc.bound_keys = 0;
+      if (sc.n0 > N) sc.n0 = N;
+      if (N < 16384 || N * 8 < plan_N) c.exact_participant = true;
+    }
+  }
+  c.first_phase = c.spec ? 1 : 0;   // phase 0 pools the first bounds: not under a speculative one
+  c.nlev = sc.nlev;
+  if (c.exact_participant) return c;
+  sc.ends[sc.nlev - 1] = N;
+  // The bound pass gives way to an exact level 0 where its prefix is more than half of this shard -- or where a size query
+  // asks what that would need: the workspace is sized for whichever of the two needs more.
+  if (sc.bound_keys > N / 2 || in.exact_level0) {
+    sc.bound_keys = 0;
+    if (sc.n0 > N) sc.n0 = N;
+  }
+  if (in.exchange && in.n_shards > 1 && sc.bound_keys > 0 && B <= FILTER_SLAB_MAX_B && plan_N >= 4 * 4096) {  // (the cost-model branch)
+    // G shards pool their samples through the exchange (the k-th largest of the union of every shard's best group
+    // maxima): each scans 1/G of the prefix one bank would -- at least one stage per part
+    const int64_t min_keys = filter_round_up((int64_t)k * stage_keys);
+    const int64_t bk = filter_round_up(sc.bound_keys / in.n_shards);
+    sc.bound_keys = bk < min_keys ? (min_keys < sc.bound_keys ? min_keys : sc.bound_keys) : bk;
+  }
+  if (!in.exchange) {
+    // One bank whose schedule has a bound pass to save: theta = prior for every query, every level filters with max(prior,
+    // the running k-th best), and the verify launch behind the last level sends the queries the prior was too high for to
+    // the exact scan.
+    c.spec = prior_ok && sc.bound_keys > 0 && N == plan_N;
+    if (c.spec) drop_first_level_under_prior();
+  }
+  const bool bound = sc.bound_keys > 0 && !c.spec;
+  c.level0 = c.spec ? FILTER_L0_NONE : (bound ? FILTER_L0_BOUND : (sc.slab0 ? FILTER_L0_SLAB : FILTER_L0_TILE));
+  c.level0_bytes = sc.bound_keys > 0 ? 0
+                   : sc.slab0        ? align_up((size_t)(B < FILTER_SLAB_MAX_B ? B : FILTER_SLAB_MAX_B) * (size_t)sc.n0 * sizeof(float), 256)
+                                     : ragraph_topk_cosine_workspace_bytes(B, sc.n0, D, k);
+  c.n0 = sc.n0;
+  c.bound_keys = sc.bound_keys;
+  c.parts = bound ? filter_bound_parts(k, sc.bound_keys, D, B, ns) : k;
+  c.nlev = sc.nlev;
+  c.i8_levels = filter_i8_levels(sc, B, in.i8_cap, in.env);
+  c.bf16_image = B <= FILTER_QB_MAX_B && (B <= 256 || bound || c.nlev > c.i8_levels);
+  for (int l = 0; l < c.nlev; ++l) {
+    FilterLevel& lv = c.level[l];
+    lv.key0 = l ? sc.ends[l - 1] : 0;   // the first level re-reads [0, n0): its keys pass the bound and need no merge
+    lv.key1 = sc.ends[l];
+    lv.int8 = l >= c.nlev - c.i8_levels;
+    // (sharded banks keep the plain lists: a level's threshold already is the k-th best over ALL shards -- sharper than
+    // anything round 1 can find among this shard's keys, so nothing is pruned and only the second round's latency and the
+    // 16-row tiles' occupancy are lost: emulated rank of 2 / 4 / 8 GPUs 13.49 -> 13.26 / 7.61 -> 8.00 / 4.76 -> 5.24 ms per
+    // step, profiles/r3_emul.txt.  RAGRAPH_FILTER_SCORED_SHARDS = largest shard count that takes them: A/B.)
+    lv.scored = lv.int8 && (!in.exchange || in.n_shards <= in.env.scored_shards) && c.scored_slots;
+  }
+  return c;
 }

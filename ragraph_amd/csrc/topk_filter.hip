@@ -39,7 +39,6 @@
 #include <new>
 #include "segment_plan.h"
 #include <cmath>
-#include <vector>
 #include <type_traits>
 
 namespace ragraph {
@@ -111,46 +110,6 @@ __device__ __forceinline__ void fring_signal(unsigned* ctr, int lane) {
 #include "filter_rescore.h"
 
 #include "filter_verify_fixup.h"
-
-static bool rescore_coop() {  // RAGRAPH_RESCORE_COOP=0: every lane reads its own row (A/B)
-  static const bool on = [] {
-    const char* e = getenv("RAGRAPH_RESCORE_COOP");
-    return !(e && atoi(e) == 0);
-  }();
-  return on;
-}
-
-// Scored candidate lists for the int8 levels (topk_rescore_scored_kernel): calls whose rescoring is bound by the row
-// gathers, i.e. the ones that take the one-wave-per-query kernels.  RAGRAPH_FILTER_SCORED=0/1: A/B.
-// D = 256 only: measured with / without (ms per call, profiles/r3_scored_ab.txt) 2048 x 1M x 256: 0.874 / 0.836, 16384:
-// 4.50 / 4.21, 100 000: 24.4 / 22.8; but 50 000 x 2M x 128: 12.71 / 12.63 and 65 536 x 4M x 64: 15.73 / 15.93 -- shorter rows
-// are cheaper to fetch and their scores spread wider against the same eps (fewer extra candidates to prune), so the
-// second round only adds latency.
-// k <= 16: round 1 is 16 rows and lists beyond 256 entries take the plain path -- 50 000 x 1M x 256 at k = 16: 14.5 / 13.7 ms,
-// k = 20: 15.6 / 15.8, k = 32: 18.7 / 20.3.
-static bool filter_scored_lists(int64_t B, int D, int k) {
-  const char* env_s = getenv("RAGRAPH_FILTER_SCORED");  // (read per call: the tests switch it)
-  const int env = env_s ? atoi(env_s) : -1;
-  // every call of the ring kernel (> 256 queries) ...: a scored list needs so few rows that ONE wave per query beats the
-  // four-wave workgroups of the wide kernels even at a few hundred queries, whose single level admits ~380 candidates per
-  // query and prunes 90 % of them (257 x 1M x 256: 0.214 -> 0.189 ms, 512: 0.267 -> 0.228, 1024: 0.436 -> 0.377, 1536: 0.580 ->
-  // 0.490; RAGRAPH_FILTER_SCORED_MIN_B: A/B)
-  // ... and the direct kernel's calls of 65 - 256 queries (entries carry ceil(I / 256)): 128 x 1M: 0.111 -> 0.106 ms, 256:
-  // 0.148 -> 0.136.  Up to 64 queries the direct kernel keeps several sub-lists per query and several workgroups rescore
-  // each: one wave per query measured slower there (one query 0.075 -> 0.080 ms).
-  static const int64_t min_b = [] { const char* e = getenv("RAGRAPH_FILTER_SCORED_MIN_B"); return e ? (int64_t)atoll(e) : (int64_t)65; }();
-  if (B < (min_b > 65 ? min_b : 65) || !rescore_coop()) return false;
-  if (env >= 0) return env != 0;
-  return D == 256 && k <= 16;
-}
-
-static bool filter_wide_waves(int64_t B) {  // RAGRAPH_FILTER_QW128=0/1: A/B; default from 1024 queries (one full tile)
-  static const int env = [] {
-    const char* e = getenv("RAGRAPH_FILTER_QW128");
-    return e ? atoi(e) : -1;
-  }();
-  return env < 0 ? B >= 1024 : env != 0;
-}
 
 static int filter_device_cus() { return device_cus_multiple_of_8(); }  // per device (common.h)
 
@@ -233,13 +192,9 @@ extern "C" int ragraph_filter_profile_levels(ragraph_filter_profile* p, float* m
 
 #include "filter_schedule.h"
 
-// Which levels run on the int8 copy: the LAST level of a large batch (D = 128 / 256).  Its threshold is the highest of the
-// call, so the ~4x wider eps costs ~100 extra candidates per query (1 KiB row gathers: ~2.5 ms at the bench shape) where
-// the matrix work of three quarters of the bank halves (25.6 -> ~13 ms).  Earlier levels and smaller batches stay on
-// bf16: a level of a few thousand queries is not matrix-bound enough to pay for the extra rescoring.
-// RAGRAPH_FILTER_I8 = n forces the last n levels (0: none) -- A/B runs and the tests of the int8 path on small shapes.
 // A caller that knows its bank (ragraph_amd/kernels_index.py: the copy's measured error, or a call that overflowed) caps
-// the int8 levels of ITS thread's following calls: -1 = the rule below, 0 = none.  Thread-local: no shared state.
+// the int8 levels (filter_schedule.h: filter_i8_levels) of ITS thread's following calls: -1 = the library's rule, 0 = none.
+// Thread-local: no shared state.
 static thread_local int t_max_i8_levels = -1;
 // A SPECULATIVE first bound for the calling thread's following filtered calls (NaN = none, the default): the owner of a bank
 // that has answered many queries knows where their k-th best scores lie (the statistics words of every call), and a call
@@ -271,33 +226,6 @@ int ragraph::launch_overflow_fixup(int D, const float* Qn, const float* Kn, int6
 #undef RG_FIX
   RG_CHECK_LAUNCH("overflow fixup");
   return RAGRAPH_OK;
-}
-
-static int filter_i8_levels(const FilterSchedule& sc, int64_t B, int D, int64_t N) {
-  const char* env = getenv("RAGRAPH_FILTER_I8");  // (read per call: the tests switch it)
-  const int force = env ? atoi(env) : -1;
-  if (D != 64 && D != 128 && D != 256) return 0;
-  if (B <= 256) {  // the direct kernel's int8 form: every level or none, as the schedule planned
-    if (t_max_i8_levels == 0 || sc.i8_levels == 0) return 0;
-    return sc.nlev;
-  }
-  if (force >= 0) return force < sc.nlev ? force : sc.nlev;
-  if (t_max_i8_levels == 0) return 0;
-  // The schedule plans them (filter_schedule: sc.i8_levels -- the level STRUCTURE never depends on the per-thread cap, so
-  // the shards of a bank keep the same phases whatever each thinks of its rows).  Measured on the 1M x 256 bank (ms per
-  // call, 0 / 1 / 2 int8 levels on round 2's schedules; profiles/r3_i8_ab.txt): 1024 queries 0.538 / 0.519 / 0.505; 2048:
-  // 0.98 / 0.80 / 0.83; 4096: 1.75 / 1.34 / 1.28; 16384: 6.09 / 4.55 / 4.19; 100 000 (the bench step): 38.3 / 28.3 / 26.9
-  // (three: 27.7); with the schedule chosen for int8 (two levels, the second on int8): 512: 0.314 -> 0.276, 1024: 0.509 -> 0.426.
-  int n = sc.i8_levels < sc.nlev ? sc.i8_levels : sc.nlev;
-  if (t_max_i8_levels > 0 && n > t_max_i8_levels) n = t_max_i8_levels;
-  return n;
-}
-
-// workspace of level 0: the tile kernel's, or the score slab
-static size_t filter_level0_ws(const FilterSchedule& sc, int64_t B, int D, int k) {
-  if (sc.bound_keys > 0) return 0;
-  return sc.slab0 ? align_up((size_t)(B < FILTER_SLAB_MAX_B ? B : FILTER_SLAB_MAX_B) * (size_t)sc.n0 * sizeof(float), 256)
-                  : ragraph_topk_cosine_workspace_bytes(B, sc.n0, D, k);
 }
 
 static bool filter_dim_ok(int D) { return D == 64 || D == 128 || D == 256; }
@@ -361,63 +289,11 @@ extern "C" int64_t ragraph_keys_bf16_rows(int64_t N) {
   return npad + 1 + npad / 2 + 1 + (npad / 4096 + 8) + FILTER_COPY_SLACK_ROWS;
 }
 
-extern "C" int ragraph_topk_cosine_filtered_cap(int k) { return 2048; }
-static int rescore_slices(int64_t B, int k);
-// slots of a query's candidate region: one list, or (<= 64 queries) one full-size list per rescoring slice
-static int filter_cap(int64_t B, int k) { return ragraph_topk_cosine_filtered_cap(k) * (B <= 64 ? rescore_slices(B, k) : 1); }
-
-static size_t filter_ws_carve(char* w, int64_t B, int D, int k, int cap, struct FilterWs* out);
+extern "C" int ragraph_topk_cosine_filtered_cap(int k) { return FILTER_LIST_CAP; }
 
 constexpr size_t FILTER_STATS_BYTES = 256;  // (the statistics block plus the slack that aligns it)
 extern "C" size_t ragraph_topk_cosine_filtered_stats_offset(size_t ws_bytes) {
   return ws_bytes < FILTER_STATS_INTS * sizeof(int) ? 0 : (ws_bytes - FILTER_STATS_INTS * sizeof(int)) & ~(size_t)15;
-}
-
-static size_t filter_workspace_bytes(int64_t B, int64_t N, int D, int k, int n_shards) {
-  if (B < 1 || N < 1 || k < 1 || n_shards < 1 || !filter_dim_ok(D)) return 0;
-  const int cap = filter_cap(B, k);
-  // run_filtered may turn the planned bound pass into an exact level 0 (a shard shorter than twice the prefix, a shard's
-  // share of a pooled sample, the schedule switches): size for whichever of the two needs more, and run_filtered checks
-  // the schedule it really runs against ws_bytes before carving
-  FilterSchedule sc = filter_schedule(B, N, D, k, n_shards);
-  size_t level0 = filter_level0_ws(sc, B, D, k);
-  if (sc.bound_keys > 0) {
-    sc.bound_keys = 0;
-    const size_t exact0 = filter_level0_ws(sc, B, D, k);
-    if (exact0 > level0) level0 = exact0;
-  }
-  return level0 + filter_ws_carve(nullptr, B, D, k, cap, nullptr) + FILTER_STATS_BYTES;
-}
-
-extern "C" size_t ragraph_topk_cosine_filtered_workspace_bytes(int64_t B, int64_t N, int D, int k) {
-  return filter_workspace_bytes(B, N, D, k, 1);
-}
-// The sharded entry plans for (plan_N, n_shards): its first sample can be another one than the single bank's of plan_N rows.
-extern "C" size_t ragraph_topk_cosine_filtered_sharded_workspace_bytes(int64_t B, int64_t plan_N, int D, int k, int n_shards) {
-  if (!filter_dim_ok(D)) return 0;  // (ragraph_topk_cosine_f32 alone takes other widths)
-  const size_t a = filter_workspace_bytes(B, plan_N, D, k, n_shards), b = filter_workspace_bytes(B, plan_N, D, k, 1);
-  const size_t c = ragraph_topk_cosine_workspace_bytes(B, plan_N, D, k);   // (a short shard's exact top-k)
-  const size_t ab = a > b ? a : b;  // (exchange = NULL runs the single-bank schedule)
-  return ab > c ? ab : c;
-}
-
-extern "C" int ragraph_topk_cosine_filtered_i8_levels(int64_t B, int64_t N, int D, int k) {
-  if (B < 1 || N < 1 || k < 1 || k > 32 || k > N || !filter_dim_ok(D)) return 0;
-  const FilterSchedule sc = filter_schedule(B, N, D, k);
-  return filter_i8_levels(sc, B, D, N);
-}
-
-extern "C" int ragraph_topk_cosine_filtered_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]) {
-  RG_REQUIRE(plan, RAGRAPH_EINVAL, "topk_cosine_filtered_plan: null pointer");
-  RG_REQUIRE(filter_dim_ok(D), RAGRAPH_EUNSUPPORTED, "topk_cosine_filtered_plan: D=%d not in {64,128,256}", D);
-  RG_REQUIRE(B >= 1 && N >= 1 && k >= 1 && k <= 32 && k <= N, RAGRAPH_EINVAL, "topk_cosine_filtered_plan: bad B/N/k");
-  const FilterSchedule sc = filter_schedule(B, N, D, k);
-  plan[0] = sc.n0;
-  plan[1] = sc.bound_keys > 0 ? 2 : sc.slab0;
-  plan[2] = sc.nlev;
-  for (int l = 0; l < FILTER_MAX_LEVELS; ++l) plan[3 + l] = l < sc.nlev ? sc.ends[l] : 0;
-  plan[6] = sc.bound_keys;
-  return sc.nlev;
 }
 
 // Everything one call keeps in its workspace behind level 0's scratch.
@@ -441,7 +317,9 @@ struct FilterWs {
   signed char* Qb8;     // (B <= FILTER_QB_MAX_B) the queries as int8 B operands in fragment order, padded to whole groups of 32
 };
 
-static size_t filter_ws_carve(char* w, int64_t B, int D, int k, int cap, FilterWs* out) {
+static size_t filter_ws_carve(char* w, const FilterShape& in, const FilterCall& c, FilterWs* out) {
+  const int64_t B = in.B;
+  const int D = in.D, k = in.k;
   size_t off = 0;
   auto take = [&](size_t bytes) {
     char* ptr = w ? w + off : nullptr;
@@ -454,8 +332,8 @@ static size_t filter_ws_carve(char* w, int64_t B, int D, int k, int cap, FilterW
   f.eq = reinterpret_cast<float*>(take((size_t)B * sizeof(float)));
   f.count = reinterpret_cast<int*>(take((size_t)B * filter_count_stride(B) * sizeof(int)));
   f.flag = reinterpret_cast<unsigned char*>(take((size_t)B));
-  // (a call that may keep scored lists -- {key, I} -- gets 8 bytes per slot; sharded calls of the same shape do not use them)
-  f.cand = reinterpret_cast<int*>(take((size_t)B * cap * (filter_scored_lists(B, D, k) ? sizeof(int2) : sizeof(int))));
+  // (a call that may keep scored lists -- {key, I} -- gets 8 bytes per slot)
+  f.cand = reinterpret_cast<int*>(take((size_t)B * c.cap * (c.scored_slots ? sizeof(int2) : sizeof(int))));
   f.gmax = reinterpret_cast<int*>(take((size_t)B * filter_bound_parts(k, INT64_MAX, 256) * sizeof(int)));
   f.theta = reinterpret_cast<float*>(take((size_t)B * sizeof(float)));
   f.overflow_list = reinterpret_cast<int*>(take((size_t)B * sizeof(int)));
@@ -471,32 +349,89 @@ static size_t filter_ws_carve(char* w, int64_t B, int D, int k, int cap, FilterW
   return off;
 }
 
-// A handful of queries: S workgroups rescore a query (S k <= 256 partial winners for the merge launch), and the direct
-// kernel keeps S sub-lists per query, one per rescoring workgroup (filter_common.h: FILTER_COUNT_STRIDE).
-static int rescore_slices(int64_t B, int k) {
-  static const int slice_env = [] {  // RAGRAPH_RESCORE_SLICES: A/B (0 or 1 = never slice; a power of two <= 8)
-    const char* e = getenv("RAGRAPH_RESCORE_SLICES");
-    return e ? atoi(e) : -1;
-  }();
-  int S = B <= 16 ? 8 : (B <= 32 ? 4 : (B <= 64 ? 2 : 1));
-  if (slice_env >= 0) S = slice_env >= 8 ? 8 : (slice_env >= 4 ? 4 : (slice_env >= 2 ? 2 : 1));
-  if (B > 64) S = 1;  // (part_s / part_i exist up to 64 queries)
-  while (S > 1 && S * k > 256) S >>= 1;
-  return S;
+// ---- the host queries: readers of the call plan ---------------------------------------------------------------------
+// The one argument check of the plan's readers and of the call: 0, or the error code of a shape no filtered call takes.
+static int filter_shape_code(int64_t B, int64_t N, int D, int k) {
+  if (!filter_dim_ok(D)) return RAGRAPH_EUNSUPPORTED;
+  return B >= 1 && N >= 1 && k >= 1 && k <= 32 && k <= N ? RAGRAPH_OK : RAGRAPH_EINVAL;
+}
+#define RG_REQUIRE_FILTER_SHAPE(who, B, N, D, k)                                                                      \
+  do {                                                                                                                \
+    const int code__ = filter_shape_code(B, N, D, k);                                                                 \
+    RG_REQUIRE(code__ != RAGRAPH_EUNSUPPORTED, RAGRAPH_EUNSUPPORTED, who ": D=%d not in {64,128,256}", D);           \
+    RG_REQUIRE(code__ == RAGRAPH_OK, RAGRAPH_EINVAL, who ": bad B/N/k");                                              \
+  } while (0)
+
+// The shape a query asks about: one bank of N rows, or the largest of n_shards shards, without a prior.
+static FilterShape filter_query_shape(int64_t B, int64_t N, int D, int k, int n_shards, bool exchange) {
+  return {B, N, N, D, k, n_shards, exchange, __builtin_nanf(""), -1, false, filter_env(), filter_device_cus()};
+}
+
+// A call may replace the planned bound pass by an exact level 0 (a shard shorter than twice the prefix, a shard's share of
+// a pooled sample): the size covers whichever of the two needs more, and run_filtered checks the plan it really runs
+// against ws_bytes before carving.
+static size_t filter_workspace_bytes(FilterShape in, const FilterSchedule& sc) {
+  const FilterCall planned = filter_call_plan(in, sc);
+  in.exact_level0 = true;
+  const FilterCall exact0 = filter_call_plan(in, sc);
+  return (planned.level0_bytes > exact0.level0_bytes ? planned.level0_bytes : exact0.level0_bytes) +
+         filter_ws_carve(nullptr, in, planned, nullptr) + FILTER_STATS_BYTES;
+}
+static size_t filter_workspace_bytes(int64_t B, int64_t N, int D, int k, int n_shards) {
+  if (B < 1 || N < 1 || k < 1 || n_shards < 1 || !filter_dim_ok(D)) return 0;
+  const FilterShape in = filter_query_shape(B, N, D, k, n_shards, n_shards > 1);
+  return filter_workspace_bytes(in, filter_schedule(in));
+}
+
+extern "C" size_t ragraph_topk_cosine_filtered_workspace_bytes(int64_t B, int64_t N, int D, int k) {
+  return filter_workspace_bytes(B, N, D, k, 1);
+}
+// The sharded entry plans for (plan_N, n_shards): its first sample can be another one than the single bank's of plan_N rows.
+extern "C" size_t ragraph_topk_cosine_filtered_sharded_workspace_bytes(int64_t B, int64_t plan_N, int D, int k, int n_shards) {
+  if (!filter_dim_ok(D)) return 0;  // (ragraph_topk_cosine_f32 alone takes other widths)
+  const size_t a = filter_workspace_bytes(B, plan_N, D, k, n_shards), b = filter_workspace_bytes(B, plan_N, D, k, 1);
+  const size_t c = ragraph_topk_cosine_workspace_bytes(B, plan_N, D, k);   // (a short shard's exact top-k)
+  const size_t ab = a > b ? a : b;  // (exchange = NULL runs the single-bank schedule)
+  return ab > c ? ab : c;
+}
+
+extern "C" int ragraph_topk_cosine_filtered_i8_levels(int64_t B, int64_t N, int D, int k) {
+  if (filter_shape_code(B, N, D, k) != RAGRAPH_OK) return 0;
+  FilterShape in = filter_query_shape(B, N, D, k, 1, false);
+  in.i8_cap = t_max_i8_levels;
+  return filter_call_plan(in, filter_schedule(in)).i8_levels;
+}
+
+extern "C" int ragraph_topk_cosine_filtered_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]) {
+  RG_REQUIRE(plan, RAGRAPH_EINVAL, "topk_cosine_filtered_plan: null pointer");
+  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered_plan", B, N, D, k);
+  const FilterShape in = filter_query_shape(B, N, D, k, 1, false);
+  // (the plan of one whole bank IS its schedule: filter_schedule leaves such a bank bound_keys <= N / 4 or <= ends[0] < N / 2
+  // and n0 <= N, so filter_call_plan's adjustments to a shard's own length change none of the words below)
+  const FilterCall c = filter_call_plan(in, filter_schedule(in));
+  plan[0] = c.n0;
+  plan[1] = c.level0 == FILTER_L0_BOUND ? 2 : (c.level0 == FILTER_L0_SLAB ? 1 : 0);
+  plan[2] = c.nlev;
+  for (int l = 0; l < FILTER_MAX_LEVELS; ++l) plan[3 + l] = l < c.nlev ? c.level[l].key1 : 0;
+  plan[6] = c.bound_keys;
+  return c.nlev;
+}
+
+// Would a sharded call of this shape speculate under a prior?  (Any valid one: the answer is the plan's, not the value's.)
+extern "C" int ragraph_topk_cosine_filtered_sharded_speculates(int64_t B, int64_t plan_N, int D, int k, int n_shards) {
+  if (filter_shape_code(B, plan_N, D, k) != RAGRAPH_OK || n_shards < 1) return 0;
+  FilterShape in = filter_query_shape(B, plan_N, D, k, n_shards, true);
+  in.prior = 0.f;
+  return filter_call_plan(in, filter_schedule(in)).spec ? 1 : 0;
 }
 
 // Ring-kernel launch shared by the filter levels and the bound pass (B > 256: the direct kernel takes smaller batches).
 template <int D, int QW, bool BOUND, bool I8 = false, bool SCORED = false, bool PIPE = false>
-static int launch_ring(FilterParams p, int64_t B, int prof_slot, hipStream_t st) {
+static int launch_ring(FilterParams p, int64_t B, int CUS, int prof_slot, hipStream_t st) {
   using C = FilterCfg<I8 ? D / 2 : D>;
   p.qtiles = cdiv(B, (int64_t)C::WAVES * QW);
-  const int CUS = filter_device_cus();
   p.xcd_map = p.qtiles >= 64 ? 1 : 0;
   p.wgs_per_group = CUS / (p.xcd_map ? 8 : 1);
-  {
-    const char* e = getenv("RAGRAPH_FILTER_PARTNER_LEAD");  // (read per call: A/B; 0 = equal priorities, the hardware's age order)
-    p.partner_lead = e ? atoi(e) : 1;
-  }
   // shortest piece of a key stream a workgroup takes: 8 stages when there is work for everybody, fewer on short launches
   // (a bound pass of 18 stages x 6 query tiles gave 14 workgroups 8 stages each and 242 nothing: 19 us of stage loop where
   // 108 workgroups need 2.5; tools/check_segment_plan.cpp covers lb_min = 1)
@@ -513,9 +448,7 @@ static int launch_ring(FilterParams p, int64_t B, int prof_slot, hipStream_t st)
     // Short launches cut the remainder at once (depth 0): a workgroup WALKS the plan's lockstep steps to its segment, every
     // step a few 64-bit divisions, and with a few tiles over 256 workgroups the last ones walk ~40 of them -- 22.8 us of
     // a 39-us launch (2708 queries x 10 000 keys: -DRG_RING_STAMPS); the re-reads the steps save are nothing at this size.
-    static const int depth_env = [] { const char* e = getenv("RAGRAPH_FILTER_DEPTH"); return e ? atoi(e) : -1; }();  // A/B
     if (p.qtiles * p.nstages_total / CUS < 16) p.depth[v] = 0;
-    if (depth_env >= 0) p.depth[v] = depth_env < p.depth[v] ? depth_env : p.depth[v];
   }
   static DeviceOnce lds_once;  // per template instance and device (common.h)
   if (hipError_t e = raise_dynamic_lds(lds_once, &topk_filter_kernel<D, QW, BOUND, I8, SCORED, PIPE>, (int)C::LDS_BYTES); e != hipSuccess) {
@@ -526,117 +459,103 @@ static int launch_ring(FilterParams p, int64_t B, int prof_slot, hipStream_t st)
   hipLaunchKernelGGL((topk_filter_kernel<D, QW, BOUND, I8, SCORED, PIPE>), dim3((unsigned)CUS), dim3(C::THREADS), C::LDS_BYTES, st, p);
   if (t_prof) (void)hipEventRecord(t_prof->ev[2 * prof_slot + 1], st);
   RG_CHECK_LAUNCH("topk_cosine_filtered(filter)");
-#ifdef RG_RING_STAMPS
-  {
-    (void)hipDeviceSynchronize();
-    unsigned long long t[2][2][8];
-    (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_ring_t), sizeof(t));
-    for (int b = 0; b < 2; ++b)
-      fprintf(stderr, "[ring stamps, %s%s launch, %s workgroup, 10 ns ticks] operands %lld thresholds %lld ring primed %lld stages %lld "
-              "flush %lld (entered %lld after workgroup 0)\n", BOUND ? "bound" : "filter", I8 ? " int8" : "", b ? "last" : "first",
-              (long long)(t[BOUND][b][1] - t[BOUND][b][0]), (long long)(t[BOUND][b][2] - t[BOUND][b][1]),
-              (long long)(t[BOUND][b][3] - t[BOUND][b][2]), (long long)(t[BOUND][b][4] - t[BOUND][b][3]),
-              (long long)(t[BOUND][b][5] - t[BOUND][b][4]), (long long)(t[BOUND][b][0] - t[BOUND][0][0]));
-    unsigned long long span[2][2], mx[2][8];
-    (void)hipMemcpyFromSymbol(span, HIP_SYMBOL(g_ring_span), sizeof(span));
-    (void)hipMemcpyFromSymbol(mx, HIP_SYMBOL(g_ring_max), sizeof(mx));
-    fprintf(stderr, "[ring stamps, all workgroups] first entry to last exit %lld; longest first-segment phases: operands %lld thresholds %lld "
-            "ring primed %lld stages %lld flush %lld\n", (long long)(span[BOUND][1] - span[BOUND][0]), (long long)mx[BOUND][1],
-            (long long)mx[BOUND][2], (long long)mx[BOUND][3], (long long)mx[BOUND][4], (long long)mx[BOUND][5]);
-    unsigned long long init_span[2][2] = {{~0ull, 0ull}, {~0ull, 0ull}}, zero[2][8] = {};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ring_span), init_span, sizeof(init_span));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_ring_max), zero, sizeof(zero));
-  }
-#endif
-#ifdef RG_TOPK_TIMING
-  {
-    (void)hipDeviceSynchronize();
-    unsigned long long t[8];
-    (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_filter_timing), sizeof(t));
-    const double n = (double)t[5];
-    if (n > 0)
-      fprintf(stderr, "[filter timing] slot %d D=%d wave-stages=%.0f ticks/stage: wait_full %.1f compute %.1f signal+vmcnt "
-              "%.1f wait_free %.1f dma_issue %.1f total %.1f; flushes in the loop: %.0f, %.1f ticks each = %.1f per stage\n",
-              prof_slot, D, n, t[0] / n, t[1] / n, t[2] / n, t[3] / n, t[4] / n, (t[0] + t[1] + t[2] + t[3] + t[4]) / n, (double)t[7],
-              t[7] ? (double)t[6] / (double)t[7] : 0.0, t[6] / n);
-    unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_filter_timing), zero, sizeof(zero));
-  }
-#endif
+  ring_stamps_report(BOUND, I8);
+  ring_timing_report(prof_slot, D);
   return RAGRAPH_OK;
 }
 
-// One bf16 pass over keys [key0, key1) of the bank copy: a filter level (bound_groups = 0: candidates of every query
-// whose threshold `thr` describes) or the bound pass (bound_groups = k group maxima into gmax).  Up to 256 queries take
-// the direct kernel (topk_filter_direct.hip: the stream, not the matrix work, is what such a call costs), more the ring
-// kernel with two -- at D = 64 and long streams four -- query groups per wave.
-template <int D>
-static int run_bf16_pass(const FilterWs& f, const uint16_t* Kb, int64_t B, int64_t key0, int64_t key1, const FilterThr& thr,
-                         int cap, int bound_groups, int prof_slot, hipStream_t st, const signed char* Kb8 = nullptr,
-                         bool scored = false) {
-  using C = FilterCfg<D>;
-  {
-    if (Kb8 && B > 256) {  // an int8 level (filter_i8_levels): the ring kernel over the int8 copy, stages of twice as many keys
-      using C8 = FilterCfg<D / 2>;
-      FilterParams p{};
-      p.Qn = f.Qn;
-      p.Kb = reinterpret_cast<const uint16_t*>(Kb8);
-      p.thr = thr;
-      p.count = f.count;
-      p.cstride = filter_count_stride(B);
-      static const bool i8_image = [] { const char* e = getenv("RAGRAPH_FILTER_I8_IMAGE"); return !e || atoi(e) != 0; }();  // A/B
-      // (the int8 image, or NULL beyond FILTER_QB_MAX_B queries: quantised per segment)
-      p.Qb = i8_image ? reinterpret_cast<const uint16_t*>(f.Qb8) : nullptr;
-      p.cand = f.cand;
-      p.B = B;
-      p.N = key1;
-      p.cap = cap;  // (scored lists: {key, I} pairs, the same number of slots -- filter_ws_carve gives them 8 bytes each)
-      RG_REQUIRE(key0 % C8::STAGE_KEYS == 0, RAGRAPH_EINVAL, "topk_cosine_filtered: an int8 level must start at a whole stage "
-                 "(key %lld, %d keys per stage)", (long long)key0, (int)C8::STAGE_KEYS);
-      p.stage_base = key0 / C8::STAGE_KEYS;
-      p.nstages_total = cdiv(key1 - key0, C8::STAGE_KEYS);
-      // int8 operands are 16 bytes per 64 elements: SIX query groups per wave (tile = 768 queries) fit the registers four
-      // bf16 groups take (224 VGPRs, no scratch), and an A fragment then feeds six MFMAs, a stage 3072 cycles of them
-      // between two ring hand-overs: the bench's last level 14.45 -> 13.8 ms (A/B on one box, profiles/r3_i8_ab.txt).
-      // Eight groups (tile = 1024) spill (256 VGPRs + 80 B of scratch): 14.2 ms.  Long streams only, and only where the
-      // larger tile does not add padding queries (the last tile of 4096 queries would be a third full).
-      const char* e = getenv("RAGRAPH_FILTER_I8_QW");
-      const int qw_env = e ? atoi(e) : 0;
-      const int64_t pad64 = cdiv(B, (int64_t)512) * 512 - B;
-      auto fits = [&](int64_t tile) {  // a long stream per workgroup, and at most 2 % more padding queries than tiles of 512
-        return cdiv(B, tile) * p.nstages_total >= 32 * (int64_t)filter_device_cus() && (cdiv(B, tile) * tile - B - pad64) * 50 <= B;
-      };
-      // (D = 64: eight groups are 32 registers of operands -- no spill -- and 65 536 x 4M x 64 runs 15.5 ms against 16.3 with
-      // six and 17.0 with four)
-      const int qw = qw_env ? qw_env : (D == 64 && fits(1024) ? 128 : (fits(768) ? 96 : 64));
-      const bool long128 = qw == 128 && cdiv(B, (int64_t)1024) * p.nstages_total >= 32 * (int64_t)filter_device_cus();
-      const bool long96 = qw == 96 && cdiv(B, (int64_t)768) * p.nstages_total >= 32 * (int64_t)filter_device_cus();
-      if constexpr (D == 256) {
-        // four groups per wave: the epilogue of a sub-tile inside the next one's MFMAs (PIPE: 222 VGPRs) -- 512 x 1M 0.213 ->
-        // 0.2005 ms, 1024 0.324 -> 0.308, 4096 1.053 -> 1.026, 16 384 3.53 -> 3.49; on the long streams that take six groups
-        // it only draws level (13.03 vs 13.03 - 13.13 ms: six groups in one set of accumulators stay).  RAGRAPH_FILTER_PIPE=0/2: A/B
-        const char* pe = getenv("RAGRAPH_FILTER_PIPE");  // (read per call)
-        const int pv = pe ? atoi(pe) : 1;
-        if ((pv == 1 && !long128 && !long96) || pv == 2)
-          return scored ? launch_ring<D, 64, false, true, true, true>(p, B, prof_slot, st)
-                        : launch_ring<D, 64, false, true, false, true>(p, B, prof_slot, st);
-      }
-      if (scored) {
-        if (long128) return launch_ring<D, 128, false, true, true>(p, B, prof_slot, st);
-        if (long96) return launch_ring<D, 96, false, true, true>(p, B, prof_slot, st);
-        return launch_ring<D, 64, false, true, true>(p, B, prof_slot, st);
-      }
-      if (long128) return launch_ring<D, 128, false, true>(p, B, prof_slot, st);
-      if (long96) return launch_ring<D, 96, false, true>(p, B, prof_slot, st);
-      return launch_ring<D, 64, false, true>(p, B, prof_slot, st);
-    }
-  }
+// Which kernel one pass over keys [key0, key1) of a bank copy runs -- a filter level, or the bound pass (bound): the direct
+// kernel up to 256 queries (topk_filter_direct.hip: the stream, not the matrix work, is what such a call costs), more the
+// ring kernel with qw = 64 queries per wave (four groups of 16), 96 or 128.
+struct PassVariant {
+  bool direct;
+  int qw;
+  bool bound, i8, scored, pipe;
+};
+static PassVariant filter_pass_variant(int D, int64_t B, int64_t key0, int64_t key1, bool bound, bool int8, bool scored, int cus,
+                                       const FilterEnv& env) {
+  PassVariant v{};
+  v.qw = 64;
+  v.bound = bound;
+  v.i8 = int8;
+  v.scored = int8 && scored;
   if (B <= 256) {
+    v.direct = true;
+    return v;
+  }
+  // (an int8 level: the ring kernel over the int8 copy, stages of twice as many keys)
+  const int64_t nstages = cdiv(key1 - key0, FILTER_STAGE_BYTES / ((int8 ? 1 : 2) * D));
+  auto long_stream = [&](int64_t tile) { return cdiv(B, tile) * nstages >= 32 * (int64_t)cus; };
+  if (!int8) {
+    // D = 64: short rows leave registers for four query groups per wave (qw = 128): half the LDS reads and ring hand-overs per
+    // MFMA (the edge flavour's D).  From 1024 queries (one full tile), and only where a workgroup keeps its 1024 queries for
+    // a long stream: on a short bank the larger tiles mean fewer, shorter segments, each paying the operand loads again --
+    // 8192 x 40000 x 64: 0.58 vs 0.46 ms
+    if (!bound && D == 64 && B >= 1024 && long_stream(1024)) v.qw = 128;
+    return v;
+  }
+  // int8 operands are 16 bytes per 64 elements: SIX query groups per wave (tile = 768 queries) fit the registers four
+  // bf16 groups take (224 VGPRs, no scratch), and an A fragment then feeds six MFMAs, a stage 3072 cycles of them
+  // between two ring hand-overs: the bench's last level 14.45 -> 13.8 ms (A/B on one box, profiles/r3_i8_ab.txt).
+  // Eight groups (tile = 1024) spill (256 VGPRs + 80 B of scratch): 14.2 ms.  Long streams only, and only where the
+  // larger tile does not add padding queries (the last tile of 4096 queries would be a third full).
+  const int64_t pad64 = cdiv(B, (int64_t)512) * 512 - B;
+  auto fits = [&](int64_t tile) {  // a long stream per workgroup, and at most 2 % more padding queries than tiles of 512
+    return long_stream(tile) && (cdiv(B, tile) * tile - B - pad64) * 50 <= B;
+  };
+  // (D = 64: eight groups are 32 registers of operands -- no spill -- and 65 536 x 4M x 64 runs 15.5 ms against 16.3 with
+  // six and 17.0 with four)
+  const int qw = env.i8_qw ? env.i8_qw : (D == 64 && fits(1024) ? 128 : (fits(768) ? 96 : 64));
+  const bool long128 = qw == 128 && long_stream(1024), long96 = qw == 96 && long_stream(768);
+  // D = 256, four groups per wave: the epilogue of a sub-tile inside the next one's MFMAs (PIPE: 222 VGPRs) -- 512 x 1M 0.213 ->
+  // 0.2005 ms, 1024 0.324 -> 0.308, 4096 1.053 -> 1.026, 16 384 3.53 -> 3.49; on the long streams that take six groups
+  // it only draws level (13.03 vs 13.03 - 13.13 ms: six groups in one set of accumulators stay).  RAGRAPH_FILTER_PIPE=0/2: A/B
+  if (D == 256 && ((env.pipe == 1 && !long128 && !long96) || env.pipe == 2)) v.pipe = true;
+  else v.qw = long128 ? 128 : (long96 ? 96 : 64);
+  return v;
+}
+
+// The ring kernel's instantiations: the bound pass and the bf16 levels at 64 queries per wave (D = 64: also 128), the int8
+// levels at 64 / 96 / 128 with plain or scored lists, and at D = 256 the pipelined form of 64.
+template <int D>
+static int launch_ring_variant(const PassVariant& v, const FilterParams& p, int64_t B, int cus, int prof_slot, hipStream_t st) {
+  RG_REQUIRE(!v.direct && (v.qw == 64 || (v.i8 ? !v.pipe && (v.qw == 96 || v.qw == 128) : D == 64 && !v.bound && v.qw == 128)) &&
+             (!v.pipe || (D == 256 && v.i8)), RAGRAPH_EINVAL, "topk_cosine_filtered: no ring kernel for D=%d qw=%d bound=%d int8=%d pipe=%d",
+             D, v.qw, (int)v.bound, (int)v.i8, (int)v.pipe);
+  if (v.bound) return launch_ring<D, 64, true>(p, B, cus, prof_slot, st);
+  if (!v.i8) {
+    if constexpr (D == 64)
+      if (v.qw == 128) return launch_ring<D, 128, false>(p, B, cus, prof_slot, st);
+    return launch_ring<D, 64, false>(p, B, cus, prof_slot, st);
+  }
+  if constexpr (D == 256)
+    if (v.pipe)
+      return v.scored ? launch_ring<D, 64, false, true, true, true>(p, B, cus, prof_slot, st)
+                      : launch_ring<D, 64, false, true, false, true>(p, B, cus, prof_slot, st);
+#define RG_RING_I8(QW_) \
+  return v.scored ? launch_ring<D, QW_, false, true, true>(p, B, cus, prof_slot, st) : launch_ring<D, QW_, false, true>(p, B, cus, prof_slot, st)
+  if (v.qw == 128) RG_RING_I8(128);
+  if (v.qw == 96) RG_RING_I8(96);
+  RG_RING_I8(64);
+#undef RG_RING_I8
+}
+
+// One pass over keys [key0, key1) of the bf16 copy or (int8) of the int8 copy: a filter level (bound_groups = 0: candidates of
+// every query whose threshold `thr` describes) or the bound pass (bound_groups part maxima into gmax).
+template <int D>
+static int run_pass(const FilterWs& f, const uint16_t* Kb, const signed char* Kb8, int64_t B, int64_t key0, int64_t key1,
+                    const FilterThr& thr, int cap, int bound_groups, bool int8, bool scored, const FilterEnv& env, int cus,
+                    int prof_slot, hipStream_t st) {
+  const PassVariant v = filter_pass_variant(D, B, key0, key1, bound_groups > 0, int8, scored, cus, env);
+  const uint16_t* keys = v.i8 ? reinterpret_cast<const uint16_t*>(Kb8) : Kb;
+  // (the queries' operand image of the copy's type; NULL beyond FILTER_QB_MAX_B queries: converted per segment)
+  const uint16_t* Qimg = v.i8 ? reinterpret_cast<const uint16_t*>(f.Qb8) : f.Qb;
+  if (v.direct) {
     DirectArgs a{};
-    a.Qb = Kb8 ? reinterpret_cast<const uint16_t*>(f.Qb8) : f.Qb;
-    a.Kb = Kb8 ? reinterpret_cast<const uint16_t*>(Kb8) : Kb;
-    a.i8 = Kb8 ? 1 : 0;
-    a.scored = Kb8 && scored ? 1 : 0;
+    a.Qb = Qimg;
+    a.Kb = keys;
+    a.i8 = v.i8;
+    a.scored = v.scored;
     a.B = B;
     a.key0 = key0;
     a.key1 = key1;
@@ -652,404 +571,322 @@ static int run_bf16_pass(const FilterWs& f, const uint16_t* Kb, int64_t B, int64
     if (t_prof) (void)hipEventRecord(t_prof->ev[2 * prof_slot + 1], st);
     return rc;
   }
+  const int stage_keys = FILTER_STAGE_BYTES / ((v.i8 ? 1 : 2) * D);  // (bf16: key0 is a multiple of 256)
+  RG_REQUIRE(!v.i8 || key0 % stage_keys == 0, RAGRAPH_EINVAL, "topk_cosine_filtered: an int8 level must start at a whole stage "
+             "(key %lld, %d keys per stage)", (long long)key0, stage_keys);
   FilterParams p{};
   p.Qn = f.Qn;
-  p.Kb = Kb;
+  p.Kb = keys;
   p.thr = thr;
   p.count = f.count;
   p.cstride = filter_count_stride(B);
-  p.Qb = f.Qb;
+  p.Qb = Qimg;
   p.cand = f.cand;
   p.gmax = bound_groups > 0 ? f.gmax : nullptr;
   p.ngroups = bound_groups;
   p.B = B;
   p.N = key1;
-  p.cap = cap;
-  p.stage_base = key0 / C::STAGE_KEYS;  // key0 is a multiple of 256
-  p.nstages_total = cdiv(key1 - key0, C::STAGE_KEYS);
-  if (bound_groups > 0) return launch_ring<D, 64, true>(p, B, prof_slot, st);
-  if constexpr (D == 64) {  // short rows leave registers for four query groups per wave: half the LDS reads and ring
-                            // hand-overs per MFMA (the edge flavour's D)
-    // (only where a workgroup keeps its 1024 queries for a long stream: on a short bank the larger tiles mean fewer,
-    // shorter segments, each paying the operand loads again -- 8192 x 40000 x 64: 0.58 vs 0.46 ms)
-    if (filter_wide_waves(B) && cdiv(B, (int64_t)1024) * p.nstages_total >= 32 * (int64_t)filter_device_cus())
-      return launch_ring<D, 128, false>(p, B, prof_slot, st);
-  }
-  return launch_ring<D, 64, false>(p, B, prof_slot, st);
+  p.cap = cap;  // (scored lists: {key, I} pairs, the same number of slots -- filter_ws_carve gives them 8 bytes each)
+  p.stage_base = key0 / stage_keys;
+  p.nstages_total = cdiv(key1 - key0, stage_keys);
+  p.partner_lead = env.partner_lead;
+  return launch_ring_variant<D>(v, p, B, cus, prof_slot, st);
 }
 
-// Exact rescoring of a level's candidates (+ merge with the running result when `merge`) and canonical selection.
+// Which kernel rescores a level's candidates.
+enum RescoreKind {
+  RESCORE_SCORED_SMALL,  // scored lists (filter_scored_lists: a large call's int8 level), from 8192 queries
+  RESCORE_SCORED,
+  RESCORE_WIDE_SLICED,   // a handful of queries: S workgroups per query, each with its sub-list
+  RESCORE_WIDE_COOP,     // up to 256 queries: one workgroup per CU, its 70 KB of tiles cost no occupancy
+  RESCORE_WIDE,          // too few queries to fill the chip with one wave each
+  RESCORE_COOP_FEW,      // one wave per query, rows staged through LDS: 16-row tiles (the later levels over a sharded bank)
+  RESCORE_COOP
+};
+static RescoreKind rescore_kind(int64_t B, int k, bool scored, bool few) {
+  if (scored) return B >= 8192 ? RESCORE_SCORED_SMALL : RESCORE_SCORED;
+  // the wide kernels up to 2048 queries -- measured: 512 queries 0.39 (wide) vs 0.44 ms, 1024-2048 equal, 4095: 1.98 vs 1.89
+  if (B < 2048) return rescore_slices(B, k) > 1 ? RESCORE_WIDE_SLICED : (B <= 256 ? RESCORE_WIDE_COOP : RESCORE_WIDE);
+  return few ? RESCORE_COOP_FEW : RESCORE_COOP;
+}
+
+// Exact rescoring of a level's candidates (+ merge with the running result when `merge`) and canonical selection.  Every
+// kind lists the queries whose list overflowed for topk_overflow_fixup_kernel (scan_n = 0: the one-wave-per-query kernels'
+// own wave scanning a million keys took 94 ms).
 template <int D>
 static int run_rescore(const FilterWs& f, const float* Kn, int64_t N, int64_t B, int cap, int k, int64_t idx_base, int merge,
-                       int final_level, float* out_scores, int64_t* out_idx, int* overflow, int* fallback_done, bool few,
-                       hipStream_t st, const FilterThr* scored_thr = nullptr, int* cstat = nullptr) {
+                       int final_level, float* out_scores, int64_t* out_idx, int* overflow, RescoreKind kind, const FilterThr& thr,
+                       int* cstat, hipStream_t st) {
   const float* ps = merge ? out_scores : nullptr;
   const int64_t* pi = merge ? out_idx : nullptr;
-  static const int64_t wide_max_b = [] {  // RAGRAPH_RESCORE_WIDE_BELOW: A/B of the crossover
-    const char* e = getenv("RAGRAPH_RESCORE_WIDE_BELOW");
-    return e ? (int64_t)atoll(e) : (int64_t)2048;  // measured: 512 queries 0.39 (wide) vs 0.44 ms, 1024-2048 equal, 4095: 1.98 vs 1.89
-  }();
-  static const int64_t wide_coop_max_b = [] {  // RAGRAPH_RESCORE_WIDE_COOP_MAX: A/B
-    const char* e = getenv("RAGRAPH_RESCORE_WIDE_COOP_MAX");
-    return e ? (int64_t)atoll(e) : (int64_t)256;
-  }();
-  // a handful of queries: S workgroups per query, each with its sub-list
-  const int S = B <= 256 ? rescore_slices(B, k) : 1;
   const int cs = filter_count_stride(B);
-  // mid-sized calls: an overflowed query is scanned by its own rescoring wave (no fallback launch); large batches keep
-  // the dedicated launch, whose four-wave workgroups scan a bank faster when MANY queries overflow
-  // the one-wave-per-query kernels leave overflowed queries to topk_overflow_fixup_kernel (their own wave scanning a
-  // million keys took 94 ms; RAGRAPH_RESCORE_SCAN_IN_WAVE=1: the old behaviour, A/B)
-  static const bool scan_in_wave = [] { const char* e = getenv("RAGRAPH_RESCORE_SCAN_IN_WAVE"); return e && atoi(e) != 0; }();
-  const int64_t scan_n = scan_in_wave && B <= FILTER_SLAB_MAX_B ? N : 0;
-  if (scored_thr) {  // (filter_scored_lists: a large call's int8 level)
-    *fallback_done = scan_n > 0;
-    static const bool small_env = [] { const char* e = getenv("RAGRAPH_RESCORE_SCORED_SMALL"); return !e || atoi(e) != 0; }();  // A/B
-    if (B >= 8192 && small_env)
-      hipLaunchKernelGGL((topk_rescore_scored_kernel<D, true>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,
-                         reinterpret_cast<const int2*>(f.cand), B, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx,
-                         overflow, f.overflow_list, f.flag, scan_n, *scored_thr, cstat);
-    else
-      hipLaunchKernelGGL((topk_rescore_scored_kernel<D, false>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,
-                         reinterpret_cast<const int2*>(f.cand), B, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx,
-                         overflow, f.overflow_list, f.flag, scan_n, *scored_thr, cstat);
-  } else if (B < wide_max_b && S > 1) {
-    hipLaunchKernelGGL((topk_rescore_wide_kernel<D, true, true>), dim3((unsigned)B, (unsigned)S), dim3(256), 0, st, f.Qn, Kn, f.count,
-                       f.cand, B, N, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx, overflow, f.overflow_list,
-                       f.flag, f.part_s, f.part_i, cstat);
-    *fallback_done = 0;   // (every call lists its overflowed queries for the sliced fixup launch)
-#ifdef RG_WIDE_TIMING
-    {
-      (void)hipDeviceSynchronize();
-      unsigned long long t[16];
-      (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_wide_t), sizeof(t));
-      fprintf(stderr, "[wide timing, block 0, 10 ns ticks]");
-      for (int i = 1; i < 10; ++i) fprintf(stderr, " %d:%lld", i, (long long)(t[i] - t[0]));
-      fprintf(stderr, "\n");
-    }
-#endif
-  } else if (B <= wide_coop_max_b) {  // one workgroup per CU: its 70 KB of tiles cost no occupancy
-    *fallback_done = 0;
-    hipLaunchKernelGGL((topk_rescore_wide_kernel<D, false, true>), dim3((unsigned)B), dim3(256), 0, st, f.Qn, Kn, f.count, f.cand,
-                       B, N, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx, overflow, f.overflow_list, f.flag,
-                       (float*)nullptr, (int*)nullptr, cstat);
-  } else if (B < wide_max_b) {  // too few queries to fill the chip with one wave each
-    *fallback_done = 0;
-    hipLaunchKernelGGL((topk_rescore_wide_kernel<D, false, false>), dim3((unsigned)B), dim3(256), 0, st, f.Qn, Kn, f.count, f.cand,
-                       B, N, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx, overflow, f.overflow_list, f.flag,
-                       (float*)nullptr, (int*)nullptr, cstat);
-  } else if (rescore_coop() && few) {
-    *fallback_done = scan_n > 0;
-    hipLaunchKernelGGL((topk_rescore_coop_kernel<D, 32, true>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,
-                       f.cand, B, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx, overflow, f.overflow_list, f.flag,
-                       scan_n, cstat);
-  } else if (rescore_coop()) {
-    *fallback_done = scan_n > 0;
-    hipLaunchKernelGGL((topk_rescore_coop_kernel<D, 32>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,
-                       f.cand, B, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx, overflow, f.overflow_list, f.flag,
-                       scan_n, cstat);
-  } else
-    hipLaunchKernelGGL((topk_rescore_kernel<D, 32>), dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, f.Qn, Kn, f.count, f.cand,
-                       B, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx, overflow, f.overflow_list, f.flag, cstat);
+  const int64_t scan_n = 0;
+#define RG_SCORED(SMALL_)                                                                                                        \
+  hipLaunchKernelGGL((topk_rescore_scored_kernel<D, SMALL_>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,    \
+                     reinterpret_cast<const int2*>(f.cand), B, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx,   \
+                     overflow, f.overflow_list, f.flag, scan_n, thr, cstat)
+#define RG_WIDE(SLICED_, COOP_, GRID_, PART_S_, PART_I_)                                                                         \
+  hipLaunchKernelGGL((topk_rescore_wide_kernel<D, SLICED_, COOP_>), GRID_, dim3(256), 0, st, f.Qn, Kn, f.count, f.cand, B, N,    \
+                     cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx, overflow, f.overflow_list, f.flag, PART_S_, \
+                     PART_I_, cstat)
+#define RG_COOP(FEW_)                                                                                                            \
+  hipLaunchKernelGGL((topk_rescore_coop_kernel<D, 32, FEW_>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,    \
+                     f.cand, B, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx, overflow, f.overflow_list,       \
+                     f.flag, scan_n, cstat)
+  switch (kind) {
+    case RESCORE_SCORED_SMALL: RG_SCORED(true); break;
+    case RESCORE_SCORED: RG_SCORED(false); break;
+    case RESCORE_WIDE_SLICED:
+      RG_WIDE(true, true, dim3((unsigned)B, (unsigned)rescore_slices(B, k)), f.part_s, f.part_i);
+      wide_timing_report();
+      break;
+    case RESCORE_WIDE_COOP: RG_WIDE(false, true, dim3((unsigned)B), (float*)nullptr, (int*)nullptr); break;
+    case RESCORE_WIDE: RG_WIDE(false, false, dim3((unsigned)B), (float*)nullptr, (int*)nullptr); break;
+    case RESCORE_COOP_FEW: RG_COOP(true); break;
+    case RESCORE_COOP: RG_COOP(false); break;
+  }
+#undef RG_SCORED
+#undef RG_WIDE
+#undef RG_COOP
   RG_CHECK_LAUNCH("topk_cosine_filtered(rescore)");
   return RAGRAPH_OK;
 }
 
+// The arguments of ragraph_topk_cosine_filtered_sharded_f32 (the single bank: plan_N = N, no exchange, one shard).
+struct FilteredArgs {
+  const float* Q;
+  int64_t B;
+  const float *Kn, *Kp;
+  const uint16_t* Kb;
+  int64_t N;
+  int D, k;
+  int64_t idx_base;
+  float* out_scores;
+  int64_t* out_idx;
+  int* overflow;
+  int64_t* overflow_idx;
+  void* ws;
+  size_t ws_bytes;
+  void* stream;
+  int64_t plan_N;  // (from here on: the sharded entry's)
+  float* theta;
+  ragraph_exchange_fn exchange;
+  void* ctx;
+  int n_shards;
+};
+
+// theta = (first: =, else max with) the k-th exact score of the running result thr.prev_scores
+static int launch_theta(FilterThr thr, int64_t B, int first, float* theta, hipStream_t st) {
+  thr.gmax = nullptr;
+  thr.theta = nullptr;
+  hipLaunchKernelGGL(filter_theta_kernel, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, thr, B, first, theta);
+  RG_CHECK_LAUNCH("topk_cosine_filtered(theta)");
+  return RAGRAPH_OK;
+}
+
+// A shard too short for the plan's phases (FilterCall::exact_participant): its fp32 top-k once, offered at every exchange.
+static int run_exact_participant(const FilteredArgs& a, const FilterCall& c) {
+  hipStream_t st = as_stream(a.stream);
+  RG_REQUIRE(a.ws_bytes >= ragraph_topk_cosine_workspace_bytes(a.B, a.N, a.D, a.k), RAGRAPH_EWORKSPACE,
+             "topk_cosine_filtered: workspace too small for a short shard's exact top-k");
+  int rc = ragraph_topk_cosine_bank_f32(a.Q, a.B, a.Kn, a.D == 256 ? a.Kp : nullptr, a.N, a.D, a.k, a.idx_base, a.out_scores,
+                                        a.out_idx, a.ws, a.ws_bytes, a.stream);
+  if (rc != RAGRAPH_OK) return rc;
+  if (hipMemsetAsync(a.overflow, 0, sizeof(int), st) != hipSuccess) {
+    set_error("topk_cosine_filtered: memset failed");
+    return RAGRAPH_EDEVICE;
+  }
+  FilterThr t0{};
+  t0.prev_scores = a.out_scores;
+  t0.k = a.k;
+  for (int ph = c.first_phase; ph < c.nlev; ++ph) {   // phase 0 (not under a speculative bound) + one exchange behind every level but the last
+    if ((rc = launch_theta(t0, a.B, ph == c.first_phase, a.theta, st)) != RAGRAPH_OK) return rc;
+    a.exchange(a.ctx, ph);
+  }
+  return RAGRAPH_OK;
+}
+
+// Steps 3 - 7 of a call (1, 2: filtered_entry): executes the plan `c` that filter_call_plan made of the shape `in` -- carve,
+// prepare, first bound, the levels, verify / fixup -- and decides nothing itself.
 template <int D>
-static int run_filtered(const float* Q, int64_t B, const float* Kn, const float* Kp, const uint16_t* Kb, int64_t N, int k,
-                        int64_t idx_base, float* out_scores, int64_t* out_idx, int* overflow, int64_t* overflow_idx,
-                        void* ws, size_t ws_bytes, void* stream, int64_t plan_N, float* theta, ragraph_exchange_fn exchange,
-                        void* ctx, int n_shards) {
-  hipStream_t st = as_stream(stream);
-  const int cap = filter_cap(B, k);
-  FilterSchedule sc = filter_schedule(B, plan_N, D, k, exchange ? n_shards : 1);  // (sharded banks: the same schedule on every shard)
-  // A speculative first bound (this thread's prior).  Sharded banks: whether the call speculates must be the SAME decision on
-  // every rank -- it removes the bound pass AND its exchange (phase 0) --, so it is taken from what every rank shares: the
-  // prior (the caller derives it from pooled statistics and sets it on every rank alike) and the PLAN's bound pass (plan_N),
-  // before any adjustment to this shard's own length.  The proof is the caller's too: a query is exact iff the k-th best of
-  // the MERGED lists reaches the prior (ragraph_amd/sharded.py verifies at the rows' owner and re-runs without the prior).
-  const float prior = t_prior;
-  const bool prior_ok = prior == prior && prior > -2.f && prior < 2.f;
-  const bool spec_x = exchange && prior_ok && sc.bound_keys > 0;
-  if (spec_x && sc.nlev == 2 && B <= 4096) {  // (as below for one bank: the prior IS the bound a first level would give)
-    sc.nlev = 1;
-    sc.ends[0] = plan_N;
-    if (sc.i8_levels > 1) sc.i8_levels = 1;
-  }
-  // Three levels under the prior, many shards: the first level (1 / 32 of the shard) exists to sharpen the bound pass's
-  // bound, and under the group's prior it passes about ONE candidate per query and shard (measured, 8 shards of the 1M bank) --
-  // a filter launch on the bf16 copy, a rescoring launch over every query and an exchange for nothing.  From
-  // RAGRAPH_FILTER_SPEC_SHARDS_TWO_LEVELS shards (default 2: every sharded bank; 0 = never) the call runs levels [0, N / 4) and
-  // [N / 4, N): emulated rank of 2 / 4 / 8, ms per step: 11.14 -> 10.83, 6.29 -> 5.92, 3.73 -> 3.46 (profiles/r6_multi_one_gpu.txt).
-  static const int spec_two = [] { const char* e = getenv("RAGRAPH_FILTER_SPEC_SHARDS_TWO_LEVELS"); return e ? atoi(e) : 2; }();
-  if (spec_x && sc.nlev == 3 && spec_two > 0 && n_shards >= spec_two) {
-    sc.ends[0] = sc.ends[1];
-    sc.ends[1] = sc.ends[2];
-    sc.nlev = 2;
-    if (sc.i8_levels > 2) sc.i8_levels = 2;
-  }
-  // A shard SHORTER than the largest one (shards of a bank whose exact duplicates were collapsed per shard hold different
-  // numbers of unique rows): the same phases -- the exchanges must line up across the ranks -- over proportionally fewer
-  // keys; a shard too short for that structure takes part as an EXACT participant: its fp32 top-k once, offered at every
-  // exchange (exact scores of k distinct keys are valid lower bounds at every phase).
-  bool exact_participant = false;
-  if (exchange && plan_N - N > 1024) {
-    int64_t prev = 0;
-    for (int l = 0; l + 1 < sc.nlev; ++l) {
-      int64_t e = (int64_t)((double)sc.ends[l] * (double)N / (double)plan_N) / 512 * 512;   // (512: whole int8 stages at any width)
-      if (e < prev + 512 || e + 512 > N) exact_participant = true;
-      sc.ends[l] = e;
-      prev = e;
-    }
-    sc.bound_keys = (int64_t)((double)sc.bound_keys * (double)N / (double)plan_N) / FILTER_PAD_KEYS * FILTER_PAD_KEYS;
-    if (sc.nlev > 1 && sc.bound_keys > sc.ends[0]) sc.bound_keys = sc.ends[0];
-    if (sc.bound_keys / (FILTER_STAGE_BYTES / (2 * D)) < (int64_t)filter_bound_parts(k, sc.bound_keys, D, B, n_shards)) sc.bound_keys = 0;
-    sc.n0 = sc.n0 < N ? sc.n0 : N;
-    if (N < 16384 || N * 8 < plan_N) exact_participant = true;
-  }
-  if (exact_participant) {
-    RG_REQUIRE(ws_bytes >= ragraph_topk_cosine_workspace_bytes(B, N, D, k), RAGRAPH_EWORKSPACE,
-               "topk_cosine_filtered: workspace too small for a short shard's exact top-k");
-    int rc0 = ragraph_topk_cosine_bank_f32(Q, B, Kn, D == 256 ? Kp : nullptr, N, D, k, idx_base, out_scores, out_idx, ws, ws_bytes, stream);
-    if (rc0 != RAGRAPH_OK) return rc0;
-    if (hipMemsetAsync(overflow, 0, sizeof(int), st) != hipSuccess) {
-      set_error("topk_cosine_filtered: memset failed");
-      return RAGRAPH_EDEVICE;
-    }
-    FilterThr t0{};
-    t0.prev_scores = out_scores;
-    t0.k = k;
-    for (int ph = spec_x ? 1 : 0; ph < sc.nlev; ++ph) {   // phase 0 (not under a speculative bound) + one exchange behind every level but the last
-      hipLaunchKernelGGL(filter_theta_kernel, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, t0, B, ph == (spec_x ? 1 : 0) ? 1 : 0, theta);
-      RG_CHECK_LAUNCH("topk_cosine_filtered(theta)");
-      exchange(ctx, ph);
-    }
-    return RAGRAPH_OK;
-  }
-  sc.ends[sc.nlev - 1] = N;
-  if (sc.bound_keys > N / 2) sc.bound_keys = 0, sc.n0 = sc.n0 < N ? sc.n0 : N;
-  if (exchange && n_shards > 1 && sc.bound_keys > 0 && B <= FILTER_SLAB_MAX_B && plan_N >= 4 * 4096) {  // (the cost-model branch)
-    // G shards pool their samples through the exchange (the k-th largest of the union of every shard's best group
-    // maxima): each scans 1/G of the prefix one bank would -- at least one stage per part
-    const int64_t min_keys = filter_round_up((int64_t)k * (FILTER_STAGE_BYTES / (2 * D)));
-    int64_t bk = filter_round_up(sc.bound_keys / n_shards);
-    sc.bound_keys = bk < min_keys ? (min_keys < sc.bound_keys ? min_keys : sc.bound_keys) : bk;
-  }
+static int run_filtered(const FilteredArgs& a, const FilterCall& c, const FilterShape& in) {
+  hipStream_t st = as_stream(a.stream);
+  const int64_t B = a.B, N = a.N;
+  const int k = a.k;
+  float* const out_scores = a.out_scores;
+  int64_t* const out_idx = a.out_idx;
+  const bool sharded = a.exchange != nullptr, bound = c.level0 == FILTER_L0_BOUND;
   static const int ablate = [] {  // RAGRAPH_FILTER_ABLATE=1: no key passes the filter (timing only, results invalid)
     const char* e = getenv("RAGRAPH_FILTER_ABLATE");
     return e ? atoi(e) : 0;
   }();
   if (t_prof) t_prof->have = t_prof->bound = 0;
 
-  char* w = static_cast<char*>(ws);
-  const size_t sample_ws = filter_level0_ws(sc, B, D, k);
+  // 3. carve: level 0's scratch, the call's buffers, the statistics words
+  char* w = static_cast<char*>(a.ws);
   FilterWs f;
-  const size_t used = sample_ws + filter_ws_carve(w + sample_ws, B, D, k, cap, &f) + FILTER_STATS_BYTES;
-  RG_REQUIRE(used <= ws_bytes, RAGRAPH_EWORKSPACE, "topk_cosine_filtered: the schedule of this call needs %zu bytes of workspace, "
-             "%zu given", used, ws_bytes);
+  const size_t used = c.level0_bytes + filter_ws_carve(w + c.level0_bytes, in, c, &f) + FILTER_STATS_BYTES;
+  RG_REQUIRE(used <= a.ws_bytes, RAGRAPH_EWORKSPACE, "topk_cosine_filtered: the schedule of this call needs %zu bytes of workspace, "
+             "%zu given", used, a.ws_bytes);
   // the call's candidate statistics: the last FILTER_STATS_INTS ints of the workspace AS PASSED (ragraph_topk_cosine_filtered_stats_offset)
-  int* stats = reinterpret_cast<int*>(w + ragraph_topk_cosine_filtered_stats_offset(ws_bytes));
-  const unsigned* max_kerr2 = reinterpret_cast<const unsigned*>(Kb + filter_round_up(N) * D);
+  int* stats = reinterpret_cast<int*>(w + ragraph_topk_cosine_filtered_stats_offset(a.ws_bytes));
+  const unsigned* max_kerr2 = reinterpret_cast<const unsigned*>(a.Kb + filter_round_up(N) * D);
   // the int8 copy lies behind the bf16 copy and its tail row (ragraph_keys_to_bf16)
-  const FilterI8View v8 = filter_i8_view(Kb, N, D);
-  const signed char* Kb8 = v8.K8;
-  const unsigned* tail8 = v8.tail8;
-  sc.i8_levels = filter_i8_levels(sc, B, D, plan_N);
-  // a speculative first bound (this thread's prior; single banks whose schedule has a bound pass to save): no bound pass,
-  // theta = prior for every query, every level filters with max(prior, the running k-th best), and the verify launch
-  // behind the last level sends the queries the prior was too high for to the exact scan
-  const bool spec = exchange ? spec_x : (sc.bound_keys > 0 && prior_ok && N == plan_N);
-  const bool bound = sc.bound_keys > 0 && !spec;
-  // A first level exists to give the second a tighter bound than the bound pass could; the prior already is one.  Measured
-  // with it (1M x 256, ms per call, two levels / one): 2048 queries 0.544 / 0.512, 4096: 0.920 / 0.898 -- but 16 384: 3.18 /
-  // 3.85, and the three levels of 100 000 queries stay (20.5 ms per step against 22.8 with two): up to 4096 queries one level.
-  if (spec && !exchange && sc.nlev == 2 && B <= 4096) {
-    sc.nlev = 1;
-    sc.ends[0] = N;
-    if (sc.i8_levels > 1) sc.i8_levels = 1;
-  }
+  const FilterI8View v8 = filter_i8_view(a.Kb, N, D);
 
+  // 4. prepare -- one launch: normalised queries, their bf16 rounding errors, empty lists, clear flags (+ group maxima at -inf;
+  // under a speculative bound theta = the prior)
   FilterStatsInit stats_init{};
-  stats_init.nlev = sc.nlev;
-  for (int l = 0; l < sc.nlev && l < 3; ++l) {
-    stats_init.i8[l] = l >= sc.nlev - sc.i8_levels;
-    const int64_t lk = sc.ends[l] - (l ? sc.ends[l - 1] : 0);
+  stats_init.nlev = c.nlev;
+  for (int l = 0; l < c.nlev; ++l) {
+    stats_init.i8[l] = c.level[l].int8;
+    const int64_t lk = c.level[l].key1 - c.level[l].key0;
     stats_init.keys[l] = lk > INT_MAX ? INT_MAX : (int)lk;
   }
-  // one launch: normalised queries, their bf16 rounding errors, empty lists, clear flags (+ group maxima at -inf)
-  static const int64_t prep_wide_b = [] { const char* e = getenv("RAGRAPH_FILTER_PREP_WIDE_B"); return e ? (int64_t)atoll(e) : (int64_t)8192; }();   // A/B
 #define RG_PREP(R_)                                                                                                                     \
-  hipLaunchKernelGGL((filter_prep_kernel<D, R_>), dim3((unsigned)cdiv(B <= FILTER_QB_MAX_B ? (B + 31) / 32 * 32 : B, 4 * (R_))), dim3(256), 0, st, Q, B, \
-                     f.Qn, f.eq, f.count, f.flag, overflow, bound ? f.gmax : nullptr, bound ? filter_bound_parts(k, sc.bound_keys, D, B, exchange ? n_shards : 1) : k, \
-                     /* (the bf16 operand image: only launches on the bf16 copy read it -- a call whose levels all run on the int8 */ \
-                     /* copy and that has no bound pass, e.g. every call under a prior, saves writing 2 D bytes per query) */           \
-                     B <= FILTER_QB_MAX_B && (B <= 256 || bound || sc.nlev > sc.i8_levels) ? f.Qb : nullptr,                           \
-                     filter_count_stride(B), sc.i8_levels > 0 ? f.eq8 : nullptr, f.qscale, B <= FILTER_QB_MAX_B ? f.Qb8 : nullptr, f.fix_done, \
-                     stats, stats_init, spec ? (exchange ? theta : f.theta) : nullptr, prior)
-  if (B >= prep_wide_b) RG_PREP(4);   // (100 000 x 256: 120 us with one row per wave, 74 with two or four, 162 with eight)
+  hipLaunchKernelGGL((filter_prep_kernel<D, R_>), dim3((unsigned)cdiv(B <= FILTER_QB_MAX_B ? (B + 31) / 32 * 32 : B, 4 * (R_))), dim3(256), 0, st, a.Q, B, \
+                     f.Qn, f.eq, f.count, f.flag, a.overflow, bound ? f.gmax : nullptr, c.parts, c.bf16_image ? f.Qb : nullptr,         \
+                     filter_count_stride(B), c.i8_levels > 0 ? f.eq8 : nullptr, f.qscale, B <= FILTER_QB_MAX_B ? f.Qb8 : nullptr, f.fix_done, \
+                     stats, stats_init, c.spec ? (sharded ? a.theta : f.theta) : nullptr, in.prior)
+  if (B >= 8192) RG_PREP(4);   // (100 000 x 256: 120 us with one row per wave, 74 with two or four, 162 with eight)
   else RG_PREP(1);
 #undef RG_PREP
   RG_CHECK_LAUNCH("topk_cosine_filtered(prepare)");
 
-  FilterThr thr{};
+  FilterThr thr{};   // (theta, prev_scores, gmax: per launch)
   thr.eq = f.eq;
   thr.max_kerr2 = max_kerr2;
   thr.eq8 = f.eq8;
   thr.qscale = f.qscale;
-  thr.tail8 = tail8;
+  thr.tail8 = v8.tail8;
   thr.cls8 = v8.cls;
   thr.flag = f.flag;
   thr.k = k;
-  const int parts = bound ? filter_bound_parts(k, sc.bound_keys, D, B, exchange ? n_shards : 1) : k;
-  thr.ngroups = parts;
+  thr.ngroups = c.parts;
   thr.ablate = ablate;
-  int rc = RAGRAPH_OK, fallback_done = 0;
-  // the first bound: group maxima of a bf16 pass over a prefix, or an exact level 0 over the first n0 keys (out_scores /
+  // 5. the first bound: group maxima of a bf16 pass over a prefix, or an exact level 0 over the first n0 keys (out_scores /
   // out_idx hold every level's running result, local indices)
-  if (spec) {
-    // (nothing to compute: the prepare launch has written theta)
-  } else if (bound) {
-    rc = run_bf16_pass<D>(f, Kb, B, 0, sc.bound_keys, thr, cap, parts, 3, st);
-    if (t_prof) {
-      t_prof->bound = 1;
-      t_prof->i8[3] = 0;
-      t_prof->keys[3] = sc.bound_keys;
+  int rc = RAGRAPH_OK;
+  switch (c.level0) {
+    case FILTER_L0_NONE: break;  // (nothing to compute: the prepare launch has written theta)
+    case FILTER_L0_BOUND:
+      rc = run_pass<D>(f, a.Kb, v8.K8, B, 0, c.bound_keys, thr, c.cap, c.parts, false, false, in.env, in.cus, 3, st);
+      if (t_prof) {
+        t_prof->bound = 1;
+        t_prof->i8[3] = 0;
+        t_prof->keys[3] = c.bound_keys;
+      }
+      break;
+    case FILTER_L0_SLAB: {
+      float* S = reinterpret_cast<float*>(w);  // one slab of scores, reused: written and read back while it is in cache
+      for (int64_t b0 = 0; b0 < B && rc == RAGRAPH_OK; b0 += FILTER_SLAB_MAX_B) {
+        const int64_t nb = B - b0 < FILTER_SLAB_MAX_B ? B - b0 : FILTER_SLAB_MAX_B;
+        rc = ragraph_linear_f32(f.Qn + b0 * D, nb, D, a.Kn, c.n0, nullptr, RAGRAPH_ACT_NONE, 0.f, S, a.stream);
+        if (rc == RAGRAPH_OK)
+          rc = ragraph_topk_rows_f32(S, nb, c.n0, c.n0, k, out_scores + b0 * k, out_idx + b0 * k, a.stream);
+      }
+      break;
     }
-  } else if (sc.slab0) {
-    float* S = reinterpret_cast<float*>(w);  // one slab of scores, reused: written and read back while it is in cache
-    for (int64_t b0 = 0; b0 < B && rc == RAGRAPH_OK; b0 += FILTER_SLAB_MAX_B) {
-      const int64_t nb = B - b0 < FILTER_SLAB_MAX_B ? B - b0 : FILTER_SLAB_MAX_B;
-      rc = ragraph_linear_f32(f.Qn + b0 * D, nb, D, Kn, sc.n0, nullptr, RAGRAPH_ACT_NONE, 0.f, S, stream);
-      if (rc == RAGRAPH_OK)
-        rc = ragraph_topk_rows_f32(S, nb, sc.n0, sc.n0, k, out_scores + b0 * k, out_idx + b0 * k, stream);
-    }
-  } else {
-    rc = ragraph_topk_cosine_bank_f32(Q, B, Kn, D == 256 ? Kp : nullptr, sc.n0, D, k, 0, out_scores, out_idx, ws, sample_ws,
-                                      stream);
+    case FILTER_L0_TILE:
+      rc = ragraph_topk_cosine_bank_f32(a.Q, B, a.Kn, D == 256 ? a.Kp : nullptr, c.n0, D, k, 0, out_scores, out_idx, a.ws,
+                                        c.level0_bytes, a.stream);
+      break;
   }
   if (rc != RAGRAPH_OK) return rc;
-  if (exchange && spec) {  // theta = the prior on every shard (the prepare launch wrote it): nothing to pool, no phase 0
-    thr.theta = theta;
-  } else if (exchange) {  // the first bound leaves through theta / out_scores, and comes back as a bound on the k-th best of ALL shards
+  if (sharded && c.spec) {  // theta = the prior on every shard (the prepare launch wrote it): nothing to pool, no phase 0
+    thr.theta = a.theta;
+  } else if (sharded) {  // the first bound leaves through theta / out_scores, and comes back as a bound on the k-th best of ALL shards
     thr.gmax = bound ? f.gmax : nullptr;
     thr.prev_scores = out_scores;
-    if (bound)  // k lower bounds of distinct keys' exact scores, descending, where a level leaves its exact top-k
-      hipLaunchKernelGGL(filter_bound_scores_kernel, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, thr, B, out_scores, theta);
-    else
-      hipLaunchKernelGGL(filter_theta_kernel, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, thr, B, 1, theta);
-    RG_CHECK_LAUNCH("topk_cosine_filtered(theta)");
-    exchange(ctx, 0);
-    thr.theta = theta;
-  } else if (bound && parts > k) {  // theta = the k-th largest of the part maxima, minus eps
+    if (bound) {  // k lower bounds of distinct keys' exact scores, descending, where a level leaves its exact top-k
+      hipLaunchKernelGGL(filter_bound_scores_kernel, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, thr, B, out_scores, a.theta);
+      RG_CHECK_LAUNCH("topk_cosine_filtered(theta)");
+    } else if ((rc = launch_theta(thr, B, 1, a.theta, st)) != RAGRAPH_OK) {
+      return rc;
+    }
+    a.exchange(a.ctx, 0);
+    thr.theta = a.theta;
+  } else if (bound && c.parts > k) {  // theta = the k-th largest of the part maxima, minus eps
     thr.gmax = f.gmax;
     hipLaunchKernelGGL(filter_bound_scores_kernel, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, thr, B, (float*)nullptr, f.theta);
     RG_CHECK_LAUNCH("topk_cosine_filtered(theta)");
   }
-  int64_t key0 = 0;
-  for (int l = 0; l < sc.nlev; ++l) {  // the first level re-reads [0, n0): its keys pass the bound and need no merge
-    thr.gmax = (l == 0 && bound && !exchange && parts == k) ? f.gmax : nullptr;  // (k parts: the minimum, inline)
-    if (!exchange) thr.theta = (spec || (l == 0 && bound && parts > k)) ? f.theta : nullptr;
+
+  // 6. the levels: filter, rescore (+ merge with the running result), sharpen the bound for the next one
+  for (int l = 0; l < c.nlev; ++l) {
+    const FilterLevel& lv = c.level[l];
+    thr.gmax = (l == 0 && bound && !sharded && c.parts == k) ? f.gmax : nullptr;  // (k parts: the minimum, inline)
+    if (!sharded) thr.theta = (c.spec || (l == 0 && bound && c.parts > k)) ? f.theta : nullptr;
     thr.prev_scores = out_scores;
-    const bool i8_level = l >= sc.nlev - sc.i8_levels;
-    // (sharded banks keep the plain lists: a level's threshold already is the k-th best over ALL shards -- sharper than
-    // anything round 1 can find among this shard's keys, so nothing is pruned and only the second round's latency and the
-    // 16-row tiles' occupancy are lost: emulated rank of 2 / 4 / 8 GPUs 13.49 -> 13.26 / 7.61 -> 8.00 / 4.76 -> 5.24 ms per
-    // step, profiles/r3_emul.txt.  RAGRAPH_FILTER_SCORED_SHARDS = largest shard count that takes them: A/B.)
-    const bool scored = i8_level && (!exchange || n_shards <= filter_scored_shards()) && filter_scored_lists(B, D, k);
-    rc = run_bf16_pass<D>(f, Kb, B, key0, sc.ends[l], thr, cap, 0, l, st, i8_level ? Kb8 : nullptr, scored);
+    rc = run_pass<D>(f, a.Kb, v8.K8, B, lv.key0, lv.key1, thr, c.cap, 0, lv.int8, lv.scored, in.env, in.cus, l, st);
     if (t_prof) {
-      t_prof->i8[l] = l >= sc.nlev - sc.i8_levels;
-      t_prof->keys[l] = sc.ends[l] - key0;
+      t_prof->i8[l] = lv.int8;
+      t_prof->keys[l] = lv.key1 - lv.key0;
     }
     if (rc != RAGRAPH_OK) return rc;
-    static const bool dbg_counts = [] { const char* e = getenv("RAGRAPH_FILTER_DEBUG_COUNTS"); return e && atoi(e) != 0; }();
-    if (dbg_counts) {  // diagnostic (synchronises): the level's candidate counts per query, before the rescoring resets them
-      const int cs_ = filter_count_stride(B);
-      std::vector<int> h((size_t)B * cs_);
-      (void)hipStreamSynchronize(st);
-      (void)hipMemcpy(h.data(), f.count, h.size() * sizeof(int), hipMemcpyDeviceToHost);
-      const int nsub_ = B <= 256 ? rescore_slices(B, k) : 1;
-      long long tot = 0, mx = 0, over_half = 0, over_cap = 0;
-      for (int64_t b = 0; b < B; ++b) {
-        long long c = 0;
-        for (int u = 0; u < nsub_; ++u) c += h[(size_t)b * cs_ + u];
-        tot += c;
-        mx = c > mx ? c : mx;
-        over_half += c > cap / 2;
-        over_cap += c > cap;
-      }
-      fprintf(stderr, "[filter counts] level %d (%s%s, keys %lld..%lld): mean %.1f max %lld per query; %lld of %lld queries above %d, %lld above %d\n",
-              l, i8_level ? "int8" : "bf16", scored ? ", scored" : "", (long long)key0, (long long)sc.ends[l], (double)tot / (double)B, mx,
-              over_half, (long long)B, cap / 2, over_cap, cap);
-    }
     if (t_prof) t_prof->have = l + 1;
-    rc = run_rescore<D>(f, Kn, N, B, cap, k, idx_base, l > 0, l == sc.nlev - 1, out_scores, out_idx, overflow,
-                        &fallback_done, exchange != nullptr && l > 0, st, scored ? &thr : nullptr, l < 3 ? stats + 2 + l : nullptr);
+    rc = run_rescore<D>(f, a.Kn, N, B, c.cap, k, a.idx_base, l > 0, l == c.nlev - 1, out_scores, out_idx, a.overflow,
+                        rescore_kind(B, k, lv.scored, sharded && l > 0), thr, stats + 2 + l, st);
     if (rc != RAGRAPH_OK) return rc;
-    key0 = sc.ends[l];
-    if (spec && !exchange && l + 1 < sc.nlev) {  // the next level filters with max(prior, the exact k-th best so far)
-      FilterThr t2 = thr;
-      t2.gmax = nullptr;
-      t2.theta = nullptr;
-      hipLaunchKernelGGL(filter_theta_kernel, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, t2, B, 0, f.theta);
-      RG_CHECK_LAUNCH("topk_cosine_filtered(theta)");
-    }
-    if (exchange && l + 1 < sc.nlev) {  // this shard's k-th exact score so far sharpens theta; then the other shards'
-      FilterThr t2 = thr;
-      t2.gmax = nullptr;
-      t2.theta = nullptr;
-      hipLaunchKernelGGL(filter_theta_kernel, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, t2, B, 0, theta);
-      RG_CHECK_LAUNCH("topk_cosine_filtered(theta)");
-      exchange(ctx, 1 + l);
+    if (l + 1 == c.nlev) break;
+    if (sharded) {  // this shard's k-th exact score so far sharpens theta; then the other shards'
+      if ((rc = launch_theta(thr, B, 0, a.theta, st)) != RAGRAPH_OK) return rc;
+      a.exchange(a.ctx, 1 + l);
+    } else if (c.spec) {  // the next level filters with max(prior, the exact k-th best so far)
+      if ((rc = launch_theta(thr, B, 0, f.theta, st)) != RAGRAPH_OK) return rc;
     }
   }
-  // overflowed queries (none on ordinary banks): exact fp32 scan on the device -- no host read-back (the sliced
-  // rescoring of a handful of queries has done it inside its merge launch)
-  if (spec && !exchange) {   // (a shard's lists prove nothing alone: the owner of a row verifies the MERGED k-th best)
-    hipLaunchKernelGGL(filter_verify_prior_kernel, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, out_scores, B, k, prior, 1, f.flag,
-                       overflow, f.overflow_list, stats);
+
+  // 7. verify / fixup
+  if (c.spec && !sharded) {   // (a shard's lists prove nothing alone: the owner of a row verifies the MERGED k-th best)
+    hipLaunchKernelGGL(filter_verify_prior_kernel, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, out_scores, B, k, in.prior, 1, f.flag,
+                       a.overflow, f.overflow_list, stats);
     RG_CHECK_LAUNCH("topk_cosine_filtered(verify)");
-    fallback_done = 0;
   }
-  if (fallback_done) return RAGRAPH_OK;
-  hipLaunchKernelGGL(topk_overflow_fixup_kernel<D>, dim3(256), dim3(256), 0, st, f.Qn, Kn, N, k, idx_base,
-                     overflow, f.overflow_list, overflow_idx, out_scores, out_idx, f.fix_done, f.fix_s, f.fix_i, B, f.flag,
-                     exchange ? nullptr : stats);
+  // overflowed queries (none on ordinary banks) and the queries a prior was too high for: exact fp32 scan on the device --
+  // no host read-back
+  hipLaunchKernelGGL(topk_overflow_fixup_kernel<D>, dim3(256), dim3(256), 0, st, f.Qn, a.Kn, N, k, a.idx_base,
+                     a.overflow, f.overflow_list, a.overflow_idx, out_scores, out_idx, f.fix_done, f.fix_s, f.fix_i, B, f.flag,
+                     sharded ? nullptr : stats);
   RG_CHECK_LAUNCH("topk_cosine_filtered(overflow fallback)");
   return RAGRAPH_OK;
 }
 
-static int filtered_entry(const float* Q, int64_t B, const float* Kn, const float* Kp, const uint16_t* Kb, int64_t N, int D,
-                          int k, int64_t idx_base, float* out_scores, int64_t* out_idx, int* overflow, int64_t* overflow_idx,
-                          void* ws, size_t ws_bytes, void* stream, int64_t plan_N, float* theta, ragraph_exchange_fn exchange,
-                          void* ctx, int n_shards) {
-  RG_REQUIRE(Q && Kn && Kb && out_scores && out_idx && overflow && ws, RAGRAPH_EINVAL, "topk_cosine_filtered: null pointer");
-  RG_REQUIRE(n_shards >= 1, RAGRAPH_EINVAL, "topk_cosine_filtered: n_shards=%d", n_shards);
-  RG_REQUIRE(filter_dim_ok(D), RAGRAPH_EUNSUPPORTED, "topk_cosine_filtered: D=%d not in {64,128,256}", D);
-  RG_REQUIRE(B >= 1 && N >= 1 && k >= 1 && k <= 32 && k <= N, RAGRAPH_EINVAL, "topk_cosine_filtered: bad B/N/k");
+// Steps 1 and 2 of a call: validate, plan, and hand the plan to whoever executes it.  The thread's prior and int8 cap and the
+// per-call switches are read here and nowhere else.  The schedule (its pow() search) is computed once for a single bank; a
+// shard among several that pool their first sample computes two -- the single bank's, which sizes the minimum workspace,
+// and its own.  filter_call_plan (cheap arithmetic) runs three times: twice for that size, once for the call.
+static int filtered_entry(const FilteredArgs& a) {
+  const int64_t B = a.B, N = a.N, plan_N = a.plan_N;
+  const int D = a.D, k = a.k;
+  RG_REQUIRE(a.Q && a.Kn && a.Kb && a.out_scores && a.out_idx && a.overflow && a.ws, RAGRAPH_EINVAL, "topk_cosine_filtered: null pointer");
+  RG_REQUIRE(a.n_shards >= 1, RAGRAPH_EINVAL, "topk_cosine_filtered: n_shards=%d", a.n_shards);
+  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered", B, N, D, k);
   RG_REQUIRE(N < (int64_t)INT_MAX - 1024, RAGRAPH_EUNSUPPORTED, "topk_cosine_filtered: shard rows must fit int32");
-  RG_REQUIRE(plan_N >= N && (exchange || plan_N - N <= 1024), RAGRAPH_EINVAL, "topk_cosine_filtered: plan_N must be the largest shard's size");
-  RG_REQUIRE(!exchange || theta, RAGRAPH_EINVAL, "topk_cosine_filtered: an exchange needs the theta buffer");
-  RG_REQUIRE(aligned16(Q) && aligned16(Kn) && aligned16(Kb) && aligned16(ws), RAGRAPH_EINVAL,
+  RG_REQUIRE(plan_N >= N && (a.exchange || plan_N - N <= 1024), RAGRAPH_EINVAL, "topk_cosine_filtered: plan_N must be the largest shard's size");
+  RG_REQUIRE(!a.exchange || a.theta, RAGRAPH_EINVAL, "topk_cosine_filtered: an exchange needs the theta buffer");
+  RG_REQUIRE(aligned16(a.Q) && aligned16(a.Kn) && aligned16(a.Kb) && aligned16(a.ws), RAGRAPH_EINVAL,
              "topk_cosine_filtered: pointers must be 16-B aligned");
-  const size_t need = ragraph_topk_cosine_filtered_workspace_bytes(B, plan_N, D, k);
-  RG_REQUIRE(ws_bytes >= need, RAGRAPH_EWORKSPACE, "topk_cosine_filtered: workspace %zu < %zu", ws_bytes, need);
-  if (D == 256)
-    return run_filtered<256>(Q, B, Kn, Kp, Kb, N, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
-                             plan_N, theta, exchange, ctx, n_shards);
-  if (D == 128)
-    return run_filtered<128>(Q, B, Kn, Kp, Kb, N, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
-                             plan_N, theta, exchange, ctx, n_shards);
-  return run_filtered<64>(Q, B, Kn, Kp, Kb, N, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
-                          plan_N, theta, exchange, ctx, n_shards);
+  // every call owns at least what the single bank of plan_N rows needs; the schedule behind that size is this call's own
+  // unless the call is one of several shards that pool their first sample
+  const FilterShape one = filter_query_shape(B, plan_N, D, k, 1, false);
+  const FilterSchedule sc_one = filter_schedule(one);
+  const size_t need = filter_workspace_bytes(one, sc_one);
+  RG_REQUIRE(a.ws_bytes >= need, RAGRAPH_EWORKSPACE, "topk_cosine_filtered: workspace %zu < %zu", a.ws_bytes, need);
+  const FilterShape in{B, N, plan_N, D, k, a.n_shards, a.exchange != nullptr, t_prior, t_max_i8_levels, false, one.env, one.cus};
+  const FilterCall c = filter_call_plan(in, a.exchange && a.n_shards > 1 ? filter_schedule(in) : sc_one);
+  if (c.exact_participant) return run_exact_participant(a, c);
+  if (D == 256) return run_filtered<256>(a, c, in);
+  if (D == 128) return run_filtered<128>(a, c, in);
+  return run_filtered<64>(a, c, in);
 }
 
 extern "C" int ragraph_topk_cosine_filtered_f32(const float* Q, int64_t B, const float* Kn, const float* Kp,
                                                 const uint16_t* Kb, int64_t N, int D, int k, int64_t idx_base,
                                                 float* out_scores, int64_t* out_idx, int* overflow,
                                                 int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream) {
-  return filtered_entry(Q, B, Kn, Kp, Kb, N, D, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
-                        N, nullptr, nullptr, nullptr, 1);
+  return filtered_entry({Q, B, Kn, Kp, Kb, N, D, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
+                         N, nullptr, nullptr, nullptr, 1});
 }
 
 extern "C" int ragraph_topk_cosine_filtered_sharded_f32(const float* Q, int64_t B, const float* Kn, const float* Kp,
@@ -1058,13 +895,8 @@ extern "C" int ragraph_topk_cosine_filtered_sharded_f32(const float* Q, int64_t 
                                                         int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream,
                                                         int64_t plan_N, float* theta, ragraph_exchange_fn exchange,
                                                         void* ctx, int n_shards) {
-  return filtered_entry(Q, B, Kn, Kp, Kb, N, D, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
-                        plan_N, theta, exchange, ctx, n_shards);
-}
-
-extern "C" int ragraph_topk_cosine_filtered_sharded_speculates(int64_t B, int64_t plan_N, int D, int k, int n_shards) {
-  if (!filter_dim_ok(D) || B < 1 || plan_N < 1 || k < 1 || k > 32 || n_shards < 1) return 0;
-  return filter_schedule(B, plan_N, D, k, n_shards).bound_keys > 0 ? 1 : 0;
+  return filtered_entry({Q, B, Kn, Kp, Kb, N, D, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
+                         plan_N, theta, exchange, ctx, n_shards});
 }
 
 extern "C" int ragraph_verify_merged_prior_f32(const float* merged_scores, int64_t R, int k, float prior, int speculative,
