@@ -431,6 +431,28 @@ size_t ragraph_sparse_workspace_bytes(int64_t nnz, int D);
 int ragraph_spmm_csr_ws_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n, const float* X, int D,
                             const float* bias, int act, float alpha, float beta, const float* Y_in, float* Y, int64_t nnz,
                             void* ws, size_t ws_bytes, void* stream);
+/* Row subset of the product: Y[r,:] = (A X)[rows[r],:] for R row ids (int64, device memory; they may repeat and come in any
+ * order), Y [R,D] row-major -- the last propagation layer of the edge flavour's training step, which the loss reads at the
+ * batch's rows only (RAGraph_edge/modules/RAGraph.py:232-240,327,343-345).  Every row's sum is the chain of
+ * ragraph_spmm_csr_f32 (fmaf in CSR order from +0; blocks of 4096 edges, see "Hub rows"): bit-identical to that entry's Y at
+ * rows[r].  No epilogue.  A row id outside [0, n) is an EMPTY row: zeros are written, nothing is dereferenced.  D % 4 == 0.
+ * ws = NULL: a hub row is walked by its own lanes.  With ws (ragraph_spmm_csr_rows_workspace_bytes(nnz, R, D) bytes) the
+ * blocks of requested hub rows are tasks for the whole chip; the area holds R + nnz / 4096 + 1 block sums -- enough for
+ * distinct rows -- and a request whose blocks do not fit (duplicated hubs) is walked by its own lanes: the same bits, and
+ * nothing is written past the area.  No allocation, no synchronisation, no read-back: capturable. */
+size_t ragraph_spmm_csr_rows_workspace_bytes(int64_t nnz, int64_t R, int D);
+int ragraph_spmm_csr_rows_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n, const float* X, int D,
+                              const int64_t* rows, int64_t R, float* Y, int64_t nnz, void* ws, size_t ws_bytes,
+                              void* stream);
+/* The edges of a row subset, for the backward of the entry above: off [R+1] = the summed lengths of rows[0..r) (off[R] = the
+ * total, -1 when it does not fit int32; rows outside [0, n) are empty), then edge e = (col, r, val) of the (e - off[r])-th
+ * edge of row rows[r] -- ascending r, CSR order inside a row; E = off[R].  ws: ragraph_csr_rows_offsets_workspace_bytes(R). */
+size_t ragraph_csr_rows_offsets_workspace_bytes(int64_t R);
+int ragraph_csr_rows_offsets_i64(const int64_t* rowptr, int64_t n, const int64_t* rows, int64_t R, int64_t* off, void* ws,
+                                 size_t ws_bytes, void* stream);
+int ragraph_csr_rows_edges_f32(const int64_t* rowptr, const int32_t* col, const float* val, const int64_t* rows, int64_t R,
+                               const int64_t* off, int64_t E, int64_t* out_col, int64_t* out_r, float* out_val,
+                               void* stream);
 /* Fine-tuning a GCN layer whose PReLU slope is a trained parameter (RAGraph_node_fewshot/RAGraph.py:69 through
  * layers/gcn.py:36-40) without reading the slope on the host: a kernel argument would freeze the slope into a captured
  * HIP graph, and reading it costs a synchronisation per step.

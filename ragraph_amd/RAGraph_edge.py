@@ -6,6 +6,8 @@ and torch.topk's indices have none); the trainers, metrics and loggers around ca
 """
 from __future__ import annotations
 
+import os
+
 import torch
 import torch.nn as nn
 
@@ -42,6 +44,9 @@ class RAGraph(nn.Module):
         self.resource_keys = self.resource_values = None
         self._keys_normalized = self._index = None
         self._csr_cache = None
+        self.loss_rows = os.environ.get("RAGRAPH_EDGE_LOSS_ROWS", type(self).loss_rows)
+        if self.loss_rows not in ("batch", "all"):
+            raise ValueError(f"RAGRAPH_EDGE_LOSS_ROWS: 'batch' or 'all', not {self.loss_rows!r}")
         if phase in ("pretrain", "for_tune"):   # :93-95: the user table, then the item table, drawn on the CPU generator
             self.user_embedding = nn.Parameter(nn.init.xavier_uniform_(torch.empty(self.num_users, emb_size)).to(device))
             self.item_embedding = nn.Parameter(nn.init.xavier_uniform_(torch.empty(self.num_items, emb_size)).to(device))
@@ -247,6 +252,71 @@ class RAGraph(nn.Module):
             total = A.axpby(total, 1 - self.retrieve_weight, rag, self.retrieve_weight)        # :328
         return total.split([self.num_users, self.num_items], dim=0)
 
+    def _distinct_rows(self, rows, n):
+        """(distinct ids ascending, inv) with distinct[inv] == rows, on the library's own sort: a stable COO -> CSR by id
+        (K.coo_to_csr), the run heads by K.mask_positions (which reads their number back: it sizes the result) and every
+        position's run by K.csr_row_ids."""
+        m = rows.numel()
+        if m == 0:
+            return rows, rows
+        _, _, perm = K.coo_to_csr(rows, torch.arange(m, device=rows.device), n)
+        s = rows[perm]
+        head = torch.ones(m, dtype=torch.bool, device=rows.device)
+        head[1:] = s[1:] != s[:-1]
+        pos = K.mask_positions(head)
+        run = K.csr_row_ids(torch.cat([pos, pos.new_full((1,), m)]), m)
+        inv = torch.empty_like(run)
+        inv[perm] = run
+        return s[pos], inv
+
+    def forward_rows(self, edges, edge_norm, edge_times, user_rows, item_rows, max_time_step=None):
+        """forward(...)[0][user_rows], forward(...)[1][item_rows] -- bit for bit -- without the rows nobody asked for.  The rows
+        may repeat and come in any order; they are deduplicated first.  Everything up to res[L-1] is forward's (each layer
+        feeds the next); the LAST layer (:280-283) enters only through sum(res) (:327), so it is computed at the distinct rows
+        (A.spmm_csr_rows: the same chain per row), and so is the retrieved term (:298-324: queries and results are row-wise,
+        and it carries no gradient).  The sums and the mix are forward's axpby chain on the gathered rows."""
+        g, perm = self._csr(edges)
+        tmin, tmax = self._time_range(edge_times, max_time_step)
+        t = K.time_rescale(edge_times[perm].contiguous(), tmin, tmax)                           # :254-257
+        time_norm = K.segment_softmax(g.rowptr, t, long_rows=g.has_long_rows)                  # :266
+        norm = K.axpby(edge_norm[perm].contiguous(), 0.5, time_norm, 0.5)                      # :267
+        train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        ue, ie = self._embeddings()
+        all_emb = self.emb_gate(torch.cat([ue, ie], dim=0))                                     # :276-277
+        if not train:
+            all_emb = all_emb.detach()
+        dev = all_emb.device
+        user_rows, item_rows = user_rows.to(dev).long().reshape(-1), item_rows.to(dev).long().reshape(-1)
+        n = self.num_users + self.num_items
+        rows, inv = self._distinct_rows(torch.cat([user_rows, item_rows + self.num_users]), n)
+        res = [all_emb]
+        gw = CSRGraph(g.rowptr, g.col, norm, g.n, _has_long_rows=g.has_long_rows)
+        for _ in range(self.num_layers - 1):                                                   # :280-283, all but the last
+            res.append(A.spmm_csr(gw, res[-1]))
+        total = A.gather_rows(res[0], rows)
+        for r in res[1:]:                                                                      # :327 sum(res_emb)
+            total = A.axpby(total, 1.0, A.gather_rows(r, rows), 1.0)
+        if self.num_layers > 0:
+            total = A.axpby(total, 1.0, A.spmm_csr_rows(gw, res[-1], rows), 1.0)
+        if self.use_RAG and self.phase in ("vanilla", "finetune"):
+            add_noise = self.use_noise and self.training
+            k = self.retrieve_num + (self.noise_retrieve_num if add_noise else 0)             # :308
+            if self._index is None:
+                self._index = K.KeyIndex(self.keys_normalized)
+            queries = K.gather_rows(res[0].detach(), rows)
+            if k > K.N.TOPK_MAX:
+                rag = K.retrieve_mean_large_k(queries, self.keys_normalized, self.resource_values, k)
+            else:
+                _, idx = self._index.topk(queries, k)
+                if add_noise:
+                    # (the one [n, 1] draw of forward, indexed by the rows: the same seed gives a row the same noise)
+                    noise = torch.randint(0, self.resource_values.shape[0], (n, self.noise_retrieve_num)).to(idx.device)
+                    idx = torch.cat([idx, noise[rows]], dim=1)
+                rag, _ = K.gather_reduce(self.resource_values, None, idx, v_scale=1.0 / idx.shape[1])  # :314,321 mean
+            total = A.axpby(total, 1 - self.retrieve_weight, rag, self.retrieve_weight)        # :328
+        out = A.gather_rows(total, inv)
+        return out[:user_rows.numel()], out[user_rows.numel():]
+
     @torch.no_grad()
     def generate(self, max_time_step=None):
         return self.forward(self.edges, self.edge_norm, self.edge_times, max_time_step=max_time_step)
@@ -260,6 +330,12 @@ class RAGraph(nn.Module):
                            # reference for the same seed, at the cost of one uniform per edge on the host and a copy per step
                            # (44 M edges: ~0.3 s of a 1-s step at c5, bench `finetune_step.edge_c5.host_mask_draw_ms`);
                            # "device": torch.rand on the device generator (another stream of random numbers, same law)
+
+    loss_rows = "batch"    # "batch": cal_loss computes the rows the loss reads -- the batch's users, positives and negatives --
+                           # through forward_rows: the same loss bits, gradients within rounding (two sums associate
+                           # differently), without the last layer and the retrieval of every other node;
+                           # "all": the whole forward, then the gathers, as the reference.  RAGRAPH_EDGE_LOSS_ROWS overrides
+                           # the default of a new model
 
     def draw_edge_mask(self):
         """The step's edge-dropout mask (bool, on the device), or None when nothing is dropped."""
@@ -282,10 +358,14 @@ class RAGraph(nn.Module):
             kept = K.mask_positions(mask)            # (the library's own prefix sums: no other library's select on this path)
             edges, norm, times = self.edges[kept], self.edge_norm[kept], self.edge_times[kept]
         users, pos_items, neg_items = (t.to(self.edges.device).long() for t in batch_data)
-        user_emb, item_emb = self.forward(edges, norm, times)
-        u = A.gather_rows(user_emb.contiguous(), users)                                        # :343-345
-        p = A.gather_rows(item_emb.contiguous(), pos_items)
-        q = A.gather_rows(item_emb.contiguous(), neg_items)
+        if self.loss_rows == "batch":
+            u, pq = self.forward_rows(edges, norm, times, users, torch.cat([pos_items, neg_items]))
+            p, q = pq[:pos_items.numel()], pq[pos_items.numel():]
+        else:
+            user_emb, item_emb = self.forward(edges, norm, times)
+            u = A.gather_rows(user_emb.contiguous(), users)                                    # :343-345
+            p = A.gather_rows(item_emb.contiguous(), pos_items)
+            q = A.gather_rows(item_emb.contiguous(), neg_items)
         # base_model.py:81-86 (the loss itself: a few thousand scalars -- trainer-side bookkeeping in torch)
         pos_score, neg_score = (u * p).sum(dim=1), (u * q).sum(dim=1)
         rec = (-torch.log(1e-10 + torch.sigmoid(pos_score - neg_score))).mean()

@@ -98,6 +98,11 @@ SIGNATURES = {
     "ragraph_sparse_workspace_bytes": (_sz, [_i64, _i32]),
     "ragraph_spmm_csr_ws_f32": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _f32, _f32, _vp, _vp, _i64, _vp, _sz,
                                        _vp]),
+    "ragraph_spmm_csr_rows_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "ragraph_spmm_csr_rows_f32": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
+    "ragraph_csr_rows_offsets_workspace_bytes": (_sz, [_i64]),
+    "ragraph_csr_rows_offsets_i64": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "ragraph_csr_rows_edges_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "ragraph_axpby_f32": (_i32, [_vp, _f32, _vp, _f32, _i64, _vp, _vp]),
     "ragraph_softmax_mix_f32": (_i32, [_vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp]),
     "ragraph_fuse_decode_f32": (_i32, [_vp, _vp, _i64, _i32, _f32, _f32, _vp, _vp, _i32, _f32, _vp, _vp, _i32, _vp, _f32,

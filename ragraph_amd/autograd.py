@@ -188,6 +188,39 @@ def spmm_csr(g, x, bias=None, act=K.ACT_NONE, alpha_param=None, alpha=0.0):
     return K.spmm_csr(g.rowptr, g.col, g.val, x, bias=bias, act=act, alpha=alpha, long_rows=g.has_long_rows)
 
 
+class _SpmmCsrRows(torch.autograd.Function):
+    """y = (A @ x)[rows] for a CSRGraph A without the other rows (K.spmm_csr_rows) -- the last propagation layer of the edge
+    flavour's step, read at the batch's rows only (modules/RAGraph.py:232-240,327,343-345).  Backward touches only the edges of
+    the requested rows: they are expanded to COO (col, r, val) in ascending-r, CSR order (K.csr_rows_edges), sorted by col --
+    stable, the library's own sort -- into the [n, R] transposed pattern, and gx = one SpMM of it over gy [R, D]: row j of gx
+    is the fmaf chain over the requests that hold j, in request order."""
+
+    @staticmethod
+    def forward(ctx, g, x, rows):
+        ctx.g, ctx.n_cols = g, x.shape[0]
+        ctx.save_for_backward(rows)
+        return K.spmm_csr_rows(g.rowptr, g.col, g.val, x, rows, long_rows=g.has_long_rows)
+
+    @staticmethod
+    def backward(ctx, gy):
+        (rows,) = ctx.saved_tensors
+        g = ctx.g
+        c, r, v = K.csr_rows_edges(g.rowptr, g.col, g.val, rows)
+        rowptr_t, col_t, perm = K.coo_to_csr(c, r, ctx.n_cols)
+        gy = gy.contiguous().reshape(rows.numel(), -1)
+        # (a column may sit in more than ROW_BLOCK requested rows only when that many were requested; the flag costs three
+        # launches and changes no bit)
+        gx = K.spmm_csr(rowptr_t, col_t, v[perm].contiguous(), gy, long_rows=rows.numel() > K.ROW_BLOCK)
+        return None, gx, None
+
+
+def spmm_csr_rows(g, x, rows):
+    """Differentiable (in x) (A @ x)[rows]; rows: int64 ids, any order, repeats allowed."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _SpmmCsrRows.apply(g, x, rows)
+    return K.spmm_csr_rows(g.rowptr, g.col, g.val, x, rows, long_rows=g.has_long_rows)
+
+
 class _SigmoidGate(torch.autograd.Function):
     """x * sigmoid(z) -- RAGraph_edge/modules/RAGraph.py:168."""
 

@@ -379,3 +379,94 @@ extern "C" int ragraph_mask_positions_i64(const unsigned char* mask, int64_t E, 
   RG_CHECK_LAUNCH("mask_positions");
   return RAGRAPH_OK;
 }
+
+// ---- the edges of a row subset (the backward of ragraph_spmm_csr_rows_f32) --------------------------------------------
+// off[r] = the summed lengths of rows[0 .. r) (off[R] = the total; a row outside [0, n) is empty), on the library's own
+// prefix sums; then edge e of the subset = (col, r, val) of the (e - off[r])-th edge of row rows[r]: ascending r, CSR order.
+namespace ragraph {
+
+__global__ void __launch_bounds__(256) rows_deg_kernel(const int64_t* __restrict__ rowptr, int64_t n,
+                                                       const int64_t* __restrict__ rows, int64_t R, int* __restrict__ deg) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r > R) return;
+  int d = 0;
+  if (r < R) {
+    const int64_t row = rows[r];
+    if (row >= 0 && row < n) d = (int)(rowptr[row + 1] - rowptr[row]);
+  }
+  deg[r] = d;   // (deg[R] = 0: the exclusive scan of R + 1 terms ends in the total)
+}
+
+// int32 prefix sums -> int64; a total of 2^31 or more shows as a sum that went down: off[R] = -1 then
+__global__ void __launch_bounds__(256) rows_off_kernel(const int* __restrict__ sum, int64_t R, int64_t* __restrict__ off,
+                                                       int* __restrict__ bad) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r > R) return;
+  if (sum[r] < 0 || (r > 0 && sum[r] < sum[r - 1])) *bad = 1;
+  if (r < R) off[r] = sum[r];
+}
+
+__global__ void rows_total_kernel(const int* __restrict__ sum, int64_t R, const int* __restrict__ bad, int64_t* __restrict__ off) {
+  off[R] = *bad ? -1 : (int64_t)sum[R];
+}
+
+__global__ void __launch_bounds__(256) rows_edges_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                         const float* __restrict__ val, const int64_t* __restrict__ rows,
+                                                         int64_t R, const int64_t* __restrict__ off, int64_t E,
+                                                         int64_t* __restrict__ out_col, int64_t* __restrict__ out_r,
+                                                         float* __restrict__ out_val) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  int64_t lo = 0, hi = R;   // invariant: off[lo] <= e < off[hi]  (the last r with off[r] <= e: the non-empty one)
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (off[mid] <= e) lo = mid;
+    else hi = mid;
+  }
+  const int64_t src = rowptr[rows[lo]] + (e - off[lo]);
+  out_col[e] = col[src];
+  out_r[e] = lo;
+  out_val[e] = val[src];
+}
+
+}  // namespace ragraph
+
+extern "C" size_t ragraph_csr_rows_offsets_workspace_bytes(int64_t R) {
+  if (R < 0 || R + 1 >= (int64_t)INT_MAX) return 0;
+  return 256 + 2 * align_up((size_t)(R + 1) * 4, 256) + scan_temp_bytes(R + 1) + 256;
+}
+
+extern "C" int ragraph_csr_rows_offsets_i64(const int64_t* rowptr, int64_t n, const int64_t* rows, int64_t R, int64_t* off,
+                                            void* ws, size_t ws_bytes, void* stream) {
+  RG_REQUIRE(rowptr && off && ws && (rows || R == 0), RAGRAPH_EINVAL, "csr_rows_offsets: null pointer");
+  RG_REQUIRE(n >= 0 && R >= 0 && R + 1 < (int64_t)INT_MAX, RAGRAPH_EINVAL, "csr_rows_offsets: bad n/R");
+  RG_REQUIRE(ws_bytes >= ragraph_csr_rows_offsets_workspace_bytes(R), RAGRAPH_EWORKSPACE, "csr_rows_offsets: workspace too small");
+  hipStream_t st = as_stream(stream);
+  char* w = static_cast<char*>(ws);
+  int* bad = reinterpret_cast<int*>(w);
+  int* deg = reinterpret_cast<int*>(w + 256);
+  int* sum = reinterpret_cast<int*>(w + 256 + align_up((size_t)(R + 1) * 4, 256));
+  void* temp = w + 256 + 2 * align_up((size_t)(R + 1) * 4, 256);
+  RG_HIPCUB(hipMemsetAsync(bad, 0, sizeof(int), st), "csr_rows_offsets(memset)");
+  const unsigned g = (unsigned)cdiv(R + 1, 256);
+  hipLaunchKernelGGL(rows_deg_kernel, dim3(g), dim3(256), 0, st, rowptr, n, rows, R, deg);
+  const int rc = scan_sum_i32(deg, sum, R + 1, false, temp, scan_temp_bytes(R + 1) + 256, st);
+  if (rc != RAGRAPH_OK) return rc;
+  hipLaunchKernelGGL(rows_off_kernel, dim3(g), dim3(256), 0, st, sum, R, off, bad);
+  hipLaunchKernelGGL(rows_total_kernel, dim3(1), dim3(1), 0, st, sum, R, bad, off);
+  RG_CHECK_LAUNCH("csr_rows_offsets");
+  return RAGRAPH_OK;
+}
+
+extern "C" int ragraph_csr_rows_edges_f32(const int64_t* rowptr, const int32_t* col, const float* val, const int64_t* rows,
+                                          int64_t R, const int64_t* off, int64_t E, int64_t* out_col, int64_t* out_r,
+                                          float* out_val, void* stream) {
+  RG_REQUIRE(E >= 0 && R >= 0, RAGRAPH_EINVAL, "csr_rows_edges: bad R/E");
+  if (E == 0) return RAGRAPH_OK;
+  RG_REQUIRE(rowptr && col && val && rows && off && out_col && out_r && out_val && R >= 1, RAGRAPH_EINVAL,
+             "csr_rows_edges: null pointer");
+  hipLaunchKernelGGL(rows_edges_kernel, dim3((unsigned)cdiv(E, 256)), dim3(256), 0, as_stream(stream), rowptr, col, val, rows,
+                     R, off, E, out_col, out_r, out_val);
+  RG_CHECK_LAUNCH("csr_rows_edges");
+  return RAGRAPH_OK;
+}

@@ -770,3 +770,196 @@ extern "C" int ragraph_spmm_csr_tiled_f32(const int* wp, const int* col3, const 
   RG_CHECK_LAUNCH("spmm_csr_tiled");
   return RAGRAPH_OK;
 }
+
+// ---- row subset: Y[r, :] = (A X)[rows[r], :] -----------------------------------------------------------------------
+// The edge flavour's training step reads the last propagation layer at the batch's rows only (RAGraph_edge/modules/
+// RAGraph.py:232-240 summed at :327, read at :343-345): a few thousand rows of millions.  One lane group per REQUEST walks
+// the requested row with row_chain -- the chain of spmm_csr_kernel, so the bits are those of the full product at that row.
+// Hub rows: with a workspace a request for a row of more than ROW_BLOCK edges reserves one task per block (rows_long_kernel;
+// the blocks kernel above sums them, spmm_rows_finish_kernel adds a request's block sums in block order).  How many blocks
+// the requests hold is only known on the device: the area takes R + nnz / ROW_BLOCK + 1 block sums, which is enough for
+// distinct rows; a request whose blocks do not fit (duplicated hubs) keeps slot -1 and is walked by its own lane group.
+namespace ragraph {
+
+// One thread per request.  slot[r] = the first task of request r, or -1 (short, outside [0, n), or no room).  The
+// reservation is a compare-and-swap on the task counter: it only ever moves by a reservation that fits, so the tasks
+// [0, ctr[1]) are all written and ctr[1] <= max_tasks.  (Which request gets which range does not reach the result.)
+__global__ void __launch_bounds__(256) rows_long_kernel(const int64_t* __restrict__ rowptr, int64_t n,
+                                                        const int64_t* __restrict__ rows, int64_t R, int* __restrict__ slot,
+                                                        LongRows w) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  int s = -1;
+  const int64_t row = rows[r];
+  if (row >= 0 && row < n) {
+    const int64_t deg = rowptr[row + 1] - rowptr[row];
+    if (deg > ROW_BLOCK) {
+      const int64_t nb = (deg + ROW_BLOCK - 1) / ROW_BLOCK;
+      int cur = __atomic_load_n(w.ctr + 1, __ATOMIC_RELAXED);
+      while ((int64_t)cur + nb <= w.max_tasks) {
+        const int prev = atomicCAS(w.ctr + 1, cur, cur + (int)nb);
+        if (prev == cur) {
+          s = cur;
+          break;
+        }
+        cur = prev;
+      }
+      if (s >= 0) {
+        const int li = atomicAdd(w.ctr, 1);   // (every reservation holds >= 2 tasks: li < max_tasks / 2 + 1 = max_rows)
+        w.rows[li] = r;
+        w.pos[li] = s;
+        for (int b = 0; b < (int)nb; ++b) {
+          w.task_row[s + b] = row;
+          w.task_blk[s + b] = b;
+        }
+      }
+    }
+  }
+  slot[r] = s;
+}
+
+// One lane group per request.  slot == nullptr: no workspace, a hub row's group walks its blocks itself.
+template <int LPR>
+__global__ void __launch_bounds__(256) spmm_rows_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                        const float* __restrict__ val, int64_t n,
+                                                        const float* __restrict__ X, int D,
+                                                        const int64_t* __restrict__ rows, int64_t R,
+                                                        const int* __restrict__ slot, float* __restrict__ Y) {
+  constexpr int RPB = 256 / LPR;
+  const int lr = threadIdx.x % LPR;
+  const int gbase = (threadIdx.x & 63) - lr;
+  const int64_t r = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
+  const bool live = r < R;   // dead groups run along with zero edges
+  const int64_t row = live ? rows[r] : -1;
+  int64_t e0 = 0, deg = 0;
+  if (row >= 0 && row < n) {   // a row outside the matrix is an empty row: zeros
+    e0 = rowptr[row];
+    deg = rowptr[row + 1] - e0;
+  }
+  bool mine = live;
+  if (slot && deg > ROW_BLOCK && slot[r] >= 0) {   // its blocks are tasks of the long-row kernels
+    mine = false;
+    deg = 0;
+  }
+  const int D4 = D >> 2;
+  const float4* X4 = reinterpret_cast<const float4*>(X);
+  for (int c4 = lr; c4 < ((D4 + LPR - 1) / LPR) * LPR; c4 += LPR) {
+    const bool colok = c4 < D4;
+    float4 acc;
+    if (deg <= ROW_BLOCK) {
+      acc = row_chain<LPR>(col, val, e0, (int)deg, X4, D4, c4, colok, lr, gbase);
+    } else {
+      acc = row_chain<LPR>(col, val, e0, ROW_BLOCK, X4, D4, c4, colok, lr, gbase);
+      for (int64_t b0 = ROW_BLOCK; b0 < deg; b0 += ROW_BLOCK) {
+        const int cnt = deg - b0 < ROW_BLOCK ? (int)(deg - b0) : ROW_BLOCK;
+        acc = add4(acc, row_chain<LPR>(col, val, e0 + b0, cnt, X4, D4, c4, colok, lr, gbase));
+      }
+    }
+    if (!mine || !colok) continue;
+    reinterpret_cast<float4*>(Y)[r * D4 + c4] = acc;
+  }
+}
+
+// One lane group per listed request: its block sums in block order -> Y[request].
+template <int LPR>
+__global__ void __launch_bounds__(256) spmm_rows_finish_kernel(const int64_t* __restrict__ rowptr,
+                                                               const int64_t* __restrict__ rows, int D,
+                                                               float* __restrict__ Y, LongRows w) {
+  constexpr int RPB = 256 / LPR;
+  const int lr = threadIdx.x % LPR;
+  const int64_t li = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
+  if (li >= w.ctr[0]) return;
+  const int64_t r = w.rows[li];
+  const int64_t row = rows[r];
+  const int64_t deg = rowptr[row + 1] - rowptr[row];
+  const int nb = (int)((deg + ROW_BLOCK - 1) / ROW_BLOCK);
+  const int64_t p = w.pos[li];
+  const int D4 = D >> 2;
+  const float4* P4 = reinterpret_cast<const float4*>(w.partial);
+  for (int c4 = lr; c4 < D4; c4 += LPR) {
+    float4 acc = P4[p * D4 + c4];
+    for (int b = 1; b < nb; ++b) acc = add4(acc, P4[(p + b) * D4 + c4]);
+    reinterpret_cast<float4*>(Y)[r * D4 + c4] = acc;
+  }
+}
+
+}  // namespace ragraph
+
+// Workspace of the row-subset product: per-request slots, then the long-row lists with rows[] = REQUEST indices.
+static size_t rows_layout(int64_t nnz, int64_t R, int D, int** slot, LongRows* w, char* base) {
+  const int64_t max_tasks = R + nnz / ROW_BLOCK + 1, max_rows = max_tasks / 2 + 1;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += align_up(bytes, 256);
+    return p;
+  };
+  char* c = take(2 * sizeof(int));
+  char* sl = take((size_t)(R > 0 ? R : 1) * sizeof(int));
+  char* r = take((size_t)max_rows * sizeof(int64_t));
+  char* ps = take((size_t)max_rows * sizeof(int));
+  char* tr = take((size_t)max_tasks * sizeof(int64_t));
+  char* tb = take((size_t)max_tasks * sizeof(int));
+  char* pa = take((size_t)max_tasks * (size_t)D * sizeof(float));
+  if (slot) *slot = reinterpret_cast<int*>(sl);
+  if (w) {
+    w->ctr = reinterpret_cast<int*>(c);
+    w->rows = reinterpret_cast<int64_t*>(r);
+    w->pos = reinterpret_cast<int*>(ps);
+    w->task_row = reinterpret_cast<int64_t*>(tr);
+    w->task_blk = reinterpret_cast<int*>(tb);
+    w->partial = reinterpret_cast<float*>(pa);
+    w->max_rows = max_rows;
+    w->max_tasks = max_tasks;
+  }
+  return off;
+}
+
+extern "C" size_t ragraph_spmm_csr_rows_workspace_bytes(int64_t nnz, int64_t R, int D) {
+  if (nnz < 0 || R < 0 || D < 1 || R + nnz / ROW_BLOCK + 1 >= (int64_t)INT_MAX) return 0;
+  return rows_layout(nnz, R, D, nullptr, nullptr, nullptr);
+}
+
+extern "C" int ragraph_spmm_csr_rows_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n,
+                                         const float* X, int D, const int64_t* rows, int64_t R, float* Y, int64_t nnz,
+                                         void* ws, size_t ws_bytes, void* stream) {
+  RG_REQUIRE(rowptr && X && (R == 0 || (rows && Y)), RAGRAPH_EINVAL, "spmm_csr_rows: null pointer");
+  RG_REQUIRE(n >= 0 && R >= 0 && nnz >= 0, RAGRAPH_EINVAL, "spmm_csr_rows: bad n/R/nnz");
+  RG_REQUIRE(D >= 4 && (D & 3) == 0, RAGRAPH_EINVAL, "spmm_csr_rows: D=%d must be a positive multiple of 4", D);
+  RG_REQUIRE(aligned16(X) && aligned16(Y) && X != Y, RAGRAPH_EINVAL, "spmm_csr_rows: X, Y must be 16-B aligned and distinct");
+  if (R == 0) return RAGRAPH_OK;
+  hipStream_t st = as_stream(stream);
+  LongRows w{};
+  int* slot = nullptr;
+  const bool par = ws != nullptr && nnz > ROW_BLOCK;  // (no row can be long otherwise)
+  if (par) {
+    const size_t need = ragraph_spmm_csr_rows_workspace_bytes(nnz, R, D);
+    RG_REQUIRE(need > 0, RAGRAPH_EUNSUPPORTED, "spmm_csr_rows: R + nnz / 4096 must fit int32");
+    RG_REQUIRE(aligned16(ws) && ws_bytes >= need, RAGRAPH_EWORKSPACE, "spmm_csr_rows: workspace %zu < %zu", ws_bytes, need);
+    rows_layout(nnz, R, D, &slot, &w, static_cast<char*>(ws));
+    if (hipMemsetAsync(w.ctr, 0, 2 * sizeof(int), st) != hipSuccess) {
+      set_error("spmm_csr_rows: memset failed");
+      return RAGRAPH_EDEVICE;
+    }
+    hipLaunchKernelGGL(rows_long_kernel, dim3((unsigned)cdiv(R, 256)), dim3(256), 0, st, rowptr, n, rows, R, slot, w);
+  }
+#define RG_SPMM_ROWS(LPR_)                                                                                             \
+  do {                                                                                                                 \
+    constexpr int RPB_ = 256 / (LPR_);                                                                                 \
+    hipLaunchKernelGGL(spmm_rows_kernel<LPR_>, dim3((unsigned)cdiv(R, RPB_)), dim3(256), 0, st, rowptr, col, val, n,   \
+                       X, D, rows, R, (const int*)slot, Y);                                                           \
+    if (par) {                                                                                                         \
+      hipLaunchKernelGGL(spmm_long_blocks_kernel<LPR_>, dim3((unsigned)cdiv(w.max_tasks, RPB_)), dim3(256), 0, st,     \
+                         rowptr, col, val, X, D, w);                                                                   \
+      hipLaunchKernelGGL(spmm_rows_finish_kernel<LPR_>, dim3((unsigned)cdiv(w.max_rows, RPB_)), dim3(256), 0, st,      \
+                         rowptr, rows, D, Y, w);                                                                       \
+    }                                                                                                                  \
+  } while (0)
+  const int D4 = D >> 2;
+  if (D4 <= 16) RG_SPMM_ROWS(16);
+  else if (D4 <= 32) RG_SPMM_ROWS(32);
+  else RG_SPMM_ROWS(64);
+#undef RG_SPMM_ROWS
+  RG_CHECK_LAUNCH("spmm_csr_rows");
+  return RAGRAPH_OK;
+}

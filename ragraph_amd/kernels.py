@@ -774,6 +774,58 @@ def spmm_csr(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, x: torc
     return y
 
 
+def spmm_csr_rows(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, x: torch.Tensor, rows: torch.Tensor,
+                  long_rows: bool = False) -> torch.Tensor:
+    """(A @ x)[rows] without the other rows (ragraph_spmm_csr_rows_f32) -- the last propagation layer of the edge flavour's
+    training step at the batch's rows, modules/RAGraph.py:232-240,327,343-345.  rows: int64 ids, any order, repeats allowed;
+    returns [R, D], bit-identical to spmm_csr(...)[rows].  `long_rows`: as spmm_csr (the blocks of requested hub rows are
+    spread over the chip through a workspace)."""
+    L = _ready()
+    rowptr = _idxc(rowptr, "spmm_csr_rows.rowptr")
+    col = _idxc(col, "spmm_csr_rows.col", torch.int32)
+    val = _f32c(val, "spmm_csr_rows.val")
+    x = _f32c(x, "spmm_csr_rows.x")
+    rows = _idxc(rows, "spmm_csr_rows.rows").reshape(-1)
+    n, D, R, nnz = rowptr.numel() - 1, x.shape[1], rows.numel(), col.numel()
+    y = torch.empty((R, D), dtype=torch.float32, device=x.device)
+    ws = None
+    if long_rows:
+        nbytes = L.ragraph_spmm_csr_rows_workspace_bytes(nnz, R, D)
+        if nbytes == 0:
+            raise RagraphNativeError(f"spmm_csr_rows: unsupported sizes (nnz={nnz}, R={R}, D={D})")
+        ws = _workspace(nbytes, x.device)
+    N.check(L.ragraph_spmm_csr_rows_f32(rowptr.data_ptr(), _ptr(col) if nnz else None, _ptr(val) if nnz else None, n,
+                                        x.data_ptr(), D, rows.data_ptr() if R else None, R, y.data_ptr(), nnz, _ptr(ws),
+                                        0 if ws is None else ws.numel(), _stream()), "spmm_csr_rows")
+    return y
+
+
+def csr_rows_edges(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, rows: torch.Tensor):
+    """The edges of the rows `rows` of a CSR matrix as COO (col int64 [E], r int64 [E] = the POSITION in `rows`, val [E]):
+    ascending r, CSR order inside a row (ragraph_csr_rows_offsets_i64 on the library's own prefix sums, then
+    ragraph_csr_rows_edges_f32) -- what the backward of spmm_csr_rows multiplies by.  Reads the edge count back (one
+    synchronisation: it sizes the result)."""
+    L = _ready()
+    rowptr = _idxc(rowptr, "csr_rows_edges.rowptr")
+    col = _idxc(col, "csr_rows_edges.col", torch.int32)
+    val = _f32c(val, "csr_rows_edges.val")
+    rows = _idxc(rows, "csr_rows_edges.rows").reshape(-1)
+    n, R, dev = rowptr.numel() - 1, rows.numel(), rowptr.device
+    off = torch.empty(R + 1, dtype=torch.int64, device=dev)
+    ws = _workspace(L.ragraph_csr_rows_offsets_workspace_bytes(R), dev)
+    N.check(L.ragraph_csr_rows_offsets_i64(rowptr.data_ptr(), n, rows.data_ptr() if R else None, R, off.data_ptr(), ws.data_ptr(),
+                                           ws.numel(), _stream()), "csr_rows_offsets")
+    E = int(off[R].item())
+    if E < 0:
+        raise RagraphNativeError("csr_rows_edges: the requested rows hold 2^31 edges or more")
+    oc = torch.empty(E, dtype=torch.int64, device=dev)
+    orr = torch.empty(E, dtype=torch.int64, device=dev)
+    ov = torch.empty(E, dtype=torch.float32, device=dev)
+    N.check(L.ragraph_csr_rows_edges_f32(rowptr.data_ptr(), _ptr(col), _ptr(val), rows.data_ptr() if R else None, R, off.data_ptr(),
+                                         E, _ptr(oc), _ptr(orr), _ptr(ov), _stream()), "csr_rows_edges")
+    return oc, orr, ov
+
+
 def spmm_csr_panels(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, x: torch.Tensor, x_panels: bool, y_panels: bool,
                     act: int = ACT_NONE, alpha: float = 0.0) -> torch.Tensor:
     """act(A @ x) with x and / or the result PANEL-major ([D/32][n][32] floats, stored as an [n, D]-sized tensor) --
