@@ -834,6 +834,45 @@ int ragraph_edge_neg_sample_i64(const int64_t* rowptr, const int64_t* items, int
                                 const int64_t* users, int64_t B, int n_negs, int check_users, const int64_t* seed, int64_t* out,
                                 void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * NZ  noisy fine-tuning, the noise drawn on the device (finetune-noise.py of every flavour; csrc/noise.hip)
+ *
+ * The reference draws its noise from torch's CPU generator on every step.  These entries draw from the counter-based hash of
+ * the samplers above instead: a value depends on (seed[0], row id, draw) only, seed[0] is read from DEVICE memory, and no
+ * call allocates, synchronises or reads back -- a step that uses them can be captured.  Every entry takes `row_ids`, int64 [B]
+ * on the device, or NULL: row b then has the id row_base + b.
+ *
+ * ragraph_noise_rows_i64: the random bank rows behind the top-k -- RAGraph_node/ragraph_utils/ToyGraphBase.py:73-79,
+ *   RAGraph_node_fewshot/ragraph_utils/ToyGraphBase.py:70-76, RAGraph_edge/modules/RAGraph.py:316-318
+ *   (torch.randint(0, N, (B, noise_retrieve_num))).  out[b * out_stride + j] = lp_below(lp_draw(seed[0], id(b), j), N) for
+ *   j < m: the high 64 bits of hash * N, uniform over [0, N).  N >= 1, m >= 1, B >= 0, out_stride >= m -- a caller writes the
+ *   tail columns of a [B, k + m] index matrix in place (out = matrix + k, out_stride = k + m).  RAGRAPH_EINVAL (N < 1, m < 1,
+ *   out_stride < m, a null seed) before anything is written.
+ *
+ * ragraph_gather_reduce_noisy_f32: ragraph_gather_reduce_f32 / _mix_f32 over the k listed rows AND m noise rows behind them
+ *   -- RAGraph_node/RAGraph.py:48-49 with add_noise, RAGraph_edge/modules/RAGraph.py:314-321 -- with no index matrix for the
+ *   noise: row b adds V[idx[b, 0..k)] in rank order, then V[noise(b, 0..m)], noise(b, j) = lp_below(lp_draw(seed[0], id(b), j),
+ *   noise_n), in one chain of fp32 adds.  out[b,:] = v_scale * sum (then A[b,:] * wa + out * wb when A is not NULL, as _mix);
+ *   mean_L[b,:] = (sum over the k + m rows of L) / (k + m).  N and idx_base describe the shard of V as above: listed and noise
+ *   rows outside [idx_base, idx_base + N) contribute zero.  The bits of ragraph_gather_reduce_f32 (_mix_f32) on
+ *   cat(idx, ragraph_noise_rows_i64(...)).  k >= 1, m >= 1, noise_n >= 1; out must not alias A.
+ *
+ * ragraph_add_normal_noise_f32: the Gaussian noise on the gathered embeddings -- RAGraph_graph/ragraph_utils/ToyGraphBase.py:
+ *   131-134, RAGraph_graph_fewshot/ragraph_utils/ToyGraphBase.py:135-138 (torch.normal(0, std, [B, J, D]) added to them).
+ *   out[b,j,d] = X[b,j,d] + std * z(seed[0], id(b), j, d): one multiply and one add, not contracted -- the bits of
+ *   ragraph_axpby_f32(X, 1, noise, 1) on a materialised noise = std * z.  z: Box-Muller on the two 24-bit halves (bits 63..40
+ *   -> u1 = (h + 1) / 2^24 in (0, 1], bits 39..16 -> u2 in [0, 1)) of draw j * ceil(D / 2) + d / 2 of the row; even d takes
+ *   sqrt(-2 ln u1) cos(2 pi u2), odd d the sine.  |z| <= sqrt(48 ln 2) ~ 5.77.  X may be NULL (zeros: out is the noise alone);
+ *   out may alias X. */
+int ragraph_noise_rows_i64(const int64_t* seed, const int64_t* row_ids, int64_t row_base, int64_t B, int m, int64_t N,
+                           int64_t* out, int64_t out_stride, void* stream);
+int ragraph_gather_reduce_noisy_f32(const float* V, int D, const float* L, int C, int64_t N, const int64_t* idx, int64_t B,
+                                    int k, int64_t idx_base, float v_scale, const int64_t* seed, const int64_t* row_ids,
+                                    int64_t row_base, int m, int64_t noise_n, const float* A, float wa, float wb, float* out,
+                                    float* mean_L, void* stream);
+int ragraph_add_normal_noise_f32(const float* X, int64_t B, int64_t J, int D, float std, const int64_t* seed,
+                                 const int64_t* row_ids, int64_t row_base, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,9 +71,10 @@ class RAGraph(nn.Module):
                 return sliced
         pretrain_embedddings = self.pretrain_model.inference(features, g)                      # RAGraph.py:40
         add_noise = self.training and self.noise_finetune
-        if add_noise and torch.cuda.is_current_stream_capturing():
+        if add_noise and getattr(tgb, "noise_rng", "host") != "device" and torch.cuda.is_current_stream_capturing():
             raise K.RagraphNativeError("noisy fine-tuning draws its noise on the host generator, as the reference does: "
-                                       "its step cannot be captured in a HIP graph (train it eagerly)")
+                                       "its step cannot be captured in a HIP graph (train it eagerly, or set "
+                                       "toy_graph_base.noise_rng = 'device')")
         queries = self._queries(pretrain_embedddings, g)
         # structure-aware retrieval: the query rows' position codes (ToyGraphBase.py:49-50 of the few-shot flavour); raises
         # here, before any retrieval kernel, when the bank holds no codes

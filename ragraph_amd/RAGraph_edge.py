@@ -240,13 +240,20 @@ class RAGraph(nn.Module):
                 total = A.axpby(total, 1 - self.retrieve_weight, rag, self.retrieve_weight)    # :328
                 return total.split([self.num_users, self.num_items], dim=0)
             _, idx = self._index.topk(queries, k)
-            if add_noise:
-                # (drawn from the default CPU generator as the reference does, :316; its per-slab draws of
-                # [batch, 1] concatenate to this one [n, 1] draw, so torch.manual_seed reproduces its rows)
-                noise = torch.randint(0, self.resource_values.shape[0], (idx.shape[0], self.noise_retrieve_num)
-                                      ).to(idx.device)
-                idx = torch.cat([idx, noise], dim=1)
-            rag, _ = K.gather_reduce(self.resource_values, None, idx, v_scale=1.0 / idx.shape[1])  # :314,321 mean
+            if add_noise and self.noise_rng == "device":
+                # the noise rows are made inside the reduction, keyed by the GLOBAL node id (a query shard's row b is node
+                # lo + b): no [n, 1] draw, no index matrix for them; the mean is over the k listed + the noise rows (:314,321)
+                m = self.noise_retrieve_num
+                rag, _ = K.gather_reduce_noisy(self.resource_values, None, idx, self._draw_noise_seed(), m,
+                                               row_base=lo if qs is not None else 0, v_scale=1.0 / (idx.shape[1] + m))
+            else:
+                if add_noise:
+                    # (drawn from the default CPU generator as the reference does, :316; its per-slab draws of
+                    # [batch, 1] concatenate to this one [n, 1] draw, so torch.manual_seed reproduces its rows)
+                    noise = torch.randint(0, self.resource_values.shape[0], (idx.shape[0], self.noise_retrieve_num)
+                                          ).to(idx.device)
+                    idx = torch.cat([idx, noise], dim=1)
+                rag, _ = K.gather_reduce(self.resource_values, None, idx, v_scale=1.0 / idx.shape[1])  # :314,321 mean
             if qs is not None:
                 rag = qs.gather_rows(rag, res[0].shape[0])
             total = A.axpby(total, 1 - self.retrieve_weight, rag, self.retrieve_weight)        # :328
@@ -308,11 +315,18 @@ class RAGraph(nn.Module):
                 rag = K.retrieve_mean_large_k(queries, self.keys_normalized, self.resource_values, k)
             else:
                 _, idx = self._index.topk(queries, k)
-                if add_noise:
-                    # (the one [n, 1] draw of forward, indexed by the rows: the same seed gives a row the same noise)
-                    noise = torch.randint(0, self.resource_values.shape[0], (n, self.noise_retrieve_num)).to(idx.device)
-                    idx = torch.cat([idx, noise[rows]], dim=1)
-                rag, _ = K.gather_reduce(self.resource_values, None, idx, v_scale=1.0 / idx.shape[1])  # :314,321 mean
+                if add_noise and self.noise_rng == "device":
+                    # (forward's noise is keyed by the node id: the distinct rows ARE the keys -- the same seed gives a row
+                    # the same noise, and only the rows asked for draw any)
+                    m = self.noise_retrieve_num
+                    rag, _ = K.gather_reduce_noisy(self.resource_values, None, idx, self._draw_noise_seed(), m, row_ids=rows,
+                                                   v_scale=1.0 / (idx.shape[1] + m))
+                else:
+                    if add_noise:
+                        # (the one [n, 1] draw of forward, indexed by the rows: the same seed gives a row the same noise)
+                        noise = torch.randint(0, self.resource_values.shape[0], (n, self.noise_retrieve_num)).to(idx.device)
+                        idx = torch.cat([idx, noise[rows]], dim=1)
+                    rag, _ = K.gather_reduce(self.resource_values, None, idx, v_scale=1.0 / idx.shape[1])  # :314,321 mean
             total = A.axpby(total, 1 - self.retrieve_weight, rag, self.retrieve_weight)        # :328
         out = A.gather_rows(total, inv)
         return out[:user_rows.numel()], out[user_rows.numel():]
@@ -330,6 +344,19 @@ class RAGraph(nn.Module):
                            # reference for the same seed, at the cost of one uniform per edge on the host and a copy per step
                            # (44 M edges: ~0.3 s of a 1-s step at c5, bench `finetune_step.edge_c5.host_mask_draw_ms`);
                            # "device": torch.rand on the device generator (another stream of random numbers, same law)
+
+    noise_rng = K.NoiseRng()   # "host" (the default) | "device".
+                           # "host": the reference's draw of the noise rows (torch.randint on the CPU generator, :316-318: one
+                           # index per NODE and a copy per noisy step, also when forward_rows reads a few thousand of them);
+                           # "device": one seed per noisy forward, drawn on the device generator and kept in `last_noise_seed`
+                           # (never read back), the noise rows a hash of (seed, node id, draw) made inside
+                           # K.gather_reduce_noisy -- another stream of random numbers, same law; forward and forward_rows
+                           # still give a node the same noise under one torch.manual_seed
+    last_noise_seed = None
+
+    def _draw_noise_seed(self):
+        self.last_noise_seed = K.draw_noise_seed(self.edges.device)
+        return self.last_noise_seed
 
     loss_rows = "batch"    # "batch": cal_loss computes the rows the loss reads -- the batch's users, positives and negatives --
                            # through forward_rows: the same loss bits, gradients within rounding (two sums associate

@@ -77,7 +77,8 @@ class ToyGraphBaseFewShot(ToyGraphBase):
         s_sem = K.linear(K.normalize_rows(search_keys), self.keys_normalized)
         return K.axpby(s_struct, self.structure_weight, s_sem, self.semantic_weight)
 
-    def retrieve(self, search_keys, search_adj, add_noise: bool, anchors=None):
+    def retrieve(self, search_keys, search_adj, add_noise: bool, anchors=None, row_ids=None, row_base: int = 0):
+        """`row_ids` / `row_base`: the keys of the noise rows with noise_rng = "device" (ToyGraphBase.retrieve_indices)."""
         retrieve_num = 2 * self.retrieve_num if add_noise else self.retrieve_num
         if self.structure_weight != 0:   # :49-64 in one call, no [B, N] matrix in this module
             pos = self.search_positions(search_adj, None, anchors)
@@ -87,15 +88,21 @@ class ToyGraphBaseFewShot(ToyGraphBase):
         rag_embeddings = K.gather_rows(self.resource_values, idx)
         rag_labels = K.gather_rows(self.resource_labels, idx)
         if add_noise:                                                                # :70-76
-            noise_idx = torch.randint(0, self.resource_values.shape[0], (idx.shape[0], self.noise_retrieve_num),
-                                      device=idx.device)
+            if self.noise_rng == "device":
+                noise_idx = K.noise_rows(self._draw_noise_seed(), idx.shape[0], self.noise_retrieve_num,
+                                         self.resource_values.shape[0], row_ids, row_base)
+            else:
+                noise_idx = torch.randint(0, self.resource_values.shape[0], (idx.shape[0], self.noise_retrieve_num),
+                                          device=idx.device)
             rag_embeddings = torch.cat([rag_embeddings, K.gather_rows(self.resource_values, noise_idx)], dim=1)
             rag_labels = torch.cat([rag_labels, K.gather_rows(self.resource_labels, noise_idx)], dim=1)
         return rag_embeddings, rag_labels
 
 
-def _reject_noise_under_capture(add_noise: bool):
-    if add_noise and torch.cuda.is_current_stream_capturing():
+def _reject_noise_under_capture(add_noise: bool, noise_rng: str = "host"):
+    """noise_rng = "device" (ToyGraphBase.noise_rng): the noise is made inside the kernels from a seed drawn on the device
+    generator, which a capture records -- nothing to reject."""
+    if add_noise and noise_rng != "device" and torch.cuda.is_current_stream_capturing():
         raise K.RagraphNativeError("noisy fine-tuning draws new noise rows every step (on the host generator in the graph "
                                    "flavour, as the reference does): its step is not captured in a HIP graph (train it eagerly)")
 
@@ -125,7 +132,7 @@ class RAGraph(nn.Module):
         g = as_csr(adj)
         emb = self.pretrain_model.encode(features, g)                                           # :48
         add_noise = self.training and self.noise_finetune
-        _reject_noise_under_capture(add_noise)
+        _reject_noise_under_capture(add_noise, self.toy_graph_base.noise_rng)
         if anchors is None and torch.cuda.is_current_stream_capturing():
             raise K.RagraphNativeError("RAGraph_fewshot.RAGraph: pass `anchors` to a captured forward (drawn on the host "
                                        "generator otherwise: PositionAwareEncoder.py:11)")
@@ -178,7 +185,7 @@ class RAGraphGraphFewShot(nn.Module):
         tgb = self.toy_graph_base
         emb = self.pretrain_model.encode(features, g)                                            # :47
         add_noise = self.training and self.noise_finetune
-        _reject_noise_under_capture(add_noise)
+        _reject_noise_under_capture(add_noise, self.toy_graph_base.noise_rng)
         idx = tgb.retrieve_indices(emb, add_noise)                                               # :51 (k' = 2k with noise)
         k = idx.shape[1]
         label_ids = torch.argmax(K.gather_rows(tgb.resource_labels, idx), dim=-1)                # :55 (integer lookup)

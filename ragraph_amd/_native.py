@@ -152,6 +152,10 @@ SIGNATURES = {
     "ragraph_lp_combine_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _i64, _i32, _vp, _vp]),
     "ragraph_edge_hist_check_i64": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
     "ragraph_edge_neg_sample_i64": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "ragraph_noise_rows_i64": (_i32, [_vp, _vp, _i64, _i64, _i32, _i64, _vp, _i64, _vp]),
+    "ragraph_gather_reduce_noisy_f32": (_i32, [_vp, _i32, _vp, _i32, _i64, _vp, _i64, _i32, _i64, _f32, _vp, _vp, _i64, _i32, _i64,
+                                               _vp, _f32, _f32, _vp, _vp, _vp]),
+    "ragraph_add_normal_noise_f32": (_i32, [_vp, _i64, _i64, _i32, _f32, _vp, _vp, _i64, _vp, _vp]),
 }
 
 

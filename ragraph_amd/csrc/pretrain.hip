@@ -19,24 +19,14 @@
 //     item outside the history by the binary search of the LP sampler.  No read-back unless the caller asks for the user
 //     ids to be checked.
 #include "common.h"
+#include "rng.h"
 
 namespace ragraph {
 
 constexpr int LP_NEG_MAX = 4096;          // negatives per row (ranks kept in LDS)
 constexpr float LP_COS_EPS = 1e-8f;       // F.cosine_similarity's default eps
 
-// ---- randomness: splitmix64 on (seed, row, draw) ----------------------------------------------------------------------
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-__device__ __forceinline__ uint64_t lp_draw(uint64_t seed, uint64_t row, uint64_t draw) {
-  return splitmix64(splitmix64(seed ^ splitmix64(row)) + draw);
-}
-// uniform in [0, m) (the high half of the 128-bit product; bias < m / 2^64)
-__device__ __forceinline__ uint64_t lp_below(uint64_t h, uint64_t m) { return __umul64hi(h, m); }
+// (randomness: splitmix64 on (seed, row, draw) -- lp_draw / lp_below, rng.h)
 
 // rank r -> the r-th id that is not in the strictly ascending list at(0) .. at(deg - 1): r + #{j : at(j) - j <= r}
 // (at(j) - j never decreases, so a binary search counts them)

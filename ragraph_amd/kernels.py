@@ -1626,3 +1626,115 @@ def edge_neg_sample(rowptr: torch.Tensor, items: torch.Tensor, num_items: int, u
                                           sd.data_ptr(), out.data_ptr() if B else None, _ptr(ws),
                                           ws.numel() if ws is not None else 0, _stream()), "edge_neg_sample")
     return out
+
+
+# ---- noisy fine-tuning with the noise drawn on the device (csrc/noise.hip) ---------------------------------------------
+def _noise_keys(seed: torch.Tensor, row_ids, B: int, what: str):
+    sd = _idxc(seed, f"{what}.seed")
+    if sd.numel() != 1:
+        raise RagraphNativeError(f"{what}: seed must hold one int64, got {tuple(sd.shape)}")
+    if row_ids is not None:
+        row_ids = _idxc(row_ids, f"{what}.row_ids").reshape(-1)
+        if row_ids.numel() != B:
+            raise RagraphNativeError(f"{what}: {row_ids.numel()} row ids for {B} rows")
+    return sd, row_ids
+
+
+def noise_rows(seed: torch.Tensor, B: int, m: int, n: int, row_ids: torch.Tensor | None = None, row_base: int = 0,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """int64 [B, m]: m rows of a bank of n per query, slot (b, j) the hash of (seed[0], row id of b, j) reduced to [0, n)
+    (ragraph_noise_rows_i64) -- what torch.randint(0, n, (B, m)) is to the reference's noisy retrieval.  `seed` is a
+    one-element int64 device tensor (read on the device).  row_ids: the queries' ids, int64 [B] on the device; without them
+    row b has the id row_base + b.  out: an int64 [B, m] view to fill in place -- contiguous, or columns of a wider
+    contiguous matrix (the tail columns of a [B, k + m] index matrix)."""
+    L = _ready()
+    B, m = int(B), int(m)
+    sd, row_ids = _noise_keys(seed, row_ids, B, "noise_rows")
+    if out is None:
+        out = torch.empty((B, max(m, 0)), dtype=torch.int64, device=sd.device)
+        stride = m
+    else:
+        if (not out.is_cuda or out.dtype != torch.int64 or tuple(out.shape) != (B, m) or (m > 1 and out.stride(1) != 1)
+                or (B > 1 and out.stride(0) < m)):
+            raise RagraphNativeError(f"noise_rows: out must be an int64 device view [{B}, {m}] with unit column stride")
+        stride = out.stride(0) if B > 1 else m
+    N.check(L.ragraph_noise_rows_i64(sd.data_ptr(), _ptr(row_ids), int(row_base), B, m, int(n), out.data_ptr() if B else None,
+                                     stride, _stream()), "noise_rows")
+    return out
+
+
+def gather_reduce_noisy(v: torch.Tensor, labels: torch.Tensor | None, idx: torch.Tensor, seed: torch.Tensor, m: int,
+                        noise_n: int | None = None, row_ids: torch.Tensor | None = None, row_base: int = 0, idx_base: int = 0,
+                        v_scale: float = 1.0, mix=None):
+    """gather_reduce over idx [B, k] AND m noise rows per query behind them, with no index matrix for the noise: the bits of
+    gather_reduce(v, labels, cat(idx, noise_rows(seed, B, m, noise_n, row_ids, row_base)), idx_base, v_scale); the label
+    means are over k + m rows.  noise_n: the range of the draw (the whole bank; v.shape[0] when v is the whole bank).
+    mix = (a, wa, wb): a * wa + (v_scale * sum) * wb instead of the sum, as gather_reduce_mix."""
+    L = _ready()
+    v = _f32c(v, "gather_reduce_noisy.v")
+    idx = _idxc(idx, "gather_reduce_noisy.idx")
+    B, k = idx.shape
+    sd, row_ids = _noise_keys(seed, row_ids, B, "gather_reduce_noisy")
+    a, wa, wb = None, 0.0, 0.0
+    if mix is not None:
+        a, wa, wb = mix
+        a = _f32c(a, "gather_reduce_noisy.a")
+        if tuple(a.shape) != (B, v.shape[1]):
+            raise RagraphNativeError(f"gather_reduce_noisy: a is {tuple(a.shape)}, the reduction [{B}, {v.shape[1]}]")
+    out = torch.empty((B, v.shape[1]), dtype=torch.float32, device=v.device)
+    mean_l = None
+    C = 0
+    if labels is not None:
+        labels = _f32c(labels, "gather_reduce_noisy.labels")
+        C = labels.shape[1]
+        mean_l = torch.empty((B, C), dtype=torch.float32, device=v.device)
+    N.check(L.ragraph_gather_reduce_noisy_f32(v.data_ptr(), v.shape[1], _ptr(labels), C, v.shape[0], idx.data_ptr(), B, k,
+                                              int(idx_base), float(v_scale), sd.data_ptr(), _ptr(row_ids), int(row_base), int(m),
+                                              int(v.shape[0] if noise_n is None else noise_n), _ptr(a), float(wa), float(wb),
+                                              out.data_ptr(), _ptr(mean_l), _stream()), "gather_reduce_noisy")
+    return out, mean_l
+
+
+def add_normal_noise(x: torch.Tensor | None, std: float, seed: torch.Tensor, row_ids: torch.Tensor | None = None,
+                     row_base: int = 0, shape=None) -> torch.Tensor:
+    """x + std * z for x [B, J, D] (or [B, D]: J = 1), z standard normal by Box-Muller on the hash of (seed[0], row id of b,
+    j, d) (ragraph_add_normal_noise_f32) -- what adding torch.normal(0, std, x.shape) is to the reference's graph flavours.
+    x = None with shape = (B, J, D): the noise alone."""
+    L = _ready()
+    if x is None:
+        if shape is None:
+            raise RagraphNativeError("add_normal_noise: x or shape")
+        shape = tuple(int(s) for s in shape)
+    else:
+        x = _f32c(x, "add_normal_noise.x")
+        shape = tuple(x.shape)
+    if len(shape) not in (2, 3):
+        raise RagraphNativeError(f"add_normal_noise: [B, J, D] or [B, D], got {shape}")
+    B, J, D = (shape[0], 1, shape[1]) if len(shape) == 2 else shape
+    sd, row_ids = _noise_keys(seed, row_ids, B, "add_normal_noise")
+    out = torch.empty(shape, dtype=torch.float32, device=sd.device)
+    N.check(L.ragraph_add_normal_noise_f32(_ptr(x), B, J, D, float(std), sd.data_ptr(), _ptr(row_ids), int(row_base),
+                                           out.data_ptr() if out.numel() else None, _stream()), "add_normal_noise")
+    return out
+
+
+def draw_noise_seed(device) -> torch.Tensor:
+    """One int64 on the device generator (torch.manual_seed reproduces it; capturable: the generator's state is the graph's)."""
+    return torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=device)
+
+
+def check_noise_rng(value: str) -> str:
+    if value not in ("host", "device"):
+        raise ValueError(f"noise_rng: 'host' or 'device', not {value!r}")
+    return value
+
+
+class NoiseRng:
+    """The `noise_rng` attribute of the retrieval classes: "host" unless an instance sets it; a value other than "host" or
+    "device" raises ValueError where it is set."""
+
+    def __get__(self, obj, owner=None):
+        return "host" if obj is None else obj.__dict__.get("_noise_rng", "host")
+
+    def __set__(self, obj, value):
+        obj.__dict__["_noise_rng"] = check_noise_rng(value)

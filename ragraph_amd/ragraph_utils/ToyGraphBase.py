@@ -41,6 +41,21 @@ class _Bank:
 
 
 class ToyGraphBase:
+    noise_rng = K.NoiseRng()   # "host" (the default) | "device".
+                           # "host": the reference's draws (torch.randint / torch.normal on the CPU generator, then a copy to the
+                           # device) -- the same noise as the reference for the same seed, at the cost of host work on every
+                           # noisy step, which a stream capture cannot record; "device": one seed per noisy call, drawn on the
+                           # device generator and kept in `last_noise_seed` (a device tensor, never read back), and noise that is
+                           # a hash of (seed, query row, draw) made inside the kernels (K.noise_rows, K.gather_reduce_noisy,
+                           # K.add_normal_noise: another stream of random numbers, same law) -- no host work, capturable,
+                           # reproduced by torch.manual_seed
+    last_noise_seed = None
+
+    def _draw_noise_seed(self) -> Tensor:
+        """The seed of this noisy call ("device" mode)."""
+        self.last_noise_seed = K.draw_noise_seed(self.device)
+        return self.last_noise_seed
+
     def __init__(self, pretrain_model, num_class, emb_size, query_graph_hop, device="cuda", flavour="node") -> None:
         self.flavour = flavour
         if flavour == "node":   # RAGraph_node/ragraph_utils/ToyGraphBase.py:18-29
@@ -178,44 +193,66 @@ class ToyGraphBase:
         return self._index.topk(q, k)  # fp32 streaming / tile kernel or, for large batches, the bf16-filtered exact path
 
     def retrieve_indices(self, search_keys: Tensor, add_noise: bool, search_adj=None,
-                         search_positions: Tensor | None = None, anchors: Tensor | None = None) -> Tensor:
+                         search_positions: Tensor | None = None, anchors: Tensor | None = None,
+                         row_ids: Tensor | None = None, row_base: int = 0) -> Tensor:
         """The rows retrieve() gathers: the top-k' indices (k' = 2 * retrieve_num with add_noise, :66) and, in the node
         flavour with add_noise, noise_retrieve_num uniformly random rows behind them (:73-79).  The reference draws the
         noise from torch's default CPU generator (no device argument) and only then moves it to the bank's device: drawn
-        the same way here, so torch.manual_seed reproduces the reference's rows."""
+        the same way here, so torch.manual_seed reproduces the reference's rows.  With noise_rng = "device" the noise columns
+        are K.noise_rows of a fresh seed (last_noise_seed), keyed by the query's row in the call -- or by `row_ids` /
+        `row_base + b` when the caller holds a slice of a larger batch -- written into the tail of one [B, k' + m] matrix."""
         retrieve_num = 2 * self.retrieve_num if add_noise else self.retrieve_num
         pos = self.search_positions(search_adj, search_positions, anchors)         # (None unless structure_weight != 0)
         _, idx = self.topk(search_keys, retrieve_num, pos)                         # :66-67
+        if add_noise and self.flavour == "node" and self.noise_rng == "device":
+            B, k, m = idx.shape[0], idx.shape[1], self.noise_retrieve_num
+            full = torch.empty((B, k + m), dtype=torch.int64, device=idx.device)
+            full[:, :k] = idx
+            K.noise_rows(self._draw_noise_seed(), B, m, self.resource_values.shape[0], row_ids, row_base, out=full[:, k:])
+            return full
         if add_noise and self.flavour == "node":
             noise_idx = torch.randint(0, self.resource_values.shape[0], (idx.shape[0], self.noise_retrieve_num))
             idx = torch.cat([idx, noise_idx.to(idx.device)], dim=1)
         return idx
 
     def retrieve(self, search_keys: Tensor, search_adj, add_noise: bool, idx: Tensor | None = None,
-                 search_positions: Tensor | None = None, anchors: Tensor | None = None):
+                 search_positions: Tensor | None = None, anchors: Tensor | None = None,
+                 row_ids: Tensor | None = None, row_base: int = 0):
         """ToyGraphBase.py:47-81 -> (rag_embeddings [B,k',D], rag_labels [B,k',C]).  A 1-D query (graph flavour,
         RAGraph_graph/ragraph_utils/ToyGraphBase.py:56-87) gives B = 1.  `idx`: the rows, when the caller already
         holds retrieve_indices(search_keys, add_noise) (one top-k per forward instead of two).  `search_adj` (the query
-        graph), or ready `search_positions`, and `anchors` matter only with structure_weight != 0."""
+        graph), or ready `search_positions`, and `anchors` matter only with structure_weight != 0; `row_ids` / `row_base` key the
+        noise of noise_rng = "device" (see retrieve_indices)."""
         if idx is None:
-            idx = self.retrieve_indices(search_keys, add_noise, search_adj, search_positions, anchors)
+            idx = self.retrieve_indices(search_keys, add_noise, search_adj, search_positions, anchors, row_ids, row_base)
         rag_embeddings = K.gather_rows(self.resource_values, idx)                  # :70 (+ :76,78 noise rows)
         rag_labels = K.gather_rows(self.resource_labels, idx)                      # :71 (+ :77,79)
-        if add_noise and self.flavour != "node":                                   # graph :84-85,131-134
+        if add_noise and self.flavour != "node" and self.noise_rng == "device":    # graph :84-85,131-134, drawn in the kernel
+            rag_embeddings = K.add_normal_noise(rag_embeddings, self.noise_std, self._draw_noise_seed(), row_ids, row_base)
+        elif add_noise and self.flavour != "node":                                 # graph :84-85,131-134
             noise = torch.normal(mean=0, std=self.noise_std, size=rag_embeddings.shape).to(rag_embeddings.device)
             rag_embeddings = K.axpby(rag_embeddings, 1.0, noise, 1.0)
         return rag_embeddings, rag_labels
 
     def retrieve_reduced_noisy(self, search_keys: Tensor, idx: Tensor | None = None, want_labels: bool = True,
-                               search_adj=None, search_positions: Tensor | None = None, anchors: Tensor | None = None):
+                               search_adj=None, search_positions: Tensor | None = None, anchors: Tensor | None = None,
+                               row_ids: Tensor | None = None, row_base: int = 0):
         """What RAGraph.forward consumes in noisy fine-tuning (RAGraph.py:42-49 with add_noise): (sum_k' V, mean_k' L)
         over the top-2k rows plus the noise -- every reduction on the HIP kernels, ONE top-k per call (`idx`: the rows
-        when the caller already holds retrieve_indices(search_keys, True); want_labels=False skips the label means)."""
+        when the caller already holds retrieve_indices(search_keys, True); want_labels=False skips the label means).
+        Node flavour with noise_rng = "device" and no `idx`: the top-2k list alone goes into K.gather_reduce_noisy, which
+        computes the noise rows itself -- the bits of the reduction over retrieve_indices' matrix for the same seed."""
+        if idx is None and self.flavour == "node" and self.noise_rng == "device":
+            pos = self.search_positions(search_adj, search_positions, anchors)
+            _, top = self.topk(search_keys, 2 * self.retrieve_num, pos)
+            return K.gather_reduce_noisy(self.resource_values, self.resource_labels if want_labels else None, top,
+                                         self._draw_noise_seed(), self.noise_retrieve_num, row_ids=row_ids, row_base=row_base)
         if idx is None:
-            idx = self.retrieve_indices(search_keys, True, search_adj, search_positions, anchors)
+            idx = self.retrieve_indices(search_keys, True, search_adj, search_positions, anchors, row_ids, row_base)
         if self.flavour == "node":   # noise = extra rows: still a gather-reduce over an index matrix
             return K.gather_reduce(self.resource_values, self.resource_labels, idx)
-        rag_embeddings, _ = self.retrieve(search_keys, None, True, idx=idx)   # noise is added to the gathered embeddings
+        rag_embeddings, _ = self.retrieve(search_keys, None, True, idx=idx, row_ids=row_ids, row_base=row_base)   # noise is
+        # added to the gathered embeddings
         B, k, D = rag_embeddings.shape
         seg = torch.arange(0, B * k + 1, k, dtype=torch.int64, device=rag_embeddings.device)
         sum_v = K.segment_reduce(rag_embeddings.reshape(B * k, D), seg)
