@@ -12,7 +12,10 @@ ships no dataset and no pre-trained weights, .MISSING_LARGE_BLOBS).  Same steps,
 --pretrained PATH loads a state dict that examples/pretrain.py wrote (the reference's modelset/model_<ds>.pkl) into the
 encoder before the bank is built; without it the encoder keeps its random initialisation.
 
-Usage: python examples/finetune_rag.py [--epochs 5] [--graphs 120] [--pretrained modelset/model_SYNTH.pkl]
+--build-rng device draws the augmentation and the inverse-importance sampling of both bank builds (:57 and :97) inside the
+library's kernels (ToyGraphBase.build_rng); the default, host, keeps torch's draws.
+
+Usage: python examples/finetune_rag.py [--epochs 5] [--graphs 120] [--pretrained modelset/model_SYNTH.pkl] [--build-rng device]
 """
 import argparse
 import os
@@ -33,6 +36,8 @@ def main():
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--graphs", type=int, default=120)
     ap.add_argument("--pretrained", default=None, help="state dict written by examples/pretrain.py")
+    ap.add_argument("--build-rng", choices=("host", "device"), default="host",
+                    help="where bank construction makes its draws (default: host, torch's generators)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     seed_everything(0)
@@ -45,7 +50,8 @@ def main():
     if args.pretrained:
         pretrain_model.load_state_dict(torch.load(args.pretrained, map_location=dev))
     t0 = time.perf_counter()
-    rag_model = RAGraph(pretrain_model, train_ds, F_attr, C, 256, finetune=True, noise_finetune=False, device=dev)
+    rag_model = RAGraph(pretrain_model, train_ds, F_attr, C, 256, finetune=True, noise_finetune=False, device=dev,
+                        build_rng=args.build_rng)
     torch.cuda.synchronize()
     rag_model.toy_graph_base.show()
     print(f"bank build: {time.perf_counter() - t0:.2f} s for {len(train_ds)} resource graphs")

@@ -873,6 +873,66 @@ int ragraph_gather_reduce_noisy_f32(const float* V, int D, const float* L, int C
 int ragraph_add_normal_noise_f32(const float* X, int64_t B, int64_t J, int D, float std, const int64_t* seed,
                                  const int64_t* row_ids, int64_t row_base, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * BR  bank construction, the stochastic half drawn on the device (csrc/bank.hip; build_rng = "device")
+ *
+ * Augmentation.augment_features / augment_adj (RAGraph_node/ragraph_utils/Augmentation.py:8-29), torch.multinomial
+ * (RAGraph_node/ragraph_utils/ToyGraphBase.py:98, RAGraph_edge/modules/RAGraph.py:213) and adj[pick][:, pick]
+ * (ToyGraphBase.py:100), which the reference draws from torch's generator per 40-node graph.  Conventions of all five entries:
+ * a seed is a one-element int64 DEVICE pointer, read on the device; every uniform is u53(w) = (double)(w >> 11) * 2^-53 of one
+ * lp_draw word w (the hash of NZ above); an event of probability t (a float) happens iff u53(w) < (double)t (53 bits: a 24-bit
+ * uniform cannot represent the edge flavour's p * 0.01 ~ 2e-9; a NaN t never happens); scratch comes from the caller; a bad
+ * argument returns RAGRAPH_EINVAL before anything is written.  Other streams of the reference's laws, not torch's streams.
+ *
+ * ragraph_edge_rewrite_csr: Augmentation.augment_adj (Augmentation.py:23-29) for a block-diagonal batch -- graph g holds the
+ *   nodes [graph_ptr[g], graph_ptr[g+1]) of n (graph_ptr int64 [G+1], ascending, from 0 to n).  Slot (i, j) of graph g (i a
+ *   global row, j a LOCAL column) is kept iff u53(lp_draw(seed[0], i, j)) < __fmul_rn(__fadd_rn(p_i, p_j), 0.5f), the diagonal
+ *   included as in the reference.  The result is a CSR over the n nodes: rowptr int64 [n+1], col int32 GLOBAL columns ascending
+ *   per row, val 1.0.  Two calls, because only the first knows how many slots are kept:
+ *     col == NULL (and val == NULL): the count pass -- counts per row, the library's scan, rowptr [n+1], status[0] = the kept
+ *       total, status[1] = 1 when that total is 2^31 or more (rowptr and status[0] are then meaningless: the caller reports
+ *       an error, nothing wraps silently), else 0.  The caller reads status back (one synchronisation) and sizes col / val;
+ *     col != NULL: the fill pass -- the same hashes again, columns and values written behind the rowptr of the count pass
+ *       (same seed, prob and graph_ptr).  capacity: the entries col / val hold; no slot at or behind it is written.
+ *   No buffer is proportional to the node pairs: workspace 4 (n + 1) bytes + the scan's.  1 <= n < 2^31 - 1, G >= 1.
+ *
+ * ragraph_multinomial_segments_i64: torch.multinomial(prob, S, replacement=True) for each segment [seg_ptr[g], seg_ptr[g+1])
+ *   of prob [n].  Integer weights w_i = (uint64)((double)min(p_i, 1) * 2^40), 0 for a negative or NaN p_i: prefix sums are exact
+ *   and independent of the scan's shape.  Draw (g, s): t = lp_below(lp_draw(seed[0], g, s), W_g), W_g = the segment's weights;
+ *   out[g * S + s] = seg_ptr[g] + the smallest i whose inclusive prefix exceeds t -- an entry of weight 0 is never returned; a
+ *   segment with W_g = 0 (or empty) gives -1.  One block-sum level (tiles of 64 entries) serves tens of thousands of 30-node
+ *   segments and one segment of millions alike.  1 <= n < 2^23 (so every segment is shorter than 2^23 and W_g < 2^63).
+ *
+ * ragraph_csr_induced_blocks_f32: adj[pick_g][:, pick_g] (ToyGraphBase.py:100): a CSR over n nodes (columns ascending per row,
+ *   nnz entries) and pick int64 [G, S] global ids, repeats allowed -> out [G, S, S], out[g, a, b] = adj[pick[g,a], pick[g,b]]
+ *   (the first such entry of the row; 0 when there is none).  A pick outside [0, n) gives zeros.
+ *
+ * ragraph_blocks_to_csr_f32: blocks [G, S, S], S <= 64 -> the block-diagonal CSR over G * S rows: rowptr int64 [G*S+1], col
+ *   int32 (g * S + b, ascending), val -- count, scan, fill in one call; an entry is kept iff it compares unequal to 0.  col and
+ *   val hold G * S * S entries; nnz[0] = the entries written (the only thing a caller reads back).  G * S * S < 2^31.
+ *
+ * ragraph_augment_features_f32: Augmentation.augment_features (Augmentation.py:8-22; rate 0.01, std 0.1 in the reference) on X
+ *   [n, D] with prob [n]: row i, of id id_i = row_ids[i] (or row_base + i when row_ids is NULL), is kept iff
+ *   u53(lp_draw(seed_drop[0], id_i, 0)) < __fmul_rn(p_i, rate).  A kept row is __fadd_rn(x, __fmul_rn(std, z)), z from
+ *   normal_pair(seed_noise[0], id_i, d / 2): the bits of ragraph_add_normal_noise_f32 on that row (J = 1).  A dropped row is +0
+ *   in EVERY column -- the reference's `noisy * 0` leaves the noisy value's sign on its zeros; here the sign is always plus --
+ *   and no normal is computed for it (at the reference's rate that is nearly every row).  out may alias X. */
+size_t ragraph_edge_rewrite_workspace_bytes(int64_t n);
+int ragraph_edge_rewrite_csr(const int64_t* seed, const float* prob, const int64_t* graph_ptr, int64_t G, int64_t n,
+                             int64_t* rowptr, int64_t* status, int32_t* col, float* val, int64_t capacity, void* ws,
+                             size_t ws_bytes, void* stream);
+size_t ragraph_multinomial_segments_workspace_bytes(int64_t n);
+int ragraph_multinomial_segments_i64(const int64_t* seed, const float* prob, int64_t n, const int64_t* seg_ptr, int64_t G, int S,
+                                     int64_t* out, void* ws, size_t ws_bytes, void* stream);
+int ragraph_csr_induced_blocks_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n, int64_t nnz,
+                                   const int64_t* pick, int64_t G, int S, float* out, void* stream);
+size_t ragraph_blocks_to_csr_workspace_bytes(int64_t G, int S);
+int ragraph_blocks_to_csr_f32(const float* blocks, int64_t G, int S, int64_t* rowptr, int32_t* col, float* val, int64_t* nnz,
+                              void* ws, size_t ws_bytes, void* stream);
+int ragraph_augment_features_f32(const float* X, int64_t n, int D, const float* prob, float rate, float std,
+                                 const int64_t* seed_drop, const int64_t* seed_noise, const int64_t* row_ids, int64_t row_base,
+                                 float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

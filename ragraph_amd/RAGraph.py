@@ -20,7 +20,7 @@ class RAGraph(nn.Module):
     flavour = "node"
 
     def __init__(self, pretrain_model, resource_dataset, feture_size, num_class, emb_size, finetune=True,
-                 noise_finetune=False, device="cuda") -> None:
+                 noise_finetune=False, device="cuda", build_rng="host") -> None:
         super().__init__()
         self.emb_size = emb_size
         self.num_class = num_class
@@ -32,6 +32,7 @@ class RAGraph(nn.Module):
             assert self.finetune
         self.toy_graph_base = ToyGraphBase(pretrain_model, num_class, emb_size, self.query_graph_hop, device=device,
                                            flavour=self.flavour)
+        self.toy_graph_base.build_rng = build_rng   # "host" | "device": where the bank's draws are made (ToyGraphBase.build_rng)
         if resource_dataset is not None:
             self.toy_graph_base.build_toy_graph(resource_dataset)
         if self.finetune:

@@ -19,7 +19,7 @@ from .graph import CSRGraph
 class RAGraph(nn.Module):
     def __init__(self, dataset, pretrained_model=None, phase="finetune", use_RAG=True, use_noise=False,
                  use_LoRA=False, LoRA_rank=16, emb_size=64, num_layers=3, retrieve_num=10, retrieve_weight=0.3,
-                 batch_size=4096, device="cuda", num_augment_scale=0, num_inverse_sample=0):
+                 batch_size=4096, device="cuda", num_augment_scale=0, num_inverse_sample=0, build_rng="host"):
         """dataset: .num_users, .num_items, .edges [2E,2] int64 (src,dst, both directions), .edge_norm [2E] fp32,
         .edge_times [2E] int64 (the tensors modules/RAGraph.py:22-27 derives from the scipy graph).
         pretrained_model: .generate() -> (user_emb, item_emb); not used (may be None) in the phases "pretrain" and
@@ -41,6 +41,7 @@ class RAGraph(nn.Module):
         # bank construction (modules/RAGraph.py:38-44,56-62): the vanilla phase keeps an inverse-importance SAMPLE of the
         # nodes (round(0.01 n) draws) of the original and of num_augment_scale feature-augmented copies
         self.num_augment_scale, self.num_inverse_sample = num_augment_scale, num_inverse_sample
+        self.build_rng = build_rng   # "host" | "device": where _sample_bank makes its draws
         self.resource_keys = self.resource_values = None
         self._keys_normalized = self._index = None
         self._csr_cache = None
@@ -174,6 +175,8 @@ class RAGraph(nn.Module):
         (Augmentation.augment_features, modules/ragraph_utils/Augmentation.py:8-22), each cut down to num_inverse_sample
         rows drawn with replacement by inverse importance.  The draws come from torch's RNG (as the reference's)."""
         prob = self.sample_prob()                                                  # :201
+        if self.build_rng == "device":
+            return self._sample_bank_device(all_emb, all_logits, prob)
         keys_out, vals_out = [], []
         for i in range(1 + self.num_augment_scale):                                # :203-204
             k, v = all_emb, all_logits
@@ -188,6 +191,31 @@ class RAGraph(nn.Module):
             keys_out.append(k)
             vals_out.append(v)
         return torch.cat(keys_out, 0), torch.cat(vals_out, 0)                      # :220-226
+
+    def _sample_bank_device(self, all_emb, all_logits, prob):
+        """_sample_bank with build_rng = "device": per pass the rows are picked first (one segment over all nodes), the picked
+        rows of keys and of values gathered, and only those augmented, keyed by the NODE (row_ids = pick): a node drawn twice
+        carries one noise and one fate, as in the reference, where the whole table is augmented before the pick.  Keys and
+        values use different seed columns (the reference draws their noise and masks separately)."""
+        n = all_emb.shape[0]
+        S = self.num_inverse_sample
+        self.last_build_seed = seeds = K.draw_build_seeds(1 + self.num_augment_scale, all_emb.device)
+        whole = torch.tensor([0, n], dtype=torch.int64, device=all_emb.device)
+        keys_out, vals_out = [], []
+        for i in range(1 + self.num_augment_scale):
+            sd = seeds[i]
+            pick = K.multinomial_segments(prob, whole, S, sd[K.BUILD_SEED_PICK:K.BUILD_SEED_PICK + 1]).reshape(-1) if S > 0 else None
+            k = K.gather_rows(all_emb, pick) if S > 0 else all_emb
+            v = K.gather_rows(all_logits, pick) if S > 0 else all_logits
+            if i > 0:
+                p = K.gather_rows(prob.reshape(-1, 1), pick).reshape(-1) if S > 0 else prob
+                k = K.augment_features(k, p, sd[K.BUILD_SEED_NODE_DROP:K.BUILD_SEED_NODE_DROP + 1],
+                                       sd[K.BUILD_SEED_FEATURE_NOISE:K.BUILD_SEED_FEATURE_NOISE + 1], row_ids=pick)
+                v = K.augment_features(v, p, sd[K.BUILD_SEED_VALUE_DROP:K.BUILD_SEED_VALUE_DROP + 1],
+                                       sd[K.BUILD_SEED_VALUE_NOISE:K.BUILD_SEED_VALUE_NOISE + 1], row_ids=pick)
+            keys_out.append(k)
+            vals_out.append(v)
+        return torch.cat(keys_out, 0), torch.cat(vals_out, 0)
 
     @property
     def keys_normalized(self):
@@ -353,6 +381,12 @@ class RAGraph(nn.Module):
                            # K.gather_reduce_noisy -- another stream of random numbers, same law; forward and forward_rows
                            # still give a node the same noise under one torch.manual_seed
     last_noise_seed = None
+    build_rng = K.BuildRng()   # "host" (the default) | "device": the draws of _sample_bank (the vanilla phase's sampled bank).
+                           # "device": one int64 [1 + num_augment_scale, K.BUILD_SEED_COLUMNS] seed tensor on the device generator
+                           # (`last_build_seed`, never read back); the rows are picked FIRST (K.multinomial_segments) and only the
+                           # picked rows of keys and values are augmented (K.augment_features keyed by the node) -- no noise or
+                           # mask over the whole tables
+    last_build_seed = None
 
     def _draw_noise_seed(self):
         self.last_noise_seed = K.draw_noise_seed(self.edges.device)

@@ -114,7 +114,7 @@ class RAGraph(nn.Module):
     them from the host generator every forward)."""
 
     def __init__(self, pretrain_model, resource_dataset, mean_fewshot_logits, emb_size, finetune=True,
-                 noise_finetune=False, query_graph_hop=3, retrieve_num=5, device="cuda", dataset_name=None):
+                 noise_finetune=False, query_graph_hop=3, retrieve_num=5, device="cuda", dataset_name=None, build_rng="host"):
         super().__init__()
         self.emb_size = emb_size
         self.pretrain_model = pretrain_model
@@ -127,6 +127,7 @@ class RAGraph(nn.Module):
         self.query_graph_hop = query_graph_hop
         self.toy_graph_base = ToyGraphBaseFewShot(pretrain_model, len(mean_fewshot_logits), emb_size, query_graph_hop,
                                                   retrieve_num, device=device)
+        self.toy_graph_base.build_rng = build_rng   # (ToyGraphBase.build_rng: read when the bank is built)
 
     def forward(self, features, adj, mean_fewshot_logits, anchors=None):
         g = as_csr(adj)
@@ -161,7 +162,7 @@ class RAGraphGraphFewShot(nn.Module):
     row (:86).  FewShotBase (RAGraph.py:43) only loads blobs that forward never reads and is not reproduced."""
 
     def __init__(self, pretrain_model, resource_dataset, feture_size, num_class, emb_size, finetune=True,
-                 noise_finetune=False, device="cuda", dataset_name=None):
+                 noise_finetune=False, device="cuda", dataset_name=None, build_rng="host"):
         super().__init__()
         self.emb_size, self.num_class, self.pretrain_model = emb_size, num_class, pretrain_model
         name = dataset_name or getattr(resource_dataset, "name", "PROTEINS")
@@ -175,6 +176,7 @@ class RAGraphGraphFewShot(nn.Module):
         self.query_graph_hop = 1                                                               # :38
         self.toy_graph_base = ToyGraphBase(pretrain_model, num_class, emb_size, self.query_graph_hop, device=device,
                                            flavour="graph_fewshot")
+        self.toy_graph_base.build_rng = build_rng   # (no draw in this flavour's build: accepted for a uniform interface)
         if resource_dataset is not None:
             self.toy_graph_base.build_toy_graph(resource_dataset)
         self.to(device)

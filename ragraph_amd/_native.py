@@ -156,6 +156,14 @@ SIGNATURES = {
     "ragraph_gather_reduce_noisy_f32": (_i32, [_vp, _i32, _vp, _i32, _i64, _vp, _i64, _i32, _i64, _f32, _vp, _vp, _i64, _i32, _i64,
                                                _vp, _f32, _f32, _vp, _vp, _vp]),
     "ragraph_add_normal_noise_f32": (_i32, [_vp, _i64, _i64, _i32, _f32, _vp, _vp, _i64, _vp, _vp]),
+    "ragraph_edge_rewrite_workspace_bytes": (_sz, [_i64]),
+    "ragraph_edge_rewrite_csr": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "ragraph_multinomial_segments_workspace_bytes": (_sz, [_i64]),
+    "ragraph_multinomial_segments_i64": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "ragraph_csr_induced_blocks_f32": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i32, _vp, _vp]),
+    "ragraph_blocks_to_csr_workspace_bytes": (_sz, [_i64, _i32]),
+    "ragraph_blocks_to_csr_f32": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ragraph_augment_features_f32": (_i32, [_vp, _i64, _i32, _vp, _f32, _f32, _vp, _vp, _vp, _i64, _vp, _vp]),
 }
 
 

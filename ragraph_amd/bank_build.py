@@ -17,6 +17,11 @@ The STOCHASTIC draws (feature noise, node drop, edge rewrite: Augmentation.py:8-
 sampling: ToyGraphBase.py:98; anchors: PositionAwareEncoder.py:11) come from torch's RNG, batched over the graphs; the
 reference draws them from the CUDA generator per graph, so a bank is reproducible per seed here but cannot be
 draw-for-draw identical to a reference bank (the deterministic parts are pinned by golden g13 and the oracle).
+
+With `build_rng = "device"` (ToyGraphBase.build_rng) those draws are hashes of (seed, node or graph,
+draw) made inside the kernels of csrc/bank.hip instead -- K.augment_features, K.edge_rewrite_csr, K.multinomial_segments,
+K.csr_induced_blocks, K.blocks_to_csr, K.noise_rows -- from one seed tensor per batch drawn on the device generator: no torch
+chain, nothing sized by the node pairs of a graph or by the largest graph of a batch.  "host" (the default) is untouched.
 """
 from __future__ import annotations
 
@@ -79,6 +84,19 @@ def augment_batch(features: torch.Tensor, prob: torch.Tensor, graph_ptr: torch.T
     return noisy * mask, g
 
 
+def augment_batch_device(features: torch.Tensor, prob: torch.Tensor, graph_ptr: torch.Tensor, seeds: torch.Tensor):
+    """augment_batch with the draws made on the device: `seeds` is one row of K.draw_build_seeds.  Dropped rows are +0."""
+    noisy = K.augment_features(features, prob, _seed(seeds, K.BUILD_SEED_NODE_DROP), _seed(seeds, K.BUILD_SEED_FEATURE_NOISE),
+                               rate=0.01, std=0.1)                               # :8-22
+    rowptr, col, val = K.edge_rewrite_csr(prob, graph_ptr, _seed(seeds, K.BUILD_SEED_EDGE_SLOT))   # :23-29
+    return noisy, CSRGraph(rowptr, col, val, features.shape[0])
+
+
+def _seed(seeds: torch.Tensor, column: int) -> torch.Tensor:
+    """One column of a pass's row of the build seed tensor, as the one-element device tensor the kernels read."""
+    return seeds[column:column + 1]
+
+
 def _dense_blocks(g: CSRGraph, graph_ptr: torch.Tensor, pick: torch.Tensor) -> torch.Tensor:
     """adj[pick_g][:, pick_g] of every graph (ToyGraphBase.py:100): pick [G,S] global node ids -> [G,S,S] dense."""
     G, S = pick.shape
@@ -108,14 +126,32 @@ def _build_batch(tgb, features, adj: CSRGraph, node_labels, graph_ptr, graph_lab
     """_build_toy_graph_base for a batch of graphs (ToyGraphBase.py:91-119 node; RAGraph_graph/...:99-127 graph)."""
     G = graph_ptr.numel() - 1
     S = tgb.num_inverse_sample
+    seeds = None
+    if getattr(tgb, "build_rng", "host") == "device" and (S > 0 or tgb.num_augment_scale > 0):
+        tgb.last_build_seed = seeds = K.draw_build_seeds(1 + tgb.num_augment_scale, features.device)   # one row per pass
     variants = [(features, adj)]
     if tgb.num_augment_scale > 0:                                               # Augmentation.augment_graph :51-64
         prob0 = compute_sample_prob(adj, graph_ptr)
-        variants += [augment_batch(features, prob0, graph_ptr) for _ in range(tgb.num_augment_scale)]
+        if seeds is not None:
+            variants += [augment_batch_device(features, prob0, graph_ptr, seeds[1 + a]) for a in range(tgb.num_augment_scale)]
+        else:
+            variants += [augment_batch(features, prob0, graph_ptr) for _ in range(tgb.num_augment_scale)]
     embed = tgb.pretrain_model.encode if tgb.flavour == "graph_fewshot" else tgb.pretrain_model.inference
-    for aug_features, aug_adj in variants:
+    for v, (aug_features, aug_adj) in enumerate(variants):
         emb = embed(aug_features, aug_adj)                                      # :93 (graph_fewshot :120 encode)
-        if S > 0:
+        if S > 0 and seeds is not None:
+            prob = compute_sample_prob(aug_adj, graph_ptr)                      # :97
+            pick = K.multinomial_segments(prob, graph_ptr, S, _seed(seeds[v], K.BUILD_SEED_PICK))   # :98, all graphs at once
+            blocks = K.csr_induced_blocks(adj.rowptr, adj.col, adj.val, pick)   # :100 sample_adj from the ORIGINAL adj
+            flat = pick.reshape(-1)
+            keys = K.normalize_rows(K.gather_rows(emb, flat))                   # :101,109
+            labels = K.gather_rows(node_labels, flat)
+            sample_csr = CSRGraph(*K.blocks_to_csr(blocks), G * S)
+            values = Propagation.aggregate_k_hop_features(sample_csr, keys, tgb.toy_graph_hop)    # :112
+            anchors = K.noise_rows(_seed(seeds[v], K.BUILD_SEED_ANCHOR), G, NUM_ANCHORS, S)       # PositionAwareEncoder.py:11
+            positions = K.position_codes_batch(blocks, anchors, DIS_Q).reshape(G * S, NUM_ANCHORS)  # :114
+            seg_ptr = torch.arange(0, G * S + 1, S, dtype=torch.int64, device=prob.device)
+        elif S > 0:
             prob = compute_sample_prob(aug_adj, graph_ptr)                      # :97
             sizes = graph_ptr[1:] - graph_ptr[:-1]
             maxn = int(sizes.max())

@@ -13,6 +13,8 @@
 // dangling mass for the next step).  The host enqueues max_iter iterations back to back; converged graphs turn their
 // launches into no-ops through a device flag, nothing is read back in between.
 #include "common.h"
+#include "rng.h"
+#include "sortscan.h"
 
 namespace ragraph {
 
@@ -171,6 +173,250 @@ __global__ void __launch_bounds__(256) fw_position_batch_kernel(const float* __r
   }
 }
 
+// ---- the stochastic half: augmentation and inverse-importance sampling drawn on the device ---------------------------------
+// Augmentation.augment_features / augment_adj (RAGraph_node/ragraph_utils/Augmentation.py:8-29), torch.multinomial
+// (ToyGraphBase.py:98, RAGraph_edge/modules/RAGraph.py:213), adj[pick][:, pick] (ToyGraphBase.py:100).  Every draw is one
+// lp_draw word (rng.h): a slot's fate depends on (seed, row, draw) only, never on how the work is split, and every rule is
+// restated in numpy by tests/bank_rng_oracle.py.  No buffer here is proportional to the number of node PAIRS of a graph.
+
+// the g with graph_ptr[g] <= i < graph_ptr[g + 1] (graph_ptr[0] <= i < graph_ptr[G]; empty graphs are stepped over)
+__device__ __forceinline__ int64_t graph_of_node(const int64_t* __restrict__ graph_ptr, int64_t G, int64_t i) {
+  int64_t lo = 0, hi = G;
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (graph_ptr[mid] <= i) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// One wave per row i of the batch; lane u looks at the slots (i, jb + u) of i's graph.  Slot (i, j) is kept iff
+// u53(lp_draw(seed, i, j - lo)) < (p_i + p_j) * 0.5f (Augmentation.py:23-27, the diagonal included).  FILL = false: cnt[i] = the
+// kept slots of the row; FILL = true: the same hashes again, the kept columns written in ascending order behind rowptr[i].
+template <bool FILL>
+__global__ void __launch_bounds__(256) edge_rewrite_kernel(const int64_t* __restrict__ seed_p, const float* __restrict__ prob,
+                                                           const int64_t* __restrict__ graph_ptr, int64_t G, int64_t n,
+                                                           int* __restrict__ cnt, int64_t* __restrict__ status,
+                                                           const int64_t* __restrict__ rowptr, int32_t* __restrict__ col,
+                                                           float* __restrict__ val, int64_t capacity) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (!FILL && blockIdx.x == 0 && threadIdx.x == 0) {
+    cnt[n] = 0;      // (the scan runs over n + 1 counts: its last output is the total)
+    status[1] = 0;   // (the overflow word, raised by widen_rowptr_kernel)
+  }
+  if (i >= n) return;
+  const int64_t g = graph_of_node(graph_ptr, G, i);
+  const int64_t lo = graph_ptr[g] > 0 ? graph_ptr[g] : 0;
+  const int64_t hi = graph_ptr[g + 1] < n ? graph_ptr[g + 1] : n;
+  const bool mine = lo <= i && i < hi;   // (false only for a graph_ptr that does not cover [0, n): such a row stays empty)
+  const uint64_t rk = splitmix64((uint64_t)seed_p[0] ^ splitmix64((uint64_t)i));   // lp_draw's row part, once per row
+  const float pi = prob[i];
+  const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  int64_t pos = FILL ? rowptr[i] : 0;
+  int c = 0;
+  for (int64_t jb = lo; mine && jb < hi; jb += 64) {   // (wave-uniform trip count: a ballot inside)
+    const int64_t j = jb + lane;
+    bool keep = false;
+    if (j < hi) keep = lp_event(splitmix64(rk + (uint64_t)(j - lo)), __fmul_rn(__fadd_rn(pi, prob[j]), 0.5f));
+    const unsigned long long m = __ballot(keep);
+    if (FILL) {
+      const int64_t at = pos + __popcll(m & below);
+      if (keep && at >= 0 && at < capacity) {
+        col[at] = (int32_t)j;
+        val[at] = 1.f;
+      }
+      pos += __popcll(m);
+    } else {
+      c += __popcll(m);
+    }
+  }
+  if (!FILL && lane == 0) cnt[i] = c;
+}
+
+// rowptr[k] = excl[k] for k <= n (excl: the int32 exclusive scan of n counts and a trailing zero), total[0] = excl[n].
+// Every count is below 2^31, so the FIRST prefix that reaches 2^31 is still below 2^32: it shows as a negative int32 whatever
+// wrapped after it -- overflow[0] = 1 then (the caller zeroes it first), and the caller reports an error.
+__global__ void __launch_bounds__(256) widen_rowptr_kernel(const int* __restrict__ excl, int64_t n, int64_t* __restrict__ rowptr,
+                                                           int64_t* __restrict__ total, int64_t* __restrict__ overflow) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k > n) return;
+  const int v = excl[k];
+  rowptr[k] = (int64_t)(uint32_t)v;
+  if (v < 0 && overflow) overflow[0] = 1;
+  if (k == n) total[0] = (int64_t)(uint32_t)v;
+}
+
+// ---- multinomial with replacement over segments ------------------------------------------------------------------------------
+// Integer weights: w_i = (uint64)((double)min(p_i, 1) * 2^40), 0 for a negative or NaN p_i -- sums of them are exact, so the
+// prefix a draw is compared with does not depend on the shape of the scan.  Level 1: the sums of tiles of 64 entries of the
+// whole array (tile boundaries ignore the segments) and their exclusive prefix P; level 2: one wave per draw.
+constexpr int MN_TILE = 64;
+__device__ __forceinline__ uint64_t mn_weight(float p) {
+  return p > 0.f ? (uint64_t)((double)fminf(p, 1.f) * 0x1p40) : 0ull;   // (NaN > 0 is false)
+}
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// tsum[t] = the weights of tile t, t <= nt = ceil(n / 64) (the tile behind the last is empty: its prefix is the total)
+__global__ void __launch_bounds__(256) mn_tile_sums_kernel(const float* __restrict__ prob, int64_t n, int64_t nt,
+                                                           uint64_t* __restrict__ tsum) {
+  const int lane = threadIdx.x & 63;
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t > nt) return;
+  const int64_t i = t * MN_TILE + lane;
+  const uint64_t s = wave_sum_u64(i < n ? mn_weight(prob[i]) : 0ull);
+  if (lane == 0) tsum[t] = s;
+}
+
+// in place, one workgroup: P[t] = sum of tsum[0 .. t).  Thread u owns a contiguous run of entries.
+__global__ void __launch_bounds__(256) mn_tile_scan_kernel(uint64_t* __restrict__ tsum, int64_t m) {
+  __shared__ uint64_t sh[256];
+  const int64_t per = (m + 255) / 256;
+  const int64_t lo = (int64_t)threadIdx.x * per < m ? (int64_t)threadIdx.x * per : m;
+  const int64_t hi = lo + per < m ? lo + per : m;
+  uint64_t s = 0;
+  for (int64_t k = lo; k < hi; ++k) s += tsum[k];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  uint64_t run = 0;
+  for (int u = 0; u < (int)threadIdx.x; ++u) run += sh[u];
+  for (int64_t k = lo; k < hi; ++k) {
+    const uint64_t v = tsum[k];
+    tsum[k] = run;
+    run += v;
+  }
+}
+
+// One wave per draw (g, s).  F(x) = the weights of the entries below x = P[x / 64] + the head of x's tile.  W_g = F(hi) - F(lo),
+// t = lp_below(lp_draw(seed, g, s), W_g); the answer is the smallest i in [lo, hi) with F(i + 1) > F(lo) + t: the last tile k
+// with P[k] <= F(lo) + t holds it, and an inclusive wave scan over that tile finds it.  An entry of weight 0 has the prefix of
+// its predecessor, so it is never the smallest; W_g = 0 gives -1.
+__global__ void __launch_bounds__(256) mn_draw_kernel(const int64_t* __restrict__ seed_p, const float* __restrict__ prob,
+                                                      const int64_t* __restrict__ seg_ptr, int64_t G, int S, int64_t n,
+                                                      const uint64_t* __restrict__ P, int64_t* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t d = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (d >= G * S) return;
+  const int64_t g = d / S, s = d - g * S;
+  int64_t lo = seg_ptr[g], hi = seg_ptr[g + 1];
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > n ? n : hi;
+  auto below = [&](int64_t x) {   // F(x), 0 <= x <= n
+    const int64_t i = (x >> 6) * MN_TILE + lane;
+    return P[x >> 6] + wave_sum_u64(i < x ? mn_weight(prob[i]) : 0ull);
+  };
+  int64_t res = -1;
+  if (lo < hi) {
+    const uint64_t f_lo = below(lo);
+    const uint64_t W = below(hi) - f_lo;
+    if (W != 0) {
+      const uint64_t target = f_lo + lp_below(lp_draw((uint64_t)seed_p[0], (uint64_t)g, (uint64_t)s), W);
+      int64_t ka = lo >> 6, kb = (hi - 1) >> 6;   // P[ka] <= target; the answer's tile is the last k <= kb with P[k] <= target
+      while (ka < kb) {
+        const int64_t mid = (ka + kb + 1) >> 1;
+        if (P[mid] <= target) ka = mid; else kb = mid - 1;
+      }
+      const int64_t i = ka * MN_TILE + lane;
+      uint64_t incl = i < hi ? mn_weight(prob[i]) : 0ull;   // (entries below lo count: their prefixes are <= F(lo) <= target)
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t up = __shfl_up(incl, off);
+        if (lane >= off) incl += up;
+      }
+      const unsigned long long m = __ballot(P[ka] + incl > target);
+      if (m) res = ka * MN_TILE + (__ffsll((long long)m) - 1);
+    }
+  }
+  if (lane == 0) out[d] = res;
+}
+
+// ---- adj[pick_g][:, pick_g] ----------------------------------------------------------------------------------------------------
+// One lane per entry (g, a, b) of the dense [G, S, S]: the first slot of row pick[g, a] whose column is >= pick[g, b] (the
+// columns of a row ascend), its value when the column is the one asked for, else 0.  A pick outside [0, n) (the -1 of an
+// all-zero segment) gives a zero row and column.
+__global__ void __launch_bounds__(256) csr_induced_blocks_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                                 const float* __restrict__ val, int64_t n, int64_t nnz,
+                                                                 const int64_t* __restrict__ pick, int64_t G, int S,
+                                                                 float* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= G * S * S) return;
+  const int64_t ga = e / S;
+  const int b = (int)(e - ga * S);
+  const int64_t r = pick[ga], c = pick[ga - ga % S + b];
+  float v = 0.f;
+  if (r >= 0 && r < n && c >= 0 && c < n) {
+    int64_t lo = rowptr[r], hi = rowptr[r + 1];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > nnz ? nnz : hi;
+    const int64_t end = hi;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if ((int64_t)col[mid] < c) lo = mid + 1; else hi = mid;
+    }
+    if (lo < end && (int64_t)col[lo] == c) v = val[lo];
+  }
+  out[e] = v;
+}
+
+// ---- [G, S, S] dense blocks, S <= 64 -> block-diagonal CSR ------------------------------------------------------------------
+// One wave per row (g, a); lane b holds entry (g, a, b).  An entry is kept iff it compares unequal to 0 (so -0 is dropped and a
+// NaN kept, as torch.nonzero does).  FILL = false: the row's count; FILL = true: columns g * S + b ascending, the values as
+// they are, behind excl[row].
+template <bool FILL>
+__global__ void __launch_bounds__(256) blocks_to_csr_kernel(const float* __restrict__ blocks, int64_t rows, int S,
+                                                            int* __restrict__ cnt, const int* __restrict__ excl,
+                                                            int32_t* __restrict__ col, float* __restrict__ val) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (!FILL && blockIdx.x == 0 && threadIdx.x == 0) cnt[rows] = 0;
+  if (r >= rows) return;
+  const float v = lane < S ? blocks[r * S + lane] : 0.f;
+  const bool keep = lane < S && v != 0.f;
+  const unsigned long long m = __ballot(keep);
+  if (FILL) {
+    const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    if (keep) {
+      const int64_t at = (int64_t)excl[r] + __popcll(m & below);
+      col[at] = (int32_t)(r - r % S + lane);
+      val[at] = v;
+    }
+  } else if (lane == 0) {
+    cnt[r] = __popcll(m);
+  }
+}
+
+// ---- Augmentation.augment_features (Augmentation.py:8-22) ------------------------------------------------------------------
+// One lane per pair of columns, as add_normal_noise_kernel (noise.hip) with J = 1.  Row i is kept iff
+// u53(lp_draw(seed_drop, id_i, 0)) < p_i * rate; a kept row is x + std * z with the z of add_normal_noise for that id (the same
+// bits); a dropped row is +0 in every column, and no normal is computed for it.
+__global__ void __launch_bounds__(256) augment_features_kernel(const float* X, int64_t n, int D,
+                                                               const float* __restrict__ prob, float rate, float std,
+                                                               const int64_t* __restrict__ seed_drop,
+                                                               const int64_t* __restrict__ seed_noise,
+                                                               const int64_t* __restrict__ row_ids, int64_t row_base,
+                                                               float* out) {
+  const int64_t P = (D + 1) >> 1;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n * P) return;
+  const int64_t r = i / P;
+  const int p = (int)(i - r * P);
+  const uint64_t id = noise_row_id(row_ids, row_base, r);
+  const int64_t o = r * D + 2 * p;
+  const bool two = 2 * p + 1 < D;
+  float y0 = 0.f, y1 = 0.f;
+  if (lp_event(lp_draw((uint64_t)seed_drop[0], id, 0), __fmul_rn(prob[r], rate))) {
+    float z0, z1;
+    normal_pair((uint64_t)seed_noise[0], id, (uint64_t)p, z0, z1);
+    y0 = __fadd_rn(X[o], __fmul_rn(std, z0));
+    if (two) y1 = __fadd_rn(X[o + 1], __fmul_rn(std, z1));
+  }
+  out[o] = y0;
+  if (two) out[o + 1] = y1;
+}
+
 }  // namespace ragraph
 
 using namespace ragraph;
@@ -230,5 +476,127 @@ extern "C" int ragraph_position_codes_batch_f32(const float* adj, int64_t G, int
   hipLaunchKernelGGL(fw_position_batch_kernel, dim3((unsigned)G), dim3(256), 0, as_stream(stream), adj, n, anchors, A, dis_q,
                      dist_out, codes);
   RG_CHECK_LAUNCH("position_codes_batch");
+  return RAGRAPH_OK;
+}
+
+// ---- the stochastic half ---------------------------------------------------------------------------------------------------
+static size_t counts_scan_bytes(int64_t rows) {   // rows + 1 int32 counts (scanned in place) + the scan's own scratch
+  return align_up((size_t)(rows + 1) * sizeof(int), 256) + scan_temp_bytes(rows + 1);
+}
+
+extern "C" size_t ragraph_edge_rewrite_workspace_bytes(int64_t n) { return counts_scan_bytes(n > 0 ? n : 0); }
+
+extern "C" int ragraph_edge_rewrite_csr(const int64_t* seed, const float* prob, const int64_t* graph_ptr, int64_t G, int64_t n,
+                                        int64_t* rowptr, int64_t* status, int32_t* col, float* val, int64_t capacity, void* ws,
+                                        size_t ws_bytes, void* stream) {
+  RG_REQUIRE(seed, RAGRAPH_EINVAL, "edge_rewrite: null seed");
+  RG_REQUIRE(prob && graph_ptr && rowptr, RAGRAPH_EINVAL, "edge_rewrite: null pointer");
+  RG_REQUIRE(G >= 1 && n >= 1 && n <= (int64_t)INT_MAX - 1, RAGRAPH_EINVAL, "edge_rewrite: bad G=%lld / n=%lld", (long long)G,
+             (long long)n);
+  RG_REQUIRE((col == nullptr) == (val == nullptr), RAGRAPH_EINVAL, "edge_rewrite: col and val go together");
+  hipStream_t st = as_stream(stream);
+  const unsigned row_blocks = (unsigned)cdiv(n, 4);
+  if (col) {   // the fill pass
+    RG_REQUIRE(capacity >= 1, RAGRAPH_EINVAL, "edge_rewrite: capacity=%lld", (long long)capacity);
+    hipLaunchKernelGGL(edge_rewrite_kernel<true>, dim3(row_blocks), dim3(256), 0, st, seed, prob, graph_ptr, G, n, (int*)nullptr,
+                       (int64_t*)nullptr, (const int64_t*)rowptr, col, val, capacity);
+    RG_CHECK_LAUNCH("edge_rewrite(fill)");
+    return RAGRAPH_OK;
+  }
+  RG_REQUIRE(status && ws, RAGRAPH_EINVAL, "edge_rewrite: null pointer");
+  RG_REQUIRE(ws_bytes >= ragraph_edge_rewrite_workspace_bytes(n), RAGRAPH_EWORKSPACE, "edge_rewrite: workspace too small");
+  int* cnt = static_cast<int*>(ws);
+  const size_t cnt_bytes = align_up((size_t)(n + 1) * sizeof(int), 256);
+  hipLaunchKernelGGL(edge_rewrite_kernel<false>, dim3(row_blocks), dim3(256), 0, st, seed, prob, graph_ptr, G, n, cnt, status,
+                     (const int64_t*)nullptr, (int32_t*)nullptr, (float*)nullptr, (int64_t)0);
+  RG_CHECK_LAUNCH("edge_rewrite(count)");
+  const int rc = scan_sum_i32(cnt, cnt, n + 1, false, static_cast<char*>(ws) + cnt_bytes, ws_bytes - cnt_bytes, st);
+  if (rc != RAGRAPH_OK) return rc;
+  hipLaunchKernelGGL(widen_rowptr_kernel, dim3((unsigned)cdiv(n + 1, 256)), dim3(256), 0, st, (const int*)cnt, n, rowptr, status,
+                     status + 1);
+  RG_CHECK_LAUNCH("edge_rewrite(rowptr)");
+  return RAGRAPH_OK;
+}
+
+extern "C" size_t ragraph_multinomial_segments_workspace_bytes(int64_t n) {
+  return align_up((size_t)(cdiv(n > 0 ? n : 0, MN_TILE) + 1) * sizeof(uint64_t), 256);
+}
+
+extern "C" int ragraph_multinomial_segments_i64(const int64_t* seed, const float* prob, int64_t n, const int64_t* seg_ptr,
+                                                int64_t G, int S, int64_t* out, void* ws, size_t ws_bytes, void* stream) {
+  RG_REQUIRE(seed, RAGRAPH_EINVAL, "multinomial_segments: null seed");
+  RG_REQUIRE(prob && seg_ptr && out && ws, RAGRAPH_EINVAL, "multinomial_segments: null pointer");
+  RG_REQUIRE(G >= 1 && S >= 1 && n >= 1, RAGRAPH_EINVAL, "multinomial_segments: bad G=%lld / S=%d / n=%lld", (long long)G, S,
+             (long long)n);
+  // every segment lies inside [0, n): n < 2^23 bounds each of them, and their weights (<= 2^40 each) sum below 2^63
+  RG_REQUIRE(n < ((int64_t)1 << 23), RAGRAPH_EINVAL, "multinomial_segments: n=%lld, segments must be shorter than 2^23",
+             (long long)n);
+  RG_REQUIRE(G <= (((int64_t)1 << 33) - 4) / S, RAGRAPH_EINVAL, "multinomial_segments: G * S too large");
+  RG_REQUIRE(ws_bytes >= ragraph_multinomial_segments_workspace_bytes(n), RAGRAPH_EWORKSPACE,
+             "multinomial_segments: workspace too small");
+  hipStream_t st = as_stream(stream);
+  uint64_t* P = static_cast<uint64_t*>(ws);
+  const int64_t nt = cdiv(n, MN_TILE);
+  hipLaunchKernelGGL(mn_tile_sums_kernel, dim3((unsigned)cdiv(nt + 1, 4)), dim3(256), 0, st, prob, n, nt, P);
+  hipLaunchKernelGGL(mn_tile_scan_kernel, dim3(1), dim3(256), 0, st, P, nt + 1);
+  hipLaunchKernelGGL(mn_draw_kernel, dim3((unsigned)cdiv(G * S, 4)), dim3(256), 0, st, seed, prob, seg_ptr, G, S, n,
+                     (const uint64_t*)P, out);
+  RG_CHECK_LAUNCH("multinomial_segments");
+  return RAGRAPH_OK;
+}
+
+extern "C" int ragraph_csr_induced_blocks_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n, int64_t nnz,
+                                              const int64_t* pick, int64_t G, int S, float* out, void* stream) {
+  RG_REQUIRE(rowptr && pick && out, RAGRAPH_EINVAL, "csr_induced_blocks: null pointer");
+  RG_REQUIRE(nnz >= 0 && (nnz == 0 || (col && val)), RAGRAPH_EINVAL, "csr_induced_blocks: null pointer");
+  RG_REQUIRE(G >= 1 && S >= 1 && n >= 1, RAGRAPH_EINVAL, "csr_induced_blocks: bad G=%lld / S=%d / n=%lld", (long long)G, S,
+             (long long)n);
+  RG_REQUIRE(G <= (((int64_t)1 << 39) - 256) / S / S, RAGRAPH_EINVAL, "csr_induced_blocks: G * S * S too large");
+  hipLaunchKernelGGL(csr_induced_blocks_kernel, dim3((unsigned)cdiv(G * S * S, 256)), dim3(256), 0, as_stream(stream), rowptr,
+                     col, val, n, nnz, pick, G, S, out);
+  RG_CHECK_LAUNCH("csr_induced_blocks");
+  return RAGRAPH_OK;
+}
+
+extern "C" size_t ragraph_blocks_to_csr_workspace_bytes(int64_t G, int S) {
+  return counts_scan_bytes(G > 0 && S > 0 ? G * S : 0);
+}
+
+extern "C" int ragraph_blocks_to_csr_f32(const float* blocks, int64_t G, int S, int64_t* rowptr, int32_t* col, float* val,
+                                         int64_t* nnz, void* ws, size_t ws_bytes, void* stream) {
+  RG_REQUIRE(blocks && rowptr && col && val && nnz && ws, RAGRAPH_EINVAL, "blocks_to_csr: null pointer");
+  RG_REQUIRE(G >= 1 && S >= 1 && S <= 64, RAGRAPH_EINVAL, "blocks_to_csr: bad G=%lld / S=%d (S <= 64)", (long long)G, S);
+  RG_REQUIRE(G <= (int64_t)INT_MAX / S / S, RAGRAPH_EINVAL, "blocks_to_csr: G * S * S too large");
+  RG_REQUIRE(ws_bytes >= ragraph_blocks_to_csr_workspace_bytes(G, S), RAGRAPH_EWORKSPACE, "blocks_to_csr: workspace too small");
+  hipStream_t st = as_stream(stream);
+  const int64_t rows = G * S;
+  int* cnt = static_cast<int*>(ws);
+  const size_t cnt_bytes = align_up((size_t)(rows + 1) * sizeof(int), 256);
+  const unsigned row_blocks = (unsigned)cdiv(rows, 4);
+  hipLaunchKernelGGL(blocks_to_csr_kernel<false>, dim3(row_blocks), dim3(256), 0, st, blocks, rows, S, cnt, (const int*)nullptr,
+                     (int32_t*)nullptr, (float*)nullptr);
+  RG_CHECK_LAUNCH("blocks_to_csr(count)");
+  const int rc = scan_sum_i32(cnt, cnt, rows + 1, false, static_cast<char*>(ws) + cnt_bytes, ws_bytes - cnt_bytes, st);
+  if (rc != RAGRAPH_OK) return rc;
+  hipLaunchKernelGGL(widen_rowptr_kernel, dim3((unsigned)cdiv(rows + 1, 256)), dim3(256), 0, st, (const int*)cnt, rows, rowptr,
+                     nnz, (int64_t*)nullptr);
+  hipLaunchKernelGGL(blocks_to_csr_kernel<true>, dim3(row_blocks), dim3(256), 0, st, blocks, rows, S, (int*)nullptr,
+                     (const int*)cnt, col, val);
+  RG_CHECK_LAUNCH("blocks_to_csr(fill)");
+  return RAGRAPH_OK;
+}
+
+extern "C" int ragraph_augment_features_f32(const float* X, int64_t n, int D, const float* prob, float rate, float std,
+                                            const int64_t* seed_drop, const int64_t* seed_noise, const int64_t* row_ids,
+                                            int64_t row_base, float* out, void* stream) {
+  RG_REQUIRE(seed_drop && seed_noise, RAGRAPH_EINVAL, "augment_features: null seed");
+  RG_REQUIRE(n >= 0 && D >= 1, RAGRAPH_EINVAL, "augment_features: bad shape (n=%lld, D=%d)", (long long)n, D);
+  const int64_t P = ((int64_t)D + 1) >> 1;
+  RG_REQUIRE(n <= (((int64_t)1 << 39) - 256) / P, RAGRAPH_EINVAL, "augment_features: n * D too large");
+  if (n == 0) return RAGRAPH_OK;
+  RG_REQUIRE(X && prob && out, RAGRAPH_EINVAL, "augment_features: null pointer");
+  hipLaunchKernelGGL(augment_features_kernel, dim3((unsigned)cdiv(n * P, 256)), dim3(256), 0, as_stream(stream), X, n, D, prob,
+                     rate, std, seed_drop, seed_noise, row_ids, row_base, out);
+  RG_CHECK_LAUNCH("augment_features");
   return RAGRAPH_OK;
 }

@@ -17,10 +17,6 @@
 
 namespace ragraph {
 
-__device__ __forceinline__ uint64_t noise_row_id(const int64_t* __restrict__ row_ids, int64_t row_base, int64_t b) {
-  return (uint64_t)(row_ids ? row_ids[b] : row_base + b);
-}
-
 // ---- noise rows: one lane per slot ------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) noise_rows_kernel(const int64_t* __restrict__ seed_p, const int64_t* __restrict__ row_ids,
                                                          int64_t row_base, int64_t B, int m, uint64_t N,
@@ -133,19 +129,6 @@ __global__ void __launch_bounds__(256) gather_reduce_noisy_kernel(const float* _
 }
 
 // ---- Gaussian noise on gathered embeddings ----------------------------------------------------------------------------------
-// The two standard normals of draw `draw` of a row: Box-Muller on the two 24-bit halves of the word's high 48 bits.
-// u1 = (h + 1) / 2^24 lies in (0, 1], so r <= sqrt(48 ln 2) ~ 5.77; u2 = l / 2^24 in [0, 1).  Every product is explicit.
-__device__ __forceinline__ void normal_pair(uint64_t seed, uint64_t row, uint64_t draw, float& z0, float& z1) {
-  const uint64_t w = lp_draw(seed, row, draw);
-  const float u1 = __fmul_rn((float)((uint32_t)(w >> 40) + 1u), 0x1p-24f);
-  const float u2 = __fmul_rn((float)((uint32_t)(w >> 16) & 0xFFFFFFu), 0x1p-24f);
-  const float r = sqrtf(__fmul_rn(-2.f, logf(u1)));
-  float s, c;
-  sincospif(__fmul_rn(2.f, u2), &s, &c);
-  z0 = __fmul_rn(r, c);
-  z1 = __fmul_rn(r, s);
-}
-
 // One lane per pair of columns of X [B, J, D]: pair p of row (b, j) is draw j * ceil(D / 2) + p of row id(b).  out may be X.
 __global__ void __launch_bounds__(256) add_normal_noise_kernel(const float* X, int64_t B, int64_t J, int D, float std,
                                                                const int64_t* __restrict__ seed_p,

@@ -1738,3 +1738,143 @@ class NoiseRng:
 
     def __set__(self, obj, value):
         obj.__dict__["_noise_rng"] = check_noise_rng(value)
+
+
+# ---- bank construction with the draws made on the device (csrc/bank.hip) -----------------------------------
+BUILD_SEED_COLUMNS = 7
+(BUILD_SEED_FEATURE_NOISE, BUILD_SEED_NODE_DROP, BUILD_SEED_EDGE_SLOT, BUILD_SEED_PICK, BUILD_SEED_ANCHOR,
+ BUILD_SEED_VALUE_NOISE, BUILD_SEED_VALUE_DROP) = range(BUILD_SEED_COLUMNS)   # the columns of a build seed tensor
+
+
+def draw_build_seeds(passes: int, device) -> torch.Tensor:
+    """int64 [passes, BUILD_SEED_COLUMNS] on the device generator (as draw_noise_seed: torch.manual_seed reproduces it, nothing is
+    read back): row v holds the seeds of pass v of one batch of bank construction, one column per kind of draw."""
+    return torch.randint(0, 2 ** 62, (int(passes), BUILD_SEED_COLUMNS), dtype=torch.int64, device=device)
+
+
+def _seed1(seed: torch.Tensor, what: str) -> torch.Tensor:
+    sd = _idxc(seed, f"{what}.seed")
+    if sd.numel() != 1:
+        raise RagraphNativeError(f"{what}: seed must hold one int64, got {tuple(sd.shape)}")
+    return sd
+
+
+def edge_rewrite_csr(prob: torch.Tensor, graph_ptr: torch.Tensor, seed: torch.Tensor):
+    """Augmentation.augment_adj for a block-diagonal batch (ragraph_edge_rewrite_csr): slot (i, j) of a graph is 1 with
+    probability (p_i + p_j) / 2, decided by the hash of (seed[0], i, local j).  Returns (rowptr int64 [n+1], col int32 [nnz]
+    ascending per row, val fp32 ones).  Two passes (count, then fill, hashing again) around ONE read-back of the kept total;
+    nothing is sized by the node pairs.  A kept total of 2^31 or more raises."""
+    L = _ready()
+    p = _f32c(prob, "edge_rewrite_csr.prob").reshape(-1)
+    gp = _idxc(graph_ptr, "edge_rewrite_csr.graph_ptr").reshape(-1)
+    sd = _seed1(seed, "edge_rewrite_csr")
+    n, G = p.numel(), gp.numel() - 1
+    dev = p.device
+    rowptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(2, dtype=torch.int64, device=dev)
+    ws = _workspace(L.ragraph_edge_rewrite_workspace_bytes(n), dev)
+    N.check(L.ragraph_edge_rewrite_csr(sd.data_ptr(), p.data_ptr(), gp.data_ptr(), G, n, rowptr.data_ptr(), status.data_ptr(),
+                                       None, None, 0, ws.data_ptr(), ws.numel(), _stream()), "edge_rewrite_csr")
+    nnz, overflow = status.tolist()
+    if overflow:
+        raise RagraphNativeError("edge_rewrite_csr: 2^31 or more slots kept (int32 columns and counts cannot hold them)")
+    col = torch.empty(nnz, dtype=torch.int32, device=dev)
+    val = torch.empty(nnz, dtype=torch.float32, device=dev)
+    if nnz:
+        N.check(L.ragraph_edge_rewrite_csr(sd.data_ptr(), p.data_ptr(), gp.data_ptr(), G, n, rowptr.data_ptr(), None,
+                                           col.data_ptr(), val.data_ptr(), nnz, None, 0, _stream()), "edge_rewrite_csr")
+    return rowptr, col, val
+
+
+def multinomial_segments(prob: torch.Tensor, seg_ptr: torch.Tensor, S: int, seed: torch.Tensor) -> torch.Tensor:
+    """torch.multinomial(prob, S, replacement=True) for every segment [seg_ptr[g], seg_ptr[g+1]) of prob
+    (ragraph_multinomial_segments_i64): int64 [G, S] GLOBAL positions, -1 for a segment without weight.  Draw (g, s) is the
+    hash of (seed[0], g, s) pushed through the inverse CDF of the integer weights (uint64)(min(p, 1) * 2^40)."""
+    L = _ready()
+    p = _f32c(prob, "multinomial_segments.prob").reshape(-1)
+    sp = _idxc(seg_ptr, "multinomial_segments.seg_ptr").reshape(-1)
+    sd = _seed1(seed, "multinomial_segments")
+    n, G, S = p.numel(), sp.numel() - 1, int(S)
+    out = torch.empty((max(G, 0), max(S, 0)), dtype=torch.int64, device=p.device)
+    ws = _workspace(L.ragraph_multinomial_segments_workspace_bytes(n), p.device)
+    N.check(L.ragraph_multinomial_segments_i64(sd.data_ptr(), p.data_ptr(), n, sp.data_ptr(), G, S, out.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), _stream()), "multinomial_segments")
+    return out
+
+
+def csr_induced_blocks(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, pick: torch.Tensor) -> torch.Tensor:
+    """adj[pick_g][:, pick_g] of every graph (ragraph_csr_induced_blocks_f32): a CSR with ascending columns per row and pick
+    int64 [G, S] global ids (repeats allowed) -> dense fp32 [G, S, S]."""
+    L = _ready()
+    rp = _idxc(rowptr, "csr_induced_blocks.rowptr")
+    c = _idxc(col, "csr_induced_blocks.col", torch.int32)
+    v = _f32c(val, "csr_induced_blocks.val")
+    pk = _idxc(pick, "csr_induced_blocks.pick")
+    if pk.dim() != 2:
+        raise RagraphNativeError(f"csr_induced_blocks: pick must be [G, S], got {tuple(pk.shape)}")
+    G, S = pk.shape
+    nnz = c.numel()
+    out = torch.empty((G, S, S), dtype=torch.float32, device=pk.device)
+    N.check(L.ragraph_csr_induced_blocks_f32(rp.data_ptr(), c.data_ptr() if nnz else None, v.data_ptr() if nnz else None,
+                                             rp.numel() - 1, nnz, pk.data_ptr(), G, S, out.data_ptr(), _stream()),
+            "csr_induced_blocks")
+    return out
+
+
+def blocks_to_csr(blocks: torch.Tensor):
+    """Dense [G, S, S] blocks, S <= 64 -> the block-diagonal CSR over G * S rows (ragraph_blocks_to_csr_f32): (rowptr int64
+    [G*S+1], col int32, val fp32), the non-zeros in row-major order.  Reads the entry count back, nothing else."""
+    L = _ready()
+    b = _f32c(blocks, "blocks_to_csr.blocks")
+    if b.dim() != 3 or b.shape[1] != b.shape[2]:
+        raise RagraphNativeError(f"blocks_to_csr: blocks must be [G, S, S], got {tuple(b.shape)}")
+    G, S = b.shape[0], b.shape[1]
+    dev = b.device
+    rowptr = torch.empty(G * S + 1, dtype=torch.int64, device=dev)
+    col = torch.empty(G * S * S, dtype=torch.int32, device=dev)
+    val = torch.empty(G * S * S, dtype=torch.float32, device=dev)
+    nnz = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = _workspace(L.ragraph_blocks_to_csr_workspace_bytes(G, S), dev)
+    N.check(L.ragraph_blocks_to_csr_f32(b.data_ptr(), G, S, rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), nnz.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _stream()), "blocks_to_csr")
+    m = int(nnz.item())
+    return rowptr, col[:m], val[:m]
+
+
+def augment_features(x: torch.Tensor, prob: torch.Tensor, seed_drop: torch.Tensor, seed_noise: torch.Tensor,
+                     rate: float = 0.01, std: float = 0.1, row_ids: torch.Tensor | None = None, row_base: int = 0) -> torch.Tensor:
+    """Augmentation.augment_features (ragraph_augment_features_f32): row i of x [n, D] survives with probability prob[i] * rate
+    -- the hash of (seed_drop[0], id of i) -- as x + std * z, z the normals of add_normal_noise(x, std, seed_noise, ...) for
+    that id; every other row is +0.  row_ids int64 [n] / row_base: the ids, as in the noise entries."""
+    L = _ready()
+    x = _f32c(x, "augment_features.x")
+    if x.dim() != 2:
+        raise RagraphNativeError(f"augment_features: x must be [n, D], got {tuple(x.shape)}")
+    n, D = x.shape
+    p = _f32c(prob, "augment_features.prob").reshape(-1)
+    if p.numel() != n:
+        raise RagraphNativeError(f"augment_features: {p.numel()} probabilities for {n} rows")
+    sd, row_ids = _noise_keys(seed_drop, row_ids, n, "augment_features")
+    sn = _seed1(seed_noise, "augment_features")
+    out = torch.empty_like(x)
+    N.check(L.ragraph_augment_features_f32(x.data_ptr() if n else None, n, D, p.data_ptr() if n else None, float(rate), float(std),
+                                           sd.data_ptr(), sn.data_ptr(), _ptr(row_ids), int(row_base),
+                                           out.data_ptr() if n else None, _stream()), "augment_features")
+    return out
+
+
+def check_build_rng(value: str) -> str:
+    if value not in ("host", "device"):
+        raise ValueError(f"build_rng: 'host' or 'device', not {value!r}")
+    return value
+
+
+class BuildRng:
+    """The `build_rng` attribute of the classes that build a bank: "host" unless an instance sets it; a value other than
+    "host" or "device" raises ValueError where it is set."""
+
+    def __get__(self, obj, owner=None):
+        return "host" if obj is None else obj.__dict__.get("_build_rng", "host")
+
+    def __set__(self, obj, value):
+        obj.__dict__["_build_rng"] = check_build_rng(value)

@@ -50,6 +50,13 @@ class ToyGraphBase:
                            # K.add_normal_noise: another stream of random numbers, same law) -- no host work, capturable,
                            # reproduced by torch.manual_seed
     last_noise_seed = None
+    build_rng = K.BuildRng()   # "host" (the default) | "device": where bank construction (ragraph_amd.bank_build) makes its draws.
+                           # "host": torch's generators through torch chains, every bit as before; "device": one int64
+                           # [1 + num_augment_scale, K.BUILD_SEED_COLUMNS] seed tensor per batch of resource graphs, drawn on the
+                           # device generator and kept in `last_build_seed` (never read back), and every draw a hash of (seed,
+                           # node or graph, draw) made inside the kernels of csrc/bank.hip -- another stream of the same laws,
+                           # reproduced by torch.manual_seed, with nothing sized by the node pairs of a graph
+    last_build_seed = None
 
     def _draw_noise_seed(self) -> Tensor:
         """The seed of this noisy call ("device" mode)."""
