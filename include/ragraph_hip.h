@@ -651,6 +651,30 @@ int ragraph_position_code_f32(const float* dist, int n, const int64_t* anchors, 
 int ragraph_position_codes_csr_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n,
                                    const int64_t* anchors, int A, float dis_q, float* codes, float* dist, void* stream);
 
+/* The same codes for a LARGE graph: any 1 <= n < 2^31, any A >= 1.  The distance vectors live in global memory (the workspace:
+ * [n, 16] floats per chunk of 16 anchors, two dirty bytes per node and chunk, one int32 per node) and every round relaxes all
+ * rows over the whole chip.
+ *   Numerics: the contract of ragraph_position_codes_csr_f32 and of oracle_position_codes_csr, bit for bit:
+ *     d[u] = min(d[u], __fadd_rn(val[u,v], d[v])) over the out-edges with val != 0 and v != u, to the fixpoint;
+ *     code = d < dis_q ? 1/(d + 1) : 0.  min is exact and every candidate is one fp32 add, so the split of a row's edges over
+ *     lanes, waves and workgroups and the order in which rows see each other's updates change no bit of the fixpoint.
+ *   One call enqueues exactly `rounds` (>= 1) relaxation rounds, one launch each, plus the write of codes (and dist); no
+ *     allocation, no synchronisation, no read-back: it can be captured in a HIP graph.
+ *   resume = 0 initialises the state (0 at an anchor's own node, +inf elsewhere); resume = 1 continues from the state the
+ *     workspace holds (same graph, same anchors, same workspace, nothing else run in it since).
+ *   *converged (device, one word, may be NULL) = 1 when the last round of the call changed nothing -- codes and dist are then
+ *     final -- else 0: they are then valid upper bounds of the distances (codes: lower bounds).  A round whose predecessor
+ *     changed nothing returns at once, so rounds past the fixpoint cost a launch each and nothing else.
+ *   A row with more than RAGRAPH_POSITION_CODES_LONG_ROW edges is relaxed by a whole workgroup, the others by 16 lanes.
+ *   Negative weights have no fixpoint when a cycle's sum is negative: a driver must bound the rounds itself (n in total, as
+ *     the LDS kernel does); the result is then whatever that many rounds leave.
+ *   The size query returns 0 for arguments the call refuses.  ws 64-byte aligned. */
+#define RAGRAPH_POSITION_CODES_LONG_ROW 512
+size_t ragraph_position_codes_csr_global_workspace_bytes(int64_t n, int A);
+int ragraph_position_codes_csr_global_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n,
+                                          const int64_t* anchors, int A, float dis_q, float* codes, float* dist, int rounds,
+                                          int resume, int32_t* converged, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Fine-tuning backward (section 7.3 hard part 4).  The matrix parts of a backward pass are the
  * forward entry points again (ragraph_linear_f32 on transposed operands; ragraph_spmm_csr_f32 on the TRANSPOSED CSR: the

@@ -40,12 +40,18 @@ class PositionAwareEncoder:
         return K.floyd_warshall(_dense(adj))
 
     @staticmethod
-    def encode_position_aware_code(adj, num_anchors: int, dis_q: int = 10, anchors: torch.Tensor | None = None):
+    def encode_position_aware_code(adj, num_anchors: int, dis_q: int = 10, anchors: torch.Tensor | None = None,
+                                   rounds: int | None = None):
+        """`rounds`: a fixed number of relaxation rounds (K.position_codes_csr: the capturable form for graphs of more
+        than 40000 nodes); the result is then (codes, converged word on the device)."""
         g: CSRGraph = as_csr(adj.squeeze(0) if isinstance(adj, torch.Tensor) and adj.layout == torch.strided
                              and adj.dim() == 3 else adj)
         if anchors is None:  # PositionAwareEncoder.py:11 draws them from torch's global CPU generator
             anchors = torch.randint(low=0, high=g.n, size=(int(num_anchors),))
-        return K.position_codes_csr(g.rowptr, g.col, g.val, anchors.to(g.device), float(dis_q))
+        if rounds is None:
+            return K.position_codes_csr(g.rowptr, g.col, g.val, anchors.to(g.device), float(dis_q))
+        return K.position_codes_csr(g.rowptr, g.col, g.val, anchors.to(g.device), float(dis_q), rounds=rounds,
+                                    return_converged=True)
 
 
 class ToyGraphBaseFewShot(ToyGraphBase):

@@ -23,6 +23,8 @@ OK, EINVAL, EUNSUPPORTED, EWORKSPACE, EDEVICE = 0, -1, -2, -3, -4
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_LEAKY, ACT_ELU = 0, 1, 2, 3, 4
 TOPK_MAX = 64                # the fused kernels' list limit (RAGRAPH_TOPK_MAX)
 TOPK_ORDERED_MAX = 4096      # ordered top-k over exact fp32 score slabs (RAGRAPH_TOPK_ORDERED_MAX)
+POSITION_CODES_LDS_MAX = 40000     # nodes one anchor's distance vector may have in LDS (ragraph_position_codes_csr_f32)
+POSITION_CODES_LONG_ROW = 512      # RAGRAPH_POSITION_CODES_LONG_ROW: rows with more edges go to a whole workgroup
 
 _vp, _i64, _i32, _f32, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 
@@ -121,6 +123,9 @@ SIGNATURES = {
     "ragraph_floyd_warshall_f32": (_i32, [_vp, _i32, _vp, _vp]),
     "ragraph_position_code_f32": (_i32, [_vp, _i32, _vp, _i32, _f32, _vp, _vp]),
     "ragraph_position_codes_csr_f32": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _f32, _vp, _vp, _vp]),
+    "ragraph_position_codes_csr_global_workspace_bytes": (_sz, [_i64, _i32]),
+    "ragraph_position_codes_csr_global_f32": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _f32, _vp, _vp, _i32, _i32, _vp, _vp, _sz,
+                                                     _vp]),
     "ragraph_act_grad_f32": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
     "ragraph_spmm_csr_prelu_dev_f32": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
     "ragraph_act_grad_prelu_dev_f32": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp]),

@@ -105,6 +105,9 @@ __device__ __forceinline__ float apply_act(float x, int act, float alpha) {
   }
 }
 
+// PositionAwareEncoder.py:6-24: the code of a distance to an anchor (both CSR position-code kernels: rows.hip, position_codes.hip).
+__device__ __forceinline__ float position_code_of(float d, float dis_q) { return (d < dis_q) ? 1.f / (d + 1.f) : 0.f; }
+
 // ---- wave-wide reductions without LDS (gfx9 wave64 DPP) ----------------------------------------------------------------
 // __shfl_xor is a ds_bpermute_b32 -- an LDS round trip per step, six dependent ones per butterfly.  Inside a row of 16 lanes the
 // same exchanges are DPP operands of the adding instruction itself.

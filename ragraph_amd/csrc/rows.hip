@@ -493,7 +493,7 @@ __global__ void __launch_bounds__(1024) anchor_dist_kernel(const int64_t* __rest
   for (int u = tid; u < n; u += 1024) {
     const float d = anchor_d[u];
     if (dist_out) dist_out[(int64_t)u * A + a] = d;
-    codes[(int64_t)u * A + a] = (d < dis_q) ? 1.f / (d + 1.f) : 0.f;
+    codes[(int64_t)u * A + a] = position_code_of(d, dis_q);
   }
 }
 

@@ -1178,11 +1178,28 @@ def position_code(dist: torch.Tensor, anchors: torch.Tensor, dis_q: float = 10.0
     return out
 
 
+# Rounds the eager global path enqueues between two read-backs of the converged word (profiles/position_codes_global.txt).
+POSITION_CODES_ROUNDS_PER_READBACK = 16
+
+
 def position_codes_csr(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, anchors: torch.Tensor,
-                       dis_q: float = 10.0, return_dist: bool = False):
-    """Position-aware codes [n, A] from the CSR of the query batch: shortest-path distances to the A anchors only (one
-    workgroup per anchor, no n x n matrix, one launch) -- PositionAwareEncoder.py:6-24 as the few-shot retrieve uses it
-    on every forward (RAGraph_node_fewshot/ragraph_utils/ToyGraphBase.py:49-50)."""
+                       dis_q: float = 10.0, return_dist: bool = False, rounds: int | None = None,
+                       method: str | None = None, return_converged: bool = False):
+    """Position-aware codes [n, A] from the CSR of the query batch: shortest-path distances to the A anchors only, no
+    n x n matrix -- PositionAwareEncoder.py:6-24 as the few-shot retrieve uses it on every forward
+    (RAGraph_node_fewshot/ragraph_utils/ToyGraphBase.py:49-50).
+
+    `method=None`: n <= 40000 with `rounds=None` takes the LDS kernel (one workgroup per anchor, one launch); anything else
+    the global path (distance vectors in global memory, rows over the whole chip, one launch per round; any n < 2^31).
+    `method="global"` forces the global path.  Both give the same bits.
+    Global path, `rounds=None`: eager -- batches of rounds, one read-back of the converged word per batch, until converged
+    or n rounds in total; cannot be captured.  `rounds=R`: one call, exactly R rounds, no read-back (capturable); the codes
+    are final when the device int32 word `return_converged=True` adds to the result is 1, lower bounds otherwise (the LDS
+    kernel has no such word: None).  Negative weights have no fixpoint on a negative cycle: both paths stop after n rounds."""
+    if method not in (None, "global"):
+        raise ValueError(f"position_codes_csr: method={method!r} (None or 'global')")
+    if rounds is not None and (isinstance(rounds, bool) or int(rounds) != rounds or rounds < 1):
+        raise ValueError(f"position_codes_csr: rounds={rounds!r} (None or an integer >= 1)")
     L = _ready()
     rowptr = _idxc(rowptr, "position_codes_csr.rowptr")
     col = _idxc(col, "position_codes_csr.col", torch.int32)
@@ -1191,9 +1208,39 @@ def position_codes_csr(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tenso
     n, A = rowptr.numel() - 1, anchors.numel()
     codes = torch.empty((n, A), dtype=torch.float32, device=val.device)
     dist = torch.empty((n, A), dtype=torch.float32, device=val.device) if return_dist else None
-    N.check(L.ragraph_position_codes_csr_f32(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), n, anchors.data_ptr(), A,
-                                             float(dis_q), codes.data_ptr(), _ptr(dist), _stream()), "position_codes_csr")
-    return (codes, dist) if return_dist else codes
+    if method is None and rounds is None and n <= N.POSITION_CODES_LDS_MAX:
+        N.check(L.ragraph_position_codes_csr_f32(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), n, anchors.data_ptr(), A,
+                                                 float(dis_q), codes.data_ptr(), _ptr(dist), _stream()), "position_codes_csr")
+        converged = None
+    else:
+        if rounds is None and torch.cuda.is_current_stream_capturing():
+            raise RagraphNativeError("position_codes_csr: the global path reads the converged word back between batches of "
+                                     "rounds; a captured call must pass `rounds` (a fixed number of rounds, no read-back)")
+        nbytes = L.ragraph_position_codes_csr_global_workspace_bytes(n, A)
+        if nbytes == 0:
+            raise RagraphNativeError(f"position_codes_csr: n={n}, A={A} not supported (1 <= n < 2^31, A >= 1)")
+        ws = _workspace(nbytes, val.device)
+        converged = torch.empty(1, dtype=torch.int32, device=val.device)
+
+        def call(r, resume):
+            N.check(L.ragraph_position_codes_csr_global_f32(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), n,
+                                                            anchors.data_ptr(), A, float(dis_q), codes.data_ptr(), _ptr(dist),
+                                                            int(r), int(resume), converged.data_ptr(), ws.data_ptr(),
+                                                            ws.numel(), _stream()), "position_codes_csr(global)")
+        if rounds is not None:
+            call(rounds, 0)
+        else:
+            done = 0
+            while True:
+                r = max(1, min(POSITION_CODES_ROUNDS_PER_READBACK, n - done))
+                call(r, done > 0)
+                done += r
+                if done >= n or int(converged.item()) != 0:
+                    break
+    out = (codes, dist) if return_dist else (codes,)
+    if return_converged:
+        out = out + (converged,)
+    return out if len(out) > 1 else out[0]
 
 
 def sigmoid_gate(x: torch.Tensor, z: torch.Tensor) -> torch.Tensor:

@@ -91,6 +91,12 @@ class ToyGraphBase:
         # structure_weight * cos(position codes) + semantic_weight * cos(embeddings) (RAGraph_node_fewshot/.../ToyGraphBase.py:47-65)
         self.structure_weight = 0.0
         self.semantic_weight = 0.999
+        # Position codes of the query graph (search_positions): None = to the fixpoint (graphs of more than 40000 nodes then
+        # read a converged word back between batches of rounds, which a stream capture cannot record); R = exactly R
+        # relaxation rounds and no read-back.  last_position_converged: the device int32 word of the last fixed-round call
+        # (1 = the codes are final), never read back here.
+        self.position_rounds = None
+        self.last_position_converged = None
 
     # ---- bank state (attribute names of the reference) ---------------------------------------------------------
     @property
@@ -170,7 +176,11 @@ class ToyGraphBase:
             raise K.RagraphNativeError("structure-aware retrieval: pass `anchors` to a captured call (drawn on the host "
                                        "generator otherwise: PositionAwareEncoder.py:11)")
         from ..RAGraph_fewshot import PositionAwareEncoder
-        return PositionAwareEncoder.encode_position_aware_code(search_adj, self.num_anchors, self.dis_q, anchors)
+        if self.position_rounds is None:
+            return PositionAwareEncoder.encode_position_aware_code(search_adj, self.num_anchors, self.dis_q, anchors)
+        codes, self.last_position_converged = PositionAwareEncoder.encode_position_aware_code(
+            search_adj, self.num_anchors, self.dis_q, anchors, rounds=self.position_rounds)
+        return codes
 
     # ---- build (the step before the hot path; deterministic part) -----------------------------------------------
     def build_toy_graph(self, resource_dataset):
