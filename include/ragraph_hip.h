@@ -178,7 +178,10 @@ size_t ragraph_topk_cosine_filtered_workspace_bytes(int64_t B, int64_t N, int D,
  * for (answered by the exact scan, counted in *overflow), [18] / [19] the smallest / largest final exact k-th best score of
  * the call's queries as order-preserving ints (bits(x) for x >= 0, bits(x) ^ 0x7FFFFFFF below: csrc/filter_common.h f2ord; INT_MAX /
  * INT_MIN: none recorded), [20] the call's final *overflow (one copy of these words tells the owner of the bank
- * everything), [21..32) reserved.  sum / queries = candidates per query: what a level's rescoring costs.  The owner of a bank reads them back
+ * everything), [21] 1 if a TIGHT bound was in force on top of the prior (ragraph_topk_cosine_filtered_set_tight_prior), [22]
+ * soft misses (queries whose k-th best found was below the tight bound: repaired on the device, NOT counted in *overflow),
+ * [23] the repair that ran (0 none, 1 the 256-query call of the direct kernel, 2 one more level for every query), [24..32)
+ * reserved.  sum / queries = candidates per query: what a level's rescoring costs.  The owner of a bank reads them back
  * asynchronously (ragraph_amd/kernels_index.py: a bank whose int8 levels pass hundreds of candidates per query without
  * overflowing is slower on int8 than on bf16 -- the overflow count alone would never show it). */
 size_t ragraph_topk_cosine_filtered_stats_offset(size_t ws_bytes);
@@ -212,6 +215,21 @@ int ragraph_topk_cosine_filtered_max_i8_levels(int n);
  * The sharded entry honours it too (below): there the PROOF is the caller's, over the merged lists.  The reference has no
  * counterpart (torch.topk over the full score matrix, ToyGraphBase.py:66-67): this only removes work. */
 float ragraph_topk_cosine_filtered_set_prior(float theta_prior);
+/* A TIGHT speculative bound t on top of the prior p, for the CALLING THREAD's following filtered calls (thread-local; NaN =
+ * none, the default); returns the previous value.  Honoured by single-bank calls of more than 256 queries (the ring kernel's)
+ * that also run under a valid prior p < t, outside HIP-graph capture by convention of the caller; ignored otherwise -- by the
+ * sharded entry, the direct and single-launch kernels' calls -- and for shapes whose idle workspace cannot hold the repair's
+ * buffers: those live in the candidate lists the level's rescoring has consumed and in the bound pass's part maxima, so the
+ * workspace size does not change, and a call whose lists + part maxima are smaller than the 256-query repair's lists, rows
+ * and operand image (fewer than about 300 queries at D = 256) runs under the prior alone.
+ * Under t the call runs ONE level over the whole bank from theta = t (no theta launch; plan / i8_levels report it while the
+ * thread has both bounds set).  A query whose k-th best found reaches t is proven.  Any other is a SOFT miss: the k-th best
+ * it found, floored by p, is a lower bound as good as p, and one more pass with that per-query bound finds what the first
+ * left out -- for up to 256 soft misses a compact 256-query call of the direct kernel, for more one more ring level in which
+ * proven queries pass nothing.  Every repair launch is enqueued unconditionally and returns at once when the device count
+ * (statistics word [22]) says so: no read-back.  Then the verdict against p and the exact scan as above: a hard miss is still
+ * a scan.  The result has the bits of ragraph_topk_cosine_f32 for ANY t. */
+float ragraph_topk_cosine_filtered_set_tight_prior(float t);
 int ragraph_topk_cosine_filtered_f32(const float* Q, int64_t B, const float* Kn, const float* Kp, const uint16_t* Kb,
                                      int64_t N, int D, int k, int64_t idx_base, float* out_scores, int64_t* out_idx,
                                      int* overflow, int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream);

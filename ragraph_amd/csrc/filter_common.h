@@ -206,6 +206,19 @@ constexpr int FILTER_COUNT_STRIDE = 32;
 constexpr int FILTER_TICKET_SLOT = 16;  // int of a query's line that counts its finished rescoring workgroups
 __host__ __device__ constexpr int filter_count_stride(int64_t B) { return B < 2048 ? FILTER_COUNT_STRIDE : 1; }
 
+// A launch that is enqueued unconditionally and returns at its first instructions unless lo <= *word <= hi (word = NULL: always
+// runs): the repair launches behind a tight speculative bound (filter_verify_fixup.h), gated by the call's soft-miss count.
+constexpr int FILTER_REPAIR_Q = 256;  // queries of the compact repair batch: the direct kernel's largest call
+struct FilterGate {
+  const int* word;
+  int lo, hi;
+};
+__device__ __forceinline__ bool filter_gate_closed(const FilterGate& g) {
+  if (!g.word) return false;
+  const int n = *g.word;
+  return n < g.lo || n > g.hi;
+}
+
 // One filter launch of the direct kernel (topk_filter_direct.hip): up to 256 queries against keys [key0, key1) of the
 // bf16 copy (key0 a multiple of 32).  bound_groups > 0: the BOUND pass -- no thresholds, no candidates, the launch
 // records per query the best approximate score of each of bound_groups consecutive parts of the range into gmax_out.
@@ -225,6 +238,7 @@ struct DirectArgs {
   int scored;             // (i8) the lists hold {key, I} pairs in int2 slots, I = an upper bound of the integer sum that
                           // admitted the key (the lane's largest, rounded up to a multiple of 256): topk_filter.hip,
                           // topk_rescore_scored_kernel
+  FilterGate gate;        // (repair launches: filter_verify_fixup.h)
   int i8;                 // the pass runs on the int8 copy: Kb = that copy, Qb = the queries' int8 image (Qb8 of the prepare
                           // launch: block (qg * D/64 + t), lane j + 16 g = elements 64 t + 16 g .. + 15 of query 16 qg + j)
 };

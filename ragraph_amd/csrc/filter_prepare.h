@@ -15,7 +15,8 @@
 // SPECULATIVE first bound (ragraph_topk_cosine_filtered_set_prior), [17] queries whose speculation failed (answered by the
 // exact scan), [18] / [19] the smallest / largest final exact k-th best score of the call's queries as order-preserving
 // ints (f2ord; what the owner of the bank builds the next call's prior from), [20] the call's final *overflow (so that ONE
-// copy of these words tells the owner everything), [21..32) reserved.
+// copy of these words tells the owner everything), [21] a tight bound was in force, [22] soft misses, [23] the repair that ran
+// (filter_verify_fixup.h), [24..32) reserved.
 constexpr int FILTER_STATS_INTS = 32;
 constexpr int FILTER_STATS_MAGIC = 0x52414753;
 __device__ __forceinline__ void note_candidates(int* cstat, int64_t b, int n) {

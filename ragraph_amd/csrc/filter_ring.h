@@ -97,6 +97,7 @@ __global__ void __launch_bounds__(512, 2) topk_filter_kernel(FilterParams p) {
   // same change measured +- 0; D = 256 with six groups has no registers to spare: the quads spilled, and start values moved
   // into the accumulators by v_mov cost four times what the fold saves).  tools/gpu_fold_ab.sh
   constexpr bool FOLD = RG_RING_FOLD && I8 && !PIPE && !BOUND && D == 64;
+  if (filter_gate_closed(p.gate)) return;  // (kernel-uniform, before any barrier: a repair level with nothing to repair)
   extern __shared__ float4 fsmem4[];
   char* smem = reinterpret_cast<char*>(fsmem4);
   unsigned* full = reinterpret_cast<unsigned*>(smem + C::SLOTS * C::STAGE_BYTES);  // [SLOTS] then freec [SLOTS]

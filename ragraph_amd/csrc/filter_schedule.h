@@ -50,6 +50,7 @@ struct FilterEnv {
   int scored_shards;    // RAGRAPH_FILTER_SCORED_SHARDS: sharded banks of up to this many shards keep scored lists (default 2)
   int spec_two_shards;  // RAGRAPH_FILTER_SPEC_SHARDS_TWO_LEVELS: from this many shards a three-level plan runs two levels
                         // under a prior (default 2: every sharded bank; 0 = never)
+  int tight_levels;     // RAGRAPH_FILTER_TIGHT_LEVELS: levels of a call under a tight bound (default 1; 2: the plan's last two -- A/B)
 };
 static int filter_env_int(const char* name, int dflt) {
   const char* e = getenv(name);
@@ -59,7 +60,8 @@ static FilterEnv filter_env() {
   static const int scored_shards = filter_env_int("RAGRAPH_FILTER_SCORED_SHARDS", 2);
   static const int spec_two_shards = filter_env_int("RAGRAPH_FILTER_SPEC_SHARDS_TWO_LEVELS", 2);
   return {filter_env_int("RAGRAPH_FILTER_I8", -1), filter_env_int("RAGRAPH_FILTER_SCORED", -1), filter_env_int("RAGRAPH_FILTER_PIPE", 1),
-          filter_env_int("RAGRAPH_FILTER_PARTNER_LEAD", 1), filter_env_int("RAGRAPH_FILTER_I8_QW", 0), scored_shards, spec_two_shards};
+          filter_env_int("RAGRAPH_FILTER_PARTNER_LEAD", 1), filter_env_int("RAGRAPH_FILTER_I8_QW", 0), scored_shards, spec_two_shards,
+          filter_env_int("RAGRAPH_FILTER_TIGHT_LEVELS", 1)};
 }
 
 // Scored candidate lists for the int8 levels (topk_rescore_scored_kernel): calls whose rescoring is bound by the row
@@ -144,6 +146,7 @@ struct FilterShape {
   bool exact_level0;     // size queries: the plan if the bound pass gives way to an exact level 0 (see filter_call_plan)
   FilterEnv env;
   int cus;               // filter_device_cus()
+  float tight;           // the thread's tight speculative bound (NaN: none; honoured under a valid prior below it only)
 };
 
 // Sharded banks of up to this many shards keep the SCORED lists on their int8 levels (and the schedule that goes with them):
@@ -415,7 +418,19 @@ struct FilterCall {
                            // call whose levels all run on the int8 copy and that has no bound pass, e.g. every call under a
                            // prior, saves writing 2 D bytes per query
   int first_phase;         // sharded calls: the exchange is called at phases first_phase .. nlev - 1
+  bool tight;              // the levels start from theta = the tight bound; behind them the soft verdict and the repair launches
+                           // (run_filtered step 6b), whose rescoring is the call's FINAL one -- no level's is (level_final)
+  bool repair_scored;      // ... the 256-query repair keeps scored lists
+  int level_final;         // the level whose rescoring is the call's final one (adds idx_base, lists overflows), or -1
 };
+
+// What the 256-query repair behind a tight bound keeps besides its candidate lists: the gathered rows, their normalised form and
+// operand image, its own small per-query arrays and result rows (run_filtered carves them: FilterRepairWs).
+static size_t filter_repair_bytes(int D, int k, size_t slot_bytes) {
+  const size_t q = FILTER_REPAIR_Q;
+  return q * FILTER_LIST_CAP * slot_bytes + 2 * q * D * sizeof(float) + q * D * sizeof(uint16_t) + q * FILTER_COUNT_STRIDE * sizeof(int) +
+         align_up(q * k * sizeof(float), 256) + align_up(q * k * sizeof(int64_t), 256) + 16 * 1024 /* ten arrays of <= 1 KiB, aligned */;
+}
 
 static void filter_drop_first_level(FilterSchedule& sc) {
   for (int l = 0; l + 1 < sc.nlev; ++l) sc.ends[l] = sc.ends[l + 1];
@@ -498,6 +513,25 @@ static FilterCall filter_call_plan(const FilterShape& in, FilterSchedule sc) {
     c.spec = prior_ok && sc.bound_keys > 0 && N == plan_N;
     if (c.spec) drop_first_level_under_prior();
   }
+  // A TIGHT bound t (ragraph_topk_cosine_filtered_set_tight_prior) on top of the prior p: one bank, the ring kernel's batch sizes,
+  // p < t.  Every query starts from theta = t, and no intermediate level can sharpen beyond a bound that is about the lowest
+  // k-th best the bank has answered (the k-th best of a quarter of the bench's bank is 0.246 against t = 0.249), so the call runs
+  // ONE level over [0, N) -- on int8, with scored lists, where the plan's last level would -- and no theta launch.  A query
+  // whose k-th best found is below t is a SOFT miss: repaired on the device from max(p, what it found), see run_filtered.
+  // Workspace rule: the repair's buffers live in regions that are idle by then -- the candidate lists the level's rescoring
+  // has consumed and gmax behind them (no bound pass under a prior) -- and the size queries do not change; a shape whose lists
+  // + gmax are smaller than filter_repair_bytes (fewer than about 300 queries at D = 256) ignores the tight bound.
+  // RAGRAPH_FILTER_TIGHT_LEVELS=2 keeps the plan's last two levels under the tight bound (A/B): the bench step, interleaved on one
+  // box, 19.05 / 19.01 ms with two levels against 18.66 / 18.70 with one; up to 4096 queries the call under the prior runs one
+  // level anyway.  The step against the three levels under the prior alone: 19.68 - 19.83 -> 18.30 - 18.31 ms (profiles/tight_prior.txt).
+  {
+    const size_t slot = c.scored_slots ? sizeof(int2) : sizeof(int);
+    const size_t idle = align_up((size_t)B * c.cap * slot, 256) + align_up((size_t)B * filter_bound_parts(k, INT64_MAX, 256) * sizeof(int), 256);
+    c.tight = c.spec && !in.exchange && B > 256 && in.tight == in.tight && in.tight > in.prior && in.tight < 2.f &&
+              idle >= filter_repair_bytes(D, k, slot);
+  }
+  if (c.tight)
+    while (sc.nlev > (in.env.tight_levels == 2 ? 2 : 1)) filter_drop_first_level(sc);
   const bool bound = sc.bound_keys > 0 && !c.spec;
   c.level0 = c.spec ? FILTER_L0_NONE : (bound ? FILTER_L0_BOUND : (sc.slab0 ? FILTER_L0_SLAB : FILTER_L0_TILE));
   c.level0_bytes = sc.bound_keys > 0 ? 0
@@ -520,5 +554,7 @@ static FilterCall filter_call_plan(const FilterShape& in, FilterSchedule sc) {
     // step, profiles/r3_emul.txt.  RAGRAPH_FILTER_SCORED_SHARDS = largest shard count that takes them: A/B.)
     lv.scored = lv.int8 && (!in.exchange || in.n_shards <= in.env.scored_shards) && c.scored_slots;
   }
+  c.level_final = c.tight ? -1 : c.nlev - 1;
+  c.repair_scored = c.tight && c.level[c.nlev - 1].scored;
   return c;
 }

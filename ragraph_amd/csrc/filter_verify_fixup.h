@@ -53,6 +53,92 @@ __global__ void __launch_bounds__(256) filter_verify_prior_kernel(const float* _
   }
 }
 
+// ---- a TIGHT speculative bound t on top of the prior p (filter_schedule.h: FilterCall::tight) -------------------------------
+// The levels filtered with theta = max(t, the running exact k-th best).  Behind their rescoring:
+//   * a query whose k-th best found is >= t is PROVEN: every key that scores at least that passed.  theta[q] = +inf -- it
+//     passes nothing in the repair.
+//   * any other unflagged query is a SOFT miss.  Its k-th best found (exact score of a real key), floored by p, is a lower
+//     bound of its final k-th best as good as p itself: theta[q] = max(p, k-th best found), or p when it found fewer than k.
+//     Its row number goes to list[] (the first FILTER_REPAIR_Q of them; stats[22] counts them all), and its running result is
+//     RESET to the empty row: the repair relists every key it needs, including those already found, so no key is merged
+//     twice (a winner listed twice breaks the selection: docs/HISTORY.md, round 3).
+//   * flagged queries (2: zero query, 1: overflowed list) are left to the final rescoring and the fixup launch as ever.
+// Then the repair, enqueued unconditionally and gated by stats[22] on the device (FilterGate), no host read-back:
+//   1 .. 256 soft misses: filter_repair_gather_kernel copies their raw rows into a compact batch of 256 (zero rows beyond the
+//     count -- zero queries, answered without work); filter_prep_kernel prepares it; ONE pass of the direct kernel over [0, N)
+//     with the per-query theta and its rescoring; filter_repair_scatter_kernel writes the rows back (local indices) or hands
+//     a row whose repair list overflowed to the exact scan (flag 1).
+//   more: one more ring level over [0, N) for all B queries with theta[] -- proven queries pass nothing -- the bounded worst case.
+// Behind either, the call's FINAL rescoring launch (merge with the running rows, + idx_base, overflow lists), then the
+// verdict against p (filter_verify_prior_kernel: a repaired query whose final k-th best is below p was repaired from a bound
+// that was too high -- a hard miss, scanned) and the fixup launch, unchanged.
+// Statistics words: [21] = 1 a tight bound was in force, [22] soft misses, [23] the repair that ran (0 none, 1 the 256-query
+// call, 2 the all-queries level).
+__global__ void __launch_bounds__(256) filter_tight_verdict_kernel(float* __restrict__ out_s, int64_t* __restrict__ out_i, int64_t B,
+                                                                   int k, float tight, float prior,
+                                                                   const unsigned char* __restrict__ flag, float* __restrict__ theta,
+                                                                   int* __restrict__ list, int* __restrict__ stats) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  if (q == 0) stats[21] = 1;
+  bool soft = false;
+  float kth = RG_NEG_INF;
+  if (q < B) {
+    kth = out_s[q * k + k - 1];
+    soft = flag[q] == 0 && !(kth >= tight);
+    theta[q] = soft ? fmaxf(prior, kth) : __builtin_huge_valf();
+  }
+  // one atomic per wave that saw any (a flood of soft misses would serialise on the one counter otherwise)
+  const unsigned long long m = __ballot(soft);
+  if (m == 0ull) return;  // (wave-uniform)
+  int base = 0;
+  if (lane == 0) base = atomicAdd(stats + 22, __popcll(m));
+  base = __shfl(base, 0);
+  if (!soft) return;
+  const int pos = base + __popcll(m & ((1ull << lane) - 1ull));
+  if (pos < FILTER_REPAIR_Q) list[pos] = (int)q;
+  for (int j = 0; j < k; ++j) {
+    out_s[q * k + j] = RG_NEG_INF;
+    out_i[q * k + j] = INT64_MAX;
+  }
+}
+
+// One wave per row of the compact batch.  (Always writes all 256 rows: zero rows when there is nothing for the 256-query
+// repair to do, so the launches behind it read defined memory whatever the count.)
+template <int D>
+__global__ void __launch_bounds__(64) filter_repair_gather_kernel(const float* __restrict__ Q, const float* __restrict__ theta,
+                                                                  const int* __restrict__ list, float* __restrict__ Q2,
+                                                                  float* __restrict__ theta2, int* __restrict__ stats) {
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int n = stats[22];
+  if (row == 0 && lane == 0) stats[23] = n == 0 ? 0 : (n <= FILTER_REPAIR_Q ? 1 : 2);
+  const bool live = n <= FILTER_REPAIR_Q && row < n;
+  const int64_t q = live ? list[row] : 0;
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (live && lane < D / 4) v = reinterpret_cast<const float4*>(Q + q * D)[lane];
+  if (lane < D / 4) reinterpret_cast<float4*>(Q2 + (int64_t)row * D)[lane] = v;
+  if (lane == 0) theta2[row] = live ? theta[q] : 0.f;
+}
+
+__global__ void __launch_bounds__(64) filter_repair_scatter_kernel(const int* __restrict__ list, const float* __restrict__ s2,
+                                                                   const int64_t* __restrict__ i2,
+                                                                   const unsigned char* __restrict__ flag2, int k,
+                                                                   float* __restrict__ out_s, int64_t* __restrict__ out_i,
+                                                                   unsigned char* __restrict__ flag, const int* __restrict__ stats) {
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int n = stats[22];
+  if (n < 1 || n > FILTER_REPAIR_Q || row >= n) return;
+  const int64_t q = list[row];
+  if (flag2[row] != 0) {  // its repair list overflowed: the final rescoring lists the row for the exact scan
+    if (lane == 0) flag[q] = 1;
+    return;
+  }
+  if (lane < k) {
+    out_s[q * k + lane] = s2[(int64_t)row * k + lane];
+    out_i[q * k + lane] = i2[(int64_t)row * k + lane];
+  }
+}
+
 // Sharded banks under a speculative first bound: the verdict of the rows' OWNER, behind the merge of the shards' lists.  One
 // workgroup walks the R merged rows: a row is proven iff its k-th best reaches the prior (an all-zero query -- every score +0 --
 // is answered by index order and needs no proof); out[0] = rows that missed, out[1] = -(smallest proven k-th best), out[2] =

@@ -83,6 +83,7 @@ struct FilterParams {
   // bound pass (BOUND kernels): per query, the maxima of `ngroups` consecutive stage ranges of the launch's key range
   int* gmax;              // [B, ngroups] as order-preserving ints (f2ord), pre-filled with f2ord(-inf)
   int ngroups;
+  FilterGate gate;        // a repair level behind a tight bound: returns at once unless the soft-miss count opens it
 };
 
 __device__ __forceinline__ void fring_wait(unsigned* ctr, unsigned target) {
@@ -209,6 +210,13 @@ extern "C" float ragraph_topk_cosine_filtered_set_prior(float theta_prior) {
 extern "C" int ragraph_topk_cosine_filtered_max_i8_levels(int n) {
   const int old = t_max_i8_levels;
   t_max_i8_levels = n < 0 ? -1 : n;
+  return old;
+}
+// A TIGHT speculative bound on top of the prior (NaN = none, the default): see filter_call_plan and filter_verify_fixup.h.
+static thread_local float t_tight = __builtin_nanf("");
+extern "C" float ragraph_topk_cosine_filtered_set_tight_prior(float t) {
+  const float old = t_tight;
+  t_tight = t;
   return old;
 }
 int ragraph::filter_thread_i8_cap() { return t_max_i8_levels; }  // (topk_small.hip: the single-launch call honours the same cap)
@@ -364,7 +372,15 @@ static int filter_shape_code(int64_t B, int64_t N, int D, int k) {
 
 // The shape a query asks about: one bank of N rows, or the largest of n_shards shards, without a prior.
 static FilterShape filter_query_shape(int64_t B, int64_t N, int D, int k, int n_shards, bool exchange) {
-  return {B, N, N, D, k, n_shards, exchange, __builtin_nanf(""), -1, false, filter_env(), filter_device_cus()};
+  return {B, N, N, D, k, n_shards, exchange, __builtin_nanf(""), -1, false, filter_env(), filter_device_cus(), __builtin_nanf("")};
+}
+// The plan queries follow the thread's two bounds when BOTH are set and the tight one lies above the prior (the plan of a call
+// under a tight bound); any other setting reports the plan without a prior, as ever.
+static void filter_query_follow_tight(FilterShape& in) {
+  if (t_prior == t_prior && t_tight == t_tight && t_tight > t_prior) {
+    in.prior = t_prior;
+    in.tight = t_tight;
+  }
 }
 
 // A call may replace the planned bound pass by an exact level 0 (a shard shorter than twice the prefix, a shard's share of
@@ -399,13 +415,15 @@ extern "C" int ragraph_topk_cosine_filtered_i8_levels(int64_t B, int64_t N, int 
   if (filter_shape_code(B, N, D, k) != RAGRAPH_OK) return 0;
   FilterShape in = filter_query_shape(B, N, D, k, 1, false);
   in.i8_cap = t_max_i8_levels;
+  filter_query_follow_tight(in);
   return filter_call_plan(in, filter_schedule(in)).i8_levels;
 }
 
 extern "C" int ragraph_topk_cosine_filtered_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]) {
   RG_REQUIRE(plan, RAGRAPH_EINVAL, "topk_cosine_filtered_plan: null pointer");
   RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered_plan", B, N, D, k);
-  const FilterShape in = filter_query_shape(B, N, D, k, 1, false);
+  FilterShape in = filter_query_shape(B, N, D, k, 1, false);
+  filter_query_follow_tight(in);
   // (the plan of one whole bank IS its schedule: filter_schedule leaves such a bank bound_keys <= N / 4 or <= ends[0] < N / 2
   // and n0 <= N, so filter_call_plan's adjustments to a shard's own length change none of the words below)
   const FilterCall c = filter_call_plan(in, filter_schedule(in));
@@ -455,12 +473,12 @@ static int launch_ring(FilterParams p, int64_t B, int CUS, int prof_slot, hipStr
     set_error("topk_cosine_filtered: cannot raise dynamic LDS limit: %s", hipGetErrorString(e));
     return RAGRAPH_EDEVICE;
   }
-  if (t_prof) (void)hipEventRecord(t_prof->ev[2 * prof_slot], st);
+  if (t_prof && prof_slot >= 0) (void)hipEventRecord(t_prof->ev[2 * prof_slot], st);
   hipLaunchKernelGGL((topk_filter_kernel<D, QW, BOUND, I8, SCORED, PIPE>), dim3((unsigned)CUS), dim3(C::THREADS), C::LDS_BYTES, st, p);
-  if (t_prof) (void)hipEventRecord(t_prof->ev[2 * prof_slot + 1], st);
+  if (t_prof && prof_slot >= 0) (void)hipEventRecord(t_prof->ev[2 * prof_slot + 1], st);
   RG_CHECK_LAUNCH("topk_cosine_filtered(filter)");
   ring_stamps_report(BOUND, I8);
-  ring_timing_report(prof_slot, D);
+  if (prof_slot >= 0) ring_timing_report(prof_slot, D);
   return RAGRAPH_OK;
 }
 
@@ -541,11 +559,12 @@ static int launch_ring_variant(const PassVariant& v, const FilterParams& p, int6
 }
 
 // One pass over keys [key0, key1) of the bf16 copy or (int8) of the int8 copy: a filter level (bound_groups = 0: candidates of
-// every query whose threshold `thr` describes) or the bound pass (bound_groups part maxima into gmax).
+// every query whose threshold `thr` describes) or the bound pass (bound_groups part maxima into gmax).  prof_slot < 0: a repair
+// launch -- not a level, not timed; `gate`: see FilterGate.
 template <int D>
 static int run_pass(const FilterWs& f, const uint16_t* Kb, const signed char* Kb8, int64_t B, int64_t key0, int64_t key1,
                     const FilterThr& thr, int cap, int bound_groups, bool int8, bool scored, const FilterEnv& env, int cus,
-                    int prof_slot, hipStream_t st) {
+                    int prof_slot, hipStream_t st, FilterGate gate = FilterGate{nullptr, 0, 0}) {
   const PassVariant v = filter_pass_variant(D, B, key0, key1, bound_groups > 0, int8, scored, cus, env);
   const uint16_t* keys = v.i8 ? reinterpret_cast<const uint16_t*>(Kb8) : Kb;
   // (the queries' operand image of the copy's type; NULL beyond FILTER_QB_MAX_B queries: converted per segment)
@@ -566,9 +585,10 @@ static int run_pass(const FilterWs& f, const uint16_t* Kb, const signed char* Kb
     a.nsub = rescore_slices(B, thr.k);
     a.gmax_out = f.gmax;
     a.bound_groups = bound_groups;
-    if (t_prof) (void)hipEventRecord(t_prof->ev[2 * prof_slot], st);
+    a.gate = gate;
+    if (t_prof && prof_slot >= 0) (void)hipEventRecord(t_prof->ev[2 * prof_slot], st);
     const int rc = launch_filter_direct<D>(a, st);
-    if (t_prof) (void)hipEventRecord(t_prof->ev[2 * prof_slot + 1], st);
+    if (t_prof && prof_slot >= 0) (void)hipEventRecord(t_prof->ev[2 * prof_slot + 1], st);
     return rc;
   }
   const int stage_keys = FILTER_STAGE_BYTES / ((v.i8 ? 1 : 2) * D);  // (bf16: key0 is a multiple of 256)
@@ -590,6 +610,7 @@ static int run_pass(const FilterWs& f, const uint16_t* Kb, const signed char* Kb
   p.stage_base = key0 / stage_keys;
   p.nstages_total = cdiv(key1 - key0, stage_keys);
   p.partner_lead = env.partner_lead;
+  p.gate = gate;
   return launch_ring_variant<D>(v, p, B, cus, prof_slot, st);
 }
 
@@ -706,6 +727,99 @@ static int run_exact_participant(const FilteredArgs& a, const FilterCall& c) {
   return RAGRAPH_OK;
 }
 
+// The 256-query repair's buffers, carved from the idle span [f.cand, f.theta) of the call's workspace (filter_call_plan's
+// workspace rule guarantees filter_repair_bytes of it).
+struct FilterRepairWs {
+  FilterWs f;        // what run_pass / run_rescore read of a call of FILTER_REPAIR_Q queries
+  int* list;         // [256] row numbers of the soft misses
+  float* Q;          // [256, D] their raw rows
+  float* theta;      // [256] their bounds
+  float* out_s;      // [256, k] the repaired rows (local indices)
+  int64_t* out_i;
+  int* dummy;        // (the prepare launch's *overflow = 0)
+};
+static FilterRepairWs filter_repair_carve(const FilterWs& f, int D, int k, bool int8, size_t slot_bytes) {
+  char* w = reinterpret_cast<char*>(f.cand);
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* ptr = w + off;
+    off += align_up(bytes, 256);
+    return ptr;
+  };
+  const size_t q = FILTER_REPAIR_Q;
+  FilterRepairWs r{};
+  r.f.cand = reinterpret_cast<int*>(take(q * FILTER_LIST_CAP * slot_bytes));
+  r.Q = reinterpret_cast<float*>(take(q * D * sizeof(float)));
+  r.f.Qn = reinterpret_cast<float*>(take(q * D * sizeof(float)));
+  if (int8) r.f.Qb8 = reinterpret_cast<signed char*>(take(q * D));
+  else r.f.Qb = reinterpret_cast<uint16_t*>(take(q * D * sizeof(uint16_t)));
+  r.f.count = reinterpret_cast<int*>(take(q * FILTER_COUNT_STRIDE * sizeof(int)));
+  r.out_s = reinterpret_cast<float*>(take(q * k * sizeof(float)));
+  r.out_i = reinterpret_cast<int64_t*>(take(q * k * sizeof(int64_t)));
+  r.list = reinterpret_cast<int*>(take(q * sizeof(int)));
+  r.theta = reinterpret_cast<float*>(take(q * sizeof(float)));
+  r.f.eq = reinterpret_cast<float*>(take(q * sizeof(float)));
+  r.f.eq8 = reinterpret_cast<float*>(take(q * sizeof(float)));
+  r.f.qscale = reinterpret_cast<float*>(take(q * sizeof(float)));
+  r.f.flag = reinterpret_cast<unsigned char*>(take(q));
+  r.dummy = reinterpret_cast<int*>(take(sizeof(int)));
+  r.f.theta = r.theta;
+  r.f.overflow_list = f.overflow_list;   // (never written: the repair's rescoring is not a final one)
+  r.f.fix_done = f.fix_done;
+  return r;
+}
+
+// Step 6b of a call under a tight bound (the comment block in filter_verify_fixup.h tells the whole story).
+template <int D>
+static int run_tight_repair(const FilteredArgs& a, const FilterCall& c, const FilterShape& in, const FilterWs& f, FilterThr thr,
+                            const signed char* K8, int* stats, hipStream_t st) {
+  const int64_t B = a.B, N = a.N;
+  const int k = a.k;
+  const FilterLevel& lv = c.level[c.nlev - 1];
+  const size_t slot = c.scored_slots ? sizeof(int2) : sizeof(int);
+  RG_REQUIRE((size_t)(reinterpret_cast<char*>(f.theta) - reinterpret_cast<char*>(f.cand)) >= filter_repair_bytes(D, k, slot),
+             RAGRAPH_EWORKSPACE, "topk_cosine_filtered: the repair's buffers do not fit the idle lists");
+  const FilterRepairWs r = filter_repair_carve(f, D, k, lv.int8, slot);
+  hipLaunchKernelGGL(filter_tight_verdict_kernel, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, a.out_scores, a.out_idx, B, k,
+                     in.tight, in.prior, f.flag, f.theta, r.list, stats);
+  RG_CHECK_LAUNCH("topk_cosine_filtered(soft verdict)");
+  // 1 .. 256 soft misses: a compact call of the direct kernel
+  hipLaunchKernelGGL(filter_repair_gather_kernel<D>, dim3(FILTER_REPAIR_Q), dim3(64), 0, st, a.Q, f.theta, r.list, r.Q, r.theta, stats);
+  RG_CHECK_LAUNCH("topk_cosine_filtered(repair gather)");
+  hipLaunchKernelGGL((filter_prep_kernel<D, 1>), dim3(FILTER_REPAIR_Q / 4), dim3(256), 0, st, r.Q, (int64_t)FILTER_REPAIR_Q, r.f.Qn,
+                     r.f.eq, r.f.count, r.f.flag, r.dummy, (int*)nullptr, k, r.f.Qb, filter_count_stride(FILTER_REPAIR_Q),
+                     lv.int8 ? r.f.eq8 : nullptr, r.f.qscale, r.f.Qb8, r.f.fix_done, (int*)nullptr, FilterStatsInit{},
+                     (float*)nullptr, 0.f);
+  RG_CHECK_LAUNCH("topk_cosine_filtered(repair prepare)");
+  FilterThr thr2 = thr;
+  thr2.theta = r.theta;
+  thr2.prev_scores = nullptr;
+  thr2.gmax = nullptr;
+  thr2.eq = r.f.eq;
+  thr2.eq8 = r.f.eq8;
+  thr2.qscale = r.f.qscale;
+  thr2.flag = r.f.flag;
+  int rc = run_pass<D>(r.f, a.Kb, K8, FILTER_REPAIR_Q, 0, N, thr2, FILTER_LIST_CAP, 0, lv.int8, c.repair_scored, in.env, in.cus, -1, st,
+                       FilterGate{stats + 22, 1, FILTER_REPAIR_Q});
+  if (rc != RAGRAPH_OK) return rc;
+  rc = run_rescore<D>(r.f, a.Kn, N, FILTER_REPAIR_Q, FILTER_LIST_CAP, k, 0, 0, 0, r.out_s, r.out_i, r.dummy,
+                      rescore_kind(FILTER_REPAIR_Q, k, c.repair_scored, false), thr2, nullptr, st);
+  if (rc != RAGRAPH_OK) return rc;
+  hipLaunchKernelGGL(filter_repair_scatter_kernel, dim3(FILTER_REPAIR_Q), dim3(64), 0, st, r.list, r.out_s, r.out_i, r.f.flag, k,
+                     a.out_scores, a.out_idx, f.flag, stats);
+  RG_CHECK_LAUNCH("topk_cosine_filtered(repair scatter)");
+  // more than 256: one more level for everybody (proven queries carry theta = +inf)
+  thr.theta = f.theta;
+  thr.gmax = nullptr;
+  thr.prev_scores = a.out_scores;
+  rc = run_pass<D>(f, a.Kb, K8, B, 0, N, thr, c.cap, 0, lv.int8, lv.scored, in.env, in.cus, -1, st,
+                   FilterGate{stats + 22, FILTER_REPAIR_Q + 1, INT_MAX});
+  if (rc != RAGRAPH_OK) return rc;
+  // the call's final rescoring: the level's lists (empty unless it ran) merged with the running rows
+  return run_rescore<D>(f, a.Kn, N, B, c.cap, k, a.idx_base, 1, 1, a.out_scores, a.out_idx, a.overflow,
+                        rescore_kind(B, k, lv.scored, false), thr, nullptr, st);
+}
+
 // Steps 3 - 7 of a call (1, 2: filtered_entry): executes the plan `c` that filter_call_plan made of the shape `in` -- carve,
 // prepare, first bound, the levels, verify / fixup -- and decides nothing itself.
 template <int D>
@@ -747,7 +861,7 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
   hipLaunchKernelGGL((filter_prep_kernel<D, R_>), dim3((unsigned)cdiv(B <= FILTER_QB_MAX_B ? (B + 31) / 32 * 32 : B, 4 * (R_))), dim3(256), 0, st, a.Q, B, \
                      f.Qn, f.eq, f.count, f.flag, a.overflow, bound ? f.gmax : nullptr, c.parts, c.bf16_image ? f.Qb : nullptr,         \
                      filter_count_stride(B), c.i8_levels > 0 ? f.eq8 : nullptr, f.qscale, B <= FILTER_QB_MAX_B ? f.Qb8 : nullptr, f.fix_done, \
-                     stats, stats_init, c.spec ? (sharded ? a.theta : f.theta) : nullptr, in.prior)
+                     stats, stats_init, c.spec ? (sharded ? a.theta : f.theta) : nullptr, c.tight ? in.tight : in.prior)
   if (B >= 8192) RG_PREP(4);   // (100 000 x 256: 120 us with one row per wave, 74 with two or four, 162 with eight)
   else RG_PREP(1);
 #undef RG_PREP
@@ -825,7 +939,7 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
     }
     if (rc != RAGRAPH_OK) return rc;
     if (t_prof) t_prof->have = l + 1;
-    rc = run_rescore<D>(f, a.Kn, N, B, c.cap, k, a.idx_base, l > 0, l == c.nlev - 1, out_scores, out_idx, a.overflow,
+    rc = run_rescore<D>(f, a.Kn, N, B, c.cap, k, a.idx_base, l > 0, l == c.level_final, out_scores, out_idx, a.overflow,
                         rescore_kind(B, k, lv.scored, sharded && l > 0), thr, stats + 2 + l, st);
     if (rc != RAGRAPH_OK) return rc;
     if (l + 1 == c.nlev) break;
@@ -836,6 +950,9 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
       if ((rc = launch_theta(thr, B, 0, f.theta, st)) != RAGRAPH_OK) return rc;
     }
   }
+
+  // 6b. a tight bound: the soft verdict and the repair (filter_verify_fixup.h), every launch enqueued unconditionally
+  if (c.tight && (rc = run_tight_repair<D>(a, c, in, f, thr, v8.K8, stats, st)) != RAGRAPH_OK) return rc;
 
   // 7. verify / fixup
   if (c.spec && !sharded) {   // (a shard's lists prove nothing alone: the owner of a row verifies the MERGED k-th best)
@@ -873,7 +990,7 @@ static int filtered_entry(const FilteredArgs& a) {
   const FilterSchedule sc_one = filter_schedule(one);
   const size_t need = filter_workspace_bytes(one, sc_one);
   RG_REQUIRE(a.ws_bytes >= need, RAGRAPH_EWORKSPACE, "topk_cosine_filtered: workspace %zu < %zu", a.ws_bytes, need);
-  const FilterShape in{B, N, plan_N, D, k, a.n_shards, a.exchange != nullptr, t_prior, t_max_i8_levels, false, one.env, one.cus};
+  const FilterShape in{B, N, plan_N, D, k, a.n_shards, a.exchange != nullptr, t_prior, t_max_i8_levels, false, one.env, one.cus, t_tight};
   const FilterCall c = filter_call_plan(in, a.exchange && a.n_shards > 1 ? filter_schedule(in) : sc_one);
   if (c.exact_participant) return run_exact_participant(a, c);
   if (D == 256) return run_filtered<256>(a, c, in);

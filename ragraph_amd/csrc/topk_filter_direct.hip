@@ -66,6 +66,7 @@ struct DirectParams {
   int* gmax;              // BOUND
   int ngroups;            // BOUND: parts of the range
   int qgroups;            // groups of 16 queries (2..16, even: the query image is padded to whole 32s)
+  FilterGate gate;        // a repair launch: nothing to do unless the device count says so
 };
 
 #ifdef RG_DIRECT_TIMING  // diagnostic build: wall-clock stamps (10 ns ticks) of the first and the last workgroup's thread 0
@@ -89,6 +90,7 @@ __global__ void __launch_bounds__(512, 2) topk_filter_direct_kernel(DirectParams
   static_assert(!(I8 && BOUND), "the bound pass runs on the bf16 copy");
   using acc_t = typename std::conditional<I8, i32x4, f32x4>::type;
   RG_DSTAMP(0);
+  if (filter_gate_closed(p.gate)) return;  // (kernel-uniform, before any barrier)
   extern __shared__ float4 dsmem4[];
   char* smem = reinterpret_cast<char*>(dsmem4);
   const int ngl = QREG ? 0 : p.qgroups;
@@ -486,6 +488,7 @@ static int launch_filter_direct_i8(const DirectArgs& a, hipStream_t st) {
   RG_REQUIRE((p.nsub & (p.nsub - 1)) == 0 && p.nsub <= FILTER_COUNT_STRIDE, RAGRAPH_EINVAL, "filter(direct): nsub=%d", p.nsub);
   p.subcap = a.cap / p.nsub;
   p.scored = a.scored;
+  p.gate = a.gate;
   p.qgroups = 2 * (int)cdiv(a.B, 32);
   const int cus = device_cus_multiple_of_8();
   int64_t grid = cdiv(p.nunits, (int64_t)C::WAVES);
@@ -516,6 +519,7 @@ int launch_filter_direct(const DirectArgs& a, hipStream_t st) {
   RG_REQUIRE((p.nsub & (p.nsub - 1)) == 0 && p.nsub <= FILTER_COUNT_STRIDE, RAGRAPH_EINVAL, "filter(direct): nsub=%d", p.nsub);
   p.subcap = a.cap / p.nsub;
   p.gmax = a.gmax_out;
+  p.gate = a.gate;
   p.ngroups = a.bound_groups;
   p.qgroups = 2 * (int)cdiv(a.B, 32);
   const bool bound = a.bound_groups > 0;

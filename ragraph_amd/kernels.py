@@ -263,6 +263,14 @@ def set_filter_prior(theta_prior) -> float:
     return N.lib().ragraph_topk_cosine_filtered_set_prior(float("nan") if theta_prior is None else float(theta_prior))
 
 
+def set_filter_tight_prior(theta_tight) -> float:
+    """A TIGHT speculative bound for this thread's following filtered calls (None / NaN: none); returns the old one.
+    ragraph_topk_cosine_filtered_set_tight_prior: honoured by single-bank calls of more than 256 queries that also run under a
+    prior below it -- one level from theta = tight, the queries it was too high for repaired on the device from
+    max(prior, their k-th best found).  Exact for any value."""
+    return N.lib().ragraph_topk_cosine_filtered_set_tight_prior(float("nan") if theta_tight is None else float(theta_tight))
+
+
 def ord2f(v: int) -> float:
     """The float behind an order-preserving int of the statistics words (csrc/filter_common.h f2ord: non-negative floats
     keep their bits, negative ones have the 31 low bits flipped)."""

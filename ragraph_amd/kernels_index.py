@@ -57,6 +57,23 @@ class KeyIndex:
     SPEC_MIN_MARGIN = 0.01
     SPEC_MAX_CANDIDATES = 1.5
     SPEC_HISTORY = 16
+    # Tight bound (ops.set_filter_tight_prior, csrc/filter_schedule.h: filter_call_plan): a call of at least TIGHT_MIN_BATCH
+    # queries that runs under the prior above ALSO starts every query from t = lowest k-th best of the history - TIGHT_MARGIN
+    # and runs ONE level; a query whose k-th best found is below t is repaired on the device from max(prior, what it found),
+    # up to 256 of them by a 256-query call of the direct kernel, more by one more level over the bank.  So a miss of t costs
+    # about 0.1 ms (any number up to 256) where a miss of the prior costs a scan: t needs no margin of the spread.  The scores
+    # of the bench's queries have sigma = 1 / 16 and their k-th best sits 4 sigma out, where 0.002 of score is 13 % more
+    # candidates (measured at the bench shape: 0 soft misses in every polled step over its 8 distinct batches, 152 candidates
+    # per query; t 0.004 higher: 10 soft misses, 0.2 ms less per call -- not worth a repair in most steps); a call that reports
+    # more than TIGHT_MAX_SOFT soft misses doubles the margin (up to TIGHT_MARGIN_MAX), one
+    # whose repair took the all-queries level withdraws t for the re-probe interval.  RAGRAPH_SPEC_TIGHT=0: the prior alone (A/B).
+    # From TIGHT_MIN_BATCH queries: the verdict and the (empty) repair are eight more launches, ~13 us, and up to 4096 queries
+    # the call under the prior already runs one level, so t only saves candidates there -- 1M x 256, ms per call without / with
+    # t: 512 queries 0.154 / 0.167, 4096: 0.894 / 0.865, 100 000: 19.2 / 17.8 (profiles/tight_prior.txt).
+    TIGHT_MIN_BATCH = 2048
+    TIGHT_MARGIN = 0.002
+    TIGHT_MARGIN_MAX = 0.064
+    TIGHT_MAX_SOFT = 32
     DEDUP_MIN_ROWS = 2048
     DEDUP_MAX_UNIQUE = 0.9
     DEDUP_MAX_GROUP = 64
@@ -94,6 +111,8 @@ class KeyIndex:
         # the last polled call WITH a bound pass, "failed": misses so far}
         self._spec = {}
         self.spec_enabled = os.environ.get("RAGRAPH_SPEC", "1") != "0"   # (RAGRAPH_SPEC=0: every call with its bound pass -- A/B)
+        self.tight_enabled = os.environ.get("RAGRAPH_SPEC_TIGHT", "1") != "0"
+        self.last_tight = None           # the tight bound the last filtered call ran with (None: none)
         self._notes = 0                  # calls offered to _note_overflow (small calls report every fourth once settled)
         self.last_stats = None           # device view of the last filtered call's statistics words (this index, this stream)
         self.last_prior = None           # the speculative first bound the last filtered call ran with (None: a bound pass)
@@ -209,6 +228,7 @@ class KeyIndex:
             return lists_over
         st["used"] += 1
         st["failed"] += failed
+        self._judge_tight(st, words)
         loose = cand is not None and st["cand"] is not None and cand > self.SPEC_MAX_CANDIDATES * max(st["cand"], 32.0)
         if failed or loose or lists_over:
             probed_at = st.get("probed_at")
@@ -219,6 +239,35 @@ class KeyIndex:
                 st["hist"] = []
                 st["queries"] = 0
         return 0   # (a speculative call says nothing about the lists)
+
+    def _judge_tight(self, st: dict, words):
+        """A polled speculative call's words [21] (a tight bound was in force), [22] (soft misses), [23] (1: the 256-query
+        repair ran, 2: the all-queries level): widen the margin after a flood of soft misses, withdraw t after the level."""
+        if len(words) < 24 or not words[21]:
+            return
+        st["soft"] = st.get("soft", 0) + words[22]
+        st["tight_used"] = st.get("tight_used", 0) + 1
+        if words[23] == 2:
+            st["tight_off_at"] = self._queries
+        if words[23] == 2 or words[22] > self.TIGHT_MAX_SOFT:
+            st["tight_margin"] = min(2.0 * st.get("tight_margin", self.TIGHT_MARGIN), self.TIGHT_MARGIN_MAX)
+
+    def _tight_for(self, B: int, k: int, prior):
+        """The tight bound for a call of B queries that runs under `prior`, or None (no prior -- which covers captures and
+        RAGRAPH_SPEC=0 --, switched off, withdrawn, a batch the direct or single-launch kernels take, nothing above the prior)."""
+        if prior is None or not self.tight_enabled or B < self.TIGHT_MIN_BATCH or \
+                getattr(self.ops, "set_filter_tight_prior", None) is None:
+            return None
+        st = self._spec_state(k)
+        off_at = st.get("tight_off_at")
+        if off_at is not None:
+            if self._queries - off_at < self.REPROBE_QUERIES:
+                return None
+            st["tight_off_at"] = None
+        if not st["hist"]:
+            return None
+        t = min(h[0] for h in st["hist"]) - st.get("tight_margin", self.TIGHT_MARGIN)
+        return t if t > prior else None
 
     def _demote(self, what: str):
         """int8 -> bf16 levels ("i8") or filter -> fp32 kernels ("filter"), until the re-probe.  A demotion within one interval
@@ -441,8 +490,11 @@ class KeyIndex:
             had_i8 = had_i8 and ops.filtered_i8_levels(B, kn.shape[0], D, k) > 0   # (did THIS call have int8 levels?)
             stats = None
             prior = self._prior_for(B, k)
+            tight = self._tight_for(B, k, prior)
             if prior is not None:
                 ops.set_filter_prior(prior)
+            if tight is not None:
+                ops.set_filter_tight_prior(tight)
             try:
                 if getattr(ops, "FILTER_STATS", False):   # this call's own statistics words, handed on explicitly
                     s, i, over, stats = ops.topk_cosine_filtered(q, kn, self._bf16, k, idx_base=idx_base,
@@ -454,7 +506,10 @@ class KeyIndex:
                     cap(-1)
                 if prior is not None:
                     ops.set_filter_prior(None)
+                if tight is not None:
+                    ops.set_filter_tight_prior(None)
             self.last_prior = prior
+            self.last_tight = tight
             self._note_overflow(over, B, had_i8, stats, k)
             self.last_stats = stats   # (diagnostic: bench.py / tools read the levels' candidate counts of the last call)
             return s, i
