@@ -58,7 +58,9 @@ __global__ void __launch_bounds__(256) filter_prep_kernel(const float* __restric
   for (int rr = 0; rr < R; ++rr) {
   const int64_t q = q_first + rr;
   if (q == 0 && lane == 0) *overflow = 0;
-  if (q == 0 && lane < FILTER_STATS_INTS && stats) {
+  // (word [15] is COUNTED by this launch's other workgroups, in any order with this one: the launcher zeroes it on the
+  // stream in front of the launch, and it is not written here)
+  if (q == 0 && lane < FILTER_STATS_INTS && lane != 15 && stats) {
     int v = 0;
     if (lane == 0) v = FILTER_STATS_MAGIC;
     else if (lane == 1) v = si.nlev;

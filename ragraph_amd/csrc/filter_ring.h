@@ -137,11 +137,8 @@ __global__ void __launch_bounds__(512, 2) topk_filter_kernel(FilterParams p) {
   // A fragment of step n of a stage (sub-tile n / KSTEPS, k-step n % KSTEPS): block n of the slot, this lane's 16 bytes
   const unsigned apos = lds_base + (unsigned)lane * 16u;
 
-  const int x = p.xcd_map ? (int)(blockIdx.x & 7) : 0;
-  const int64_t nq = p.xcd_map ? ((p.qtiles - x + 7) >> 3) : p.qtiles;
-  const int64_t nq0 = p.xcd_map ? ((p.qtiles + 7) >> 3) : p.qtiles;
-  SegmentWalker walker(nq, p.nstages_total, p.wgs_per_group, p.lb_min, 0, p.depth[nq != nq0],
-                       p.xcd_map ? (int)(blockIdx.x >> 3) : (int)blockIdx.x);
+  // (segment_plan.h: one group, XCD groups, or XCD groups + the leftover tiles over every workgroup -- launch_ring chose)
+  RingWalker walker(p.qtiles, p.nstages_total, p.wgs_per_group, p.lb_min, p.xcd_map, p.depth[0], p.depth[1], (int)blockIdx.x);
   Segment seg;
   [[maybe_unused]] bool first_seg = true;
 #ifdef RG_RING_STAMPS
@@ -149,7 +146,7 @@ __global__ void __launch_bounds__(512, 2) topk_filter_kernel(FilterParams p) {
 #endif
   RG_RSTAMP(0);
   while (walker.next(seg)) {
-    const int64_t qtile = p.xcd_map ? x + 8 * seg.tile : seg.tile;
+    const int64_t qtile = walker.qtile(seg);
     const int64_t q_lo = qtile * QT + wave * QW + j;  // group gq's query: q_lo + 16 gq
     const int64_t st0 = seg.st0;
     const int nstages = (int)(seg.st1 - seg.st0);

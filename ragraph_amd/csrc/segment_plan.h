@@ -237,4 +237,101 @@ struct SegmentWalker {
   }
 };
 
+// ---- The ring kernel's plan (filter_ring.h): which SegmentWalker groups a launch of CUS persistent workgroups is made of.
+//   RING_ONE   one group of all workgroups (fewer than 64 query tiles);
+//   RING_XCD   eight groups of W = CUS / 8 workgroups, one per XCD (workgroup b runs on XCD b % 8): group x owns tiles
+//              x, x + 8, ... -- ceil(qtiles / 8) of them, or one fewer;
+//   RING_SPLIT (qtiles % 8 != 0) every XCD group owns qtiles / 8 tiles, walked as above, and the left = qtiles % 8 tiles
+//              8 (qtiles / 8) + t are ONE more group of all CUS workgroups (c = the workgroup's number, no XCD
+//              interleave, a depth of its own) that every workgroup walks AFTER its XCD part.  Under RING_XCD the `left`
+//              groups with one tile more finish last and the other XCDs stand idle meanwhile (131 tiles x 7813 stages on
+//              256 workgroups: the most loaded workgroup has 4151 stages, 3999 with the split; even is 3998).
+// RingWalker is the sequence of segments one workgroup walks -- the kernel, the planner below and the CPU checker
+// (tools/check_ring_plan.cpp) run this code; ring_plan_choose (host) takes RING_SPLIT only where the most loaded workgroup,
+// found by walking every workgroup's plan, has fewer stages than under RING_XCD.  The ring kernel keeps one list per
+// query, so Segment::slot / last mean nothing here and warm-ups are not modelled (warm = 0).
+enum { RING_ONE = 0, RING_XCD = 1, RING_SPLIT = 2 };
+
+struct RingWalker {
+  SegmentWalker w;
+  int64_t tile0;  // query tile of the current group's tile 0 ...
+  int tstride;    // ... and the distance of two of its tiles
+  int64_t left, left0;  // RING_SPLIT, while the leftover group is still to come: its tiles, the first of them
+  int cus, bid, depth_left;
+
+  // W: workgroups per group (CUS / 8 with XCD groups); depth0 / depth1: RING_ONE the group's (depth1 unused), RING_XCD of
+  // the groups of ceil(qtiles / 8) tiles / of one fewer, RING_SPLIT of the XCD groups / of the leftover group
+  RG_HD RingWalker(int64_t qtiles, int64_t NS, int W, int lb_min, int mode, int depth0, int depth1, int bid_)
+      : w(group_tiles(qtiles, mode, bid_), NS, W, lb_min, 0,
+          (mode == RING_XCD && group_tiles(qtiles, mode, bid_) != ((qtiles + 7) >> 3)) ? depth1 : depth0,
+          mode == RING_ONE ? bid_ : bid_ >> 3),
+        tile0(mode == RING_ONE ? 0 : (bid_ & 7)),
+        tstride(mode == RING_ONE ? 1 : 8),
+        left(mode == RING_SPLIT ? (qtiles & 7) : 0),
+        left0((qtiles >> 3) << 3),
+        cus(mode == RING_ONE ? W : 8 * W),
+        bid(bid_),
+        depth_left(depth1) {}
+
+  // tiles of workgroup b's (first) group
+  static RG_HD int64_t group_tiles(int64_t qtiles, int mode, int b) {
+    return mode == RING_ONE ? qtiles : (mode == RING_XCD ? (qtiles - (b & 7) + 7) >> 3 : qtiles >> 3);
+  }
+
+  RG_HD bool next(Segment& s) {
+    while (!w.next(s)) {
+      if (!left) return false;
+      // the XCD part is exhausted: the same walker, re-made in place for the leftover group
+      w = SegmentWalker(left, w.NS, cus, w.lb_min, 0, depth_left, bid);
+      tile0 = left0;
+      tstride = 1;
+      left = 0;
+    }
+    return true;
+  }
+  // the query tile of the segment next() returned last
+  RG_HD int64_t qtile(const Segment& s) const { return tile0 + tstride * s.tile; }
+};
+
+// ---- host side: the planner
+struct RingPlan {
+  int mode, depth[2];  // (RingWalker's mode, depth0, depth1)
+  int64_t load;        // stages of the most loaded workgroup
+};
+
+// Stages of the most loaded of the CUS workgroups, by walking every one of them.
+static inline int64_t ring_plan_load(int64_t qtiles, int64_t NS, int CUS, int lb_min, const RingPlan& pl) {
+  int64_t worst = 0;
+  for (int b = 0; b < CUS; ++b) {
+    RingWalker rw(qtiles, NS, pl.mode == RING_ONE ? CUS : CUS / 8, lb_min, pl.mode, pl.depth[0], pl.depth[1], b);
+    Segment s;
+    int64_t load = 0;
+    while (rw.next(s)) load += s.st1 - s.st0;
+    if (load > worst) worst = load;
+  }
+  return worst;
+}
+
+// The plan of a ring launch (CUS: a multiple of 8).  XCD groups from 64 query tiles; the depths are choose_depth's, except
+// that short launches cut the remainder at once (depth 0): a workgroup WALKS the plan's lockstep steps to its segment, every
+// step a few 64-bit divisions, and with a few tiles over 256 workgroups the last ones walk ~40 of them -- 22.8 us of a 39-us
+// launch (2708 queries x 10 000 keys: -DRG_RING_STAMPS); the re-reads the steps save are nothing at this size.
+static inline RingPlan ring_plan_choose(int64_t qtiles, int64_t NS, int CUS, int lb_min) {
+  const bool xcd = qtiles >= 64;
+  const int W = CUS / (xcd ? 8 : 1);
+  const bool shallow = qtiles * NS / CUS < 16;
+  auto depth_of = [&](int64_t nq, int Wg) {
+    return (nq < 1 || shallow) ? 0 : SegmentWalker::choose_depth(nq, NS, Wg, lb_min, 0).depth;
+  };
+  RingPlan pl{xcd ? RING_XCD : RING_ONE, {0, 0}, 0};
+  const int64_t nq0 = xcd ? (qtiles + 7) / 8 : qtiles;
+  pl.depth[0] = depth_of(nq0, W);
+  if (!xcd || qtiles % 8 == 0) return pl;  // (load: nobody asks)
+  pl.depth[1] = depth_of(nq0 - 1, W);
+  RingPlan sp{RING_SPLIT, {pl.depth[1], depth_of(qtiles % 8, CUS)}, 0};  // (nq0 - 1 = qtiles / 8 here)
+  pl.load = ring_plan_load(qtiles, NS, CUS, lb_min, pl);
+  sp.load = ring_plan_load(qtiles, NS, CUS, lb_min, sp);
+  return sp.load < pl.load ? sp : pl;
+}
+
 }  // namespace ragraph

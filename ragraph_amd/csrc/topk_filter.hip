@@ -78,7 +78,7 @@ struct FilterParams {
   int cap;
   int64_t stage_base;     // first stage of the key range this launch filters
   int64_t qtiles, nstages_total;  // nstages_total = stages in the range
-  int xcd_map, wgs_per_group, lb_min, depth[2];
+  int xcd_map, wgs_per_group, lb_min, depth[2];  // the launch's plan (segment_plan.h): RingWalker's mode, W, lb_min, depth0 / depth1
   int partner_lead;       // > 0: a wave's priority follows its SIMD partner's progress (see the stage loop); 0: off
   // bound pass (BOUND kernels): per query, the maxima of `ngroups` consecutive stage ranges of the launch's key range
   int* gmax;              // [B, ngroups] as order-preserving ints (f2ord), pre-filled with f2ord(-inf)
@@ -443,13 +443,30 @@ extern "C" int ragraph_topk_cosine_filtered_sharded_speculates(int64_t B, int64_
   return filter_call_plan(in, filter_schedule(in)).spec ? 1 : 0;
 }
 
+// The plan of a ring launch (segment_plan.h: ring_plan_choose walks every workgroup of two plans), kept per thread for the
+// shapes it last saw: a call's launches repeat from call to call, and a launch must not simulate 256 workgroups every time.
+static RingPlan ring_plan_cached(int64_t qtiles, int64_t NS, int CUS, int lb_min) {
+  struct Entry {
+    int64_t qtiles, NS;
+    int CUS, lb_min;
+    RingPlan pl;
+  };
+  constexpr int SLOTS = 16;
+  thread_local Entry cache[SLOTS];
+  thread_local int used = 0, victim = 0;
+  for (int i = 0; i < used; ++i)
+    if (cache[i].qtiles == qtiles && cache[i].NS == NS && cache[i].CUS == CUS && cache[i].lb_min == lb_min) return cache[i].pl;
+  const RingPlan pl = ring_plan_choose(qtiles, NS, CUS, lb_min);
+  const int at = used < SLOTS ? used++ : (victim = (victim + 1) % SLOTS);
+  cache[at] = Entry{qtiles, NS, CUS, lb_min, pl};
+  return pl;
+}
+
 // Ring-kernel launch shared by the filter levels and the bound pass (B > 256: the direct kernel takes smaller batches).
 template <int D, int QW, bool BOUND, bool I8 = false, bool SCORED = false, bool PIPE = false>
 static int launch_ring(FilterParams p, int64_t B, int CUS, int prof_slot, hipStream_t st) {
   using C = FilterCfg<I8 ? D / 2 : D>;
   p.qtiles = cdiv(B, (int64_t)C::WAVES * QW);
-  p.xcd_map = p.qtiles >= 64 ? 1 : 0;
-  p.wgs_per_group = CUS / (p.xcd_map ? 8 : 1);
   // shortest piece of a key stream a workgroup takes: 8 stages when there is work for everybody, fewer on short launches
   // (a bound pass of 18 stages x 6 query tiles gave 14 workgroups 8 stages each and 242 nothing: 19 us of stage loop where
   // 108 workgroups need 2.5; tools/check_segment_plan.cpp covers lb_min = 1)
@@ -457,17 +474,11 @@ static int launch_ring(FilterParams p, int64_t B, int CUS, int prof_slot, hipStr
     const int64_t per_wg = p.qtiles * p.nstages_total / CUS;
     p.lb_min = per_wg >= 16 ? 8 : (per_wg >= 8 ? 4 : (per_wg >= 3 ? 2 : 1));
   }
-  const int64_t nq0 = p.xcd_map ? (p.qtiles + 7) / 8 : p.qtiles;
-  for (int v = 0; v < 2; ++v) {
-    const int64_t nq = nq0 - v;
-    p.depth[v] = 0;
-    if (nq < 1 || (v == 1 && (!p.xcd_map || p.qtiles % 8 == 0))) continue;
-    p.depth[v] = SegmentWalker::choose_depth(nq, p.nstages_total, p.wgs_per_group, p.lb_min, 0).depth;
-    // Short launches cut the remainder at once (depth 0): a workgroup WALKS the plan's lockstep steps to its segment, every
-    // step a few 64-bit divisions, and with a few tiles over 256 workgroups the last ones walk ~40 of them -- 22.8 us of
-    // a 39-us launch (2708 queries x 10 000 keys: -DRG_RING_STAMPS); the re-reads the steps save are nothing at this size.
-    if (p.qtiles * p.nstages_total / CUS < 16) p.depth[v] = 0;
-  }
+  const RingPlan pl = ring_plan_cached(p.qtiles, p.nstages_total, CUS, p.lb_min);
+  p.xcd_map = pl.mode;
+  p.wgs_per_group = CUS / (pl.mode == RING_ONE ? 1 : 8);
+  p.depth[0] = pl.depth[0];
+  p.depth[1] = pl.depth[1];
   static DeviceOnce lds_once;  // per template instance and device (common.h)
   if (hipError_t e = raise_dynamic_lds(lds_once, &topk_filter_kernel<D, QW, BOUND, I8, SCORED, PIPE>, (int)C::LDS_BYTES); e != hipSuccess) {
     set_error("topk_cosine_filtered: cannot raise dynamic LDS limit: %s", hipGetErrorString(e));
@@ -856,6 +867,11 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
     stats_init.i8[l] = c.level[l].int8;
     const int64_t lk = c.level[l].key1 - c.level[l].key0;
     stats_init.keys[l] = lk > INT_MAX ? INT_MAX : (int)lk;
+  }
+  // (the zero-query count: every workgroup of the prepare launch adds to it, so it is zeroed in front of the launch)
+  if (hipMemsetAsync(stats + 15, 0, sizeof(int), st) != hipSuccess) {
+    set_error("topk_cosine_filtered: memset failed");
+    return RAGRAPH_EDEVICE;
   }
 #define RG_PREP(R_)                                                                                                                     \
   hipLaunchKernelGGL((filter_prep_kernel<D, R_>), dim3((unsigned)cdiv(B <= FILTER_QB_MAX_B ? (B + 31) / 32 * 32 : B, 4 * (R_))), dim3(256), 0, st, a.Q, B, \
