@@ -144,7 +144,7 @@ int ragraph_topk_cosine_mix_f32(const float* Q, int64_t B, const float* Kn, int6
  *   rescored with the natural-order fp32 fmaf chain and selected in canonical order, which gives the exact top-k of
  *   everything seen so far and a tighter bound for the next level (large batches: [0,N/32), [N/32,N/4), [N/4,N); small
  *   ones: fewer, steeper levels -- ragraph_topk_cosine_filtered_plan).  The result has the same bits as
- *   ragraph_topk_cosine_f32.  D in {64,128,256}, k <= 32.
+ *   ragraph_topk_cosine_f32.  D in {64,128,256}, k <= 32; lists of 33 .. 64 keys: the _wide entries below.
  *   Kb   bf16 copy of Kn made by ragraph_keys_to_bf16 (ragraph_keys_bf16_rows(N) rows x D, uint16 storage: the bf16 rows
  *        padded to a multiple of 256 keys, a tail row, the int8 rows, their tail row, the int8 copy's granule table, and
  *        256 rows of slack that the last stage of an int8 level may read).  The int8 rows come in two classes of granules
@@ -233,6 +233,18 @@ float ragraph_topk_cosine_filtered_set_tight_prior(float t);
 int ragraph_topk_cosine_filtered_f32(const float* Q, int64_t B, const float* Kn, const float* Kp, const uint16_t* Kb,
                                      int64_t N, int D, int k, int64_t idx_base, float* out_scores, int64_t* out_idx,
                                      int* overflow, int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream);
+/* The same call for lists of 33 <= k <= min(N, 64) keys: the arguments, the result's bits, the statistics words (at the same
+ * offset of the workspace as passed) and the calling thread's prior, tight bound and int8 cap of the entry above; the MFMA
+ * kernels are the same launches, and every kernel that carries a list (rescoring, scored rounds, exact scans and their
+ * merges) runs in its form for 64 winners.  One path per k: these entries return RAGRAPH_EINVAL for k <= 32 and k > 64 as
+ * the entries above do for k > 32; another D is RAGRAPH_EUNSUPPORTED and a size of 0.  _wide_plan writes the seven words of
+ * ragraph_topk_cosine_filtered_plan; _wide_workspace_bytes is the size the wide call needs (0 for a shape it refuses; never less
+ * than ragraph_topk_cosine_filtered_workspace_bytes of the same shape at k = 32). */
+size_t ragraph_topk_cosine_filtered_wide_workspace_bytes(int64_t B, int64_t N, int D, int k);
+int ragraph_topk_cosine_filtered_wide_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]);
+int ragraph_topk_cosine_filtered_wide_f32(const float* Q, int64_t B, const float* Kn, const float* Kp, const uint16_t* Kb,
+                                          int64_t N, int D, int k, int64_t idx_base, float* out_scores, int64_t* out_idx,
+                                          int* overflow, int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream);
 
 /* a1 over a ROW-SHARDED bank (one shard per GPU; the reference is single-GPU, so no reference line beyond the retrieval
  * itself -- SimilarityFunctions.py:6-16 + ToyGraphBase.py:66-67).  As ragraph_topk_cosine_filtered_f32 on this shard's

@@ -57,6 +57,10 @@ SIGNATURES = {
     "ragraph_topk_cosine_filtered_max_i8_levels": (_i32, [_i32]),
     "ragraph_topk_cosine_filtered_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
                                                 _sz, _vp]),
+    "ragraph_topk_cosine_filtered_wide_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "ragraph_topk_cosine_filtered_wide_plan": (_i32, [_i64, _i64, _i32, _i32, _vp]),
+    "ragraph_topk_cosine_filtered_wide_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
+                                                     _sz, _vp]),
     "ragraph_topk_cosine_filtered_sharded_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp,
                                                         _vp, _sz, _vp, _i64, _vp, _vp, _vp, _i32]),
     "ragraph_topk_cosine_small_ok": (_i32, [_i64, _i64, _i32, _i32]),

@@ -105,7 +105,9 @@ __device__ __forceinline__ bool pair_gt(unsigned ah, unsigned al, unsigned bh, u
 }
 // Returns false (nothing written) when more than 64 round-2 entries beat round 1's k-th pair: the caller then scores
 // the whole list the plain way (a level whose first bound was useless; rare).
-template <int D, int NS, int ROWS = 64>
+// LW = 64 (the wide entry, 33 <= k <= 64): round 1's sixteen pairs and up to 64 previous winners do not fit one row of 64
+// lanes, so the previous winners travel in a row of their own (V: lane l = winner l) and every count runs over both rows.
+template <int D, int NS, int ROWS = 64, int LW = 32>
 __device__ __forceinline__ bool rescore_scored_query(const float4* __restrict__ qrow, const float* __restrict__ Kn,
                                                      const int2* __restrict__ cb, int n, int lane, int k, int64_t base,
                                                      const float* prev_s, const int64_t* prev_i, float* out_s, int64_t* out_i,
@@ -144,31 +146,64 @@ __device__ __forceinline__ bool rescore_scored_query(const float4* __restrict__ 
   const float e1 = coop_scores_few<D>(qrow, Kn, r1key, lane, sm);
   // W: round 1 (lanes 0..15) and the previous winners (lanes 16..16+k-1) as canonical 64-bit keys (0 = no pair)
   unsigned wh = 0u, wl = 0u;
+  unsigned vh = 0u, vl = 0u;  // (LW = 64) row V: the previous winners
   if (lane < SCORED_R1) {
     wh = select_ord(e1);
     wl = ~(unsigned)r1key;
-  } else if (prev_s && lane < SCORED_R1 + k) {
+  } else if (LW == 32 && prev_s && lane < SCORED_R1 + k) {
     const int64_t pv = prev_i[lane - SCORED_R1];
     if (pv < INT_MAX) {
       wh = select_ord(prev_s[lane - SCORED_R1]);
       wl = ~(unsigned)(int)pv;
     }
   }
-  const int nwl = prev_s ? SCORED_R1 + k : SCORED_R1;
+  if constexpr (LW == 64) {
+    if (prev_s && lane < k) {
+      const int64_t pv = prev_i[lane];
+      if (pv < INT_MAX) {
+        vh = select_ord(prev_s[lane]);
+        vl = ~(unsigned)(int)pv;
+      }
+    }
+  }
+  const int nwl = (LW == 32 && prev_s) ? SCORED_R1 + k : SCORED_R1;
+  const int nvl = (LW == 64 && prev_s) ? k : 0;
   const bool w_valid = (wh | wl) != 0u;
-  const int n_w = __popcll(__ballot(w_valid));
-  int rank_w = 0;
+  const bool v_valid = (vh | vl) != 0u;
+  int n_w = __popcll(__ballot(w_valid));
+  if constexpr (LW == 64) n_w += __popcll(__ballot(v_valid));
+  int rank_w = 0, rank_v = 0;
   for (int o = 0; o < nwl; ++o) {
     const unsigned oh = (unsigned)__builtin_amdgcn_readlane((int)wh, o), ol = (unsigned)__builtin_amdgcn_readlane((int)wl, o);
     rank_w += pair_gt(oh, ol, wh, wl) ? 1 : 0;
+    if constexpr (LW == 64) rank_v += pair_gt(oh, ol, vh, vl) ? 1 : 0;
   }
+  if constexpr (LW == 64)
+    for (int o = 0; o < nvl; ++o) {
+      const unsigned oh = (unsigned)__builtin_amdgcn_readlane((int)vh, o), ol = (unsigned)__builtin_amdgcn_readlane((int)vl, o);
+      rank_w += pair_gt(oh, ol, wh, wl) ? 1 : 0;
+      rank_v += pair_gt(oh, ol, vh, vl) ? 1 : 0;
+    }
   // theta_e = the k-th best of W, a lower bound of the final k-th best (-inf: fewer than k pairs, everything is scored)
   unsigned kh = 0u, kl = 0u;
   if (n_w >= k) {
     const unsigned long long at = __ballot(w_valid && rank_w == k - 1);
-    const int src = __ffsll((long long)at) - 1;
-    kh = (unsigned)__builtin_amdgcn_readlane((int)wh, src);
-    kl = (unsigned)__builtin_amdgcn_readlane((int)wl, src);
+    if constexpr (LW == 32) {
+      const int src = __ffsll((long long)at) - 1;
+      kh = (unsigned)__builtin_amdgcn_readlane((int)wh, src);
+      kl = (unsigned)__builtin_amdgcn_readlane((int)wl, src);
+    } else {  // (ranks over both rows are unique: the pair of rank k - 1 sits in exactly one of them)
+      const unsigned long long atv = __ballot(v_valid && rank_v == k - 1);
+      if (at) {
+        const int src = __ffsll((long long)at) - 1;
+        kh = (unsigned)__builtin_amdgcn_readlane((int)wh, src);
+        kl = (unsigned)__builtin_amdgcn_readlane((int)wl, src);
+      } else {
+        const int src = __ffsll((long long)atv) - 1;
+        kh = (unsigned)__builtin_amdgcn_readlane((int)vh, src);
+        kl = (unsigned)__builtin_amdgcn_readlane((int)vl, src);
+      }
+    }
   }
   const float theta_e = n_w >= k ? select_unord(kh) : RG_NEG_INF;
   // (an entry's integer is (I << 1) | class of its key's granule: each class has its own bound -- compared on the doubled scale)
@@ -229,16 +264,29 @@ __device__ __forceinline__ bool rescore_scored_query(const float4* __restrict__ 
   for (int o = 0; o < nb; ++o) {
     const unsigned oh = (unsigned)__builtin_amdgcn_readlane((int)bh, o), ol = (unsigned)__builtin_amdgcn_readlane((int)bl, o);
     rank_w += pair_gt(oh, ol, wh, wl) ? 1 : 0;
+    if constexpr (LW == 64) rank_v += pair_gt(oh, ol, vh, vl) ? 1 : 0;
     rank_b += pair_gt(oh, ol, bh, bl) ? 1 : 0;
   }
-  if (nb > 0)
+  if (nb > 0) {
     for (int o = 0; o < nwl; ++o) {
       const unsigned oh = (unsigned)__builtin_amdgcn_readlane((int)wh, o), ol = (unsigned)__builtin_amdgcn_readlane((int)wl, o);
       rank_b += pair_gt(oh, ol, bh, bl) ? 1 : 0;
     }
+    if constexpr (LW == 64)
+      for (int o = 0; o < nvl; ++o) {
+        const unsigned oh = (unsigned)__builtin_amdgcn_readlane((int)vh, o), ol = (unsigned)__builtin_amdgcn_readlane((int)vl, o);
+        rank_b += pair_gt(oh, ol, bh, bl) ? 1 : 0;
+      }
+  }
   if (w_valid && rank_w < k) {
     out_s[rank_w] = select_unord(wh);
     out_i[rank_w] = (int64_t)(int)~wl + base;
+  }
+  if constexpr (LW == 64) {
+    if (v_valid && rank_v < k) {
+      out_s[rank_v] = select_unord(vh);
+      out_i[rank_v] = (int64_t)(int)~vl + base;
+    }
   }
   if (lane < nb && rank_b < k) {
     out_s[rank_b] = select_unord(bh);
@@ -254,7 +302,7 @@ __device__ __forceinline__ bool rescore_scored_query(const float4* __restrict__ 
 // SMALL (calls of 8192 queries and more, whose lists average ~120 entries and whose second round ~25 rows): half tiles and
 // at most four entry slots per lane -- 15 KB less LDS per workgroup and ~50 fewer registers, three waves per SIMD instead
 // of two for a kernel that lives on hiding row-gather latency; the few longer lists take lane-private row reads.
-template <int D, bool SMALL = false>
+template <int D, bool SMALL = false, int LW = 32>
 __global__ void __launch_bounds__(128) topk_rescore_scored_kernel(const float* __restrict__ Qn, const float* __restrict__ Kn,
                                                                   int* __restrict__ count, const int2* __restrict__ cand,
                                                                   int64_t B, int cap, int cs, int k, int64_t idx_base,
@@ -308,7 +356,7 @@ __global__ void __launch_bounds__(128) topk_rescore_scored_kernel(const float* _
   const int2* cb = cand + b * cap;
   const int* ck = reinterpret_cast<const int*>(cb);
 #define RG_SCORED(NS_) \
-  rescore_scored_query<D, NS_, ROWS>(qs[w], Kn, cb, n, lane, k, base, ps, pi, out_s + b * k, out_i + b * k, tile[w], surv[w], \
+  rescore_scored_query<D, NS_, ROWS, LW>(qs[w], Kn, cb, n, lane, k, base, ps, pi, out_s + b * k, out_i + b * k, tile[w], surv[w], \
                                      stage[w], thr, b)
   bool done = false;
   if (n > 24) {  // (round 1 alone would take most of a shorter list)
@@ -341,10 +389,12 @@ __global__ void __launch_bounds__(128) topk_rescore_scored_kernel(const float* _
 // sorted list (lane p = entry p), merged at the end.  No host read-back, so the call stays asynchronous and HIP-graph
 // capturable; a bank that sends many queries here is slow (one full fp32 scan per query and workgroup), which KeyIndex
 // notices from the count after the fact and stops filtering that bank.  All 256 threads of the workgroup must call.
-template <int D>
+// LW: the list width the call is built for (32: k <= 32; 64: the wide entry's 33 <= k <= 64) -- the rows of ps / pi, and how
+// many of the 4 k partial winners a lane of the merging wave holds (4 LW / 64).
+template <int D, int LW = 32>
 __device__ __forceinline__ void exact_scan_query(const float4* qs /* LDS: the query row */, const float* __restrict__ Kn,
                                                  int64_t N, int k, int64_t idx_base, float (*tile)[64 * RESCORE_LD],
-                                                 float (*ps)[32], int64_t (*pi)[32], float* __restrict__ out_s,
+                                                 float (*ps)[LW], int64_t (*pi)[LW], float* __restrict__ out_s,
                                                  int64_t* __restrict__ out_i) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (zero_query_answer<D>(qs, w == 0 ? k : 0, idx_base, lane, out_s, out_i)) {  // (no scan; every wave takes the same branch,
@@ -382,23 +432,24 @@ __device__ __forceinline__ void exact_scan_query(const float4* qs /* LDS: the qu
       pend &= __ballot(key >= 0 && cand_better(sc, key, kth_s, kth_i));
     }
   }
-  if (lane < 32) {
+  if (lane < LW) {
     ps[w][lane] = lane < k ? es : RG_NEG_INF;
     pi[w][lane] = (lane < k && ei != INT_MAX) ? (int64_t)ei : INT64_MAX;
   }
   __syncthreads();
-  if (w == 0) {  // 4 k <= 128 partial winners: two per lane
-    float s2[2];
-    int id2[2];
+  if (w == 0) {  // 4 k <= 128 partial winners: two per lane (LW = 64: 4 k <= 256, four per lane)
+    constexpr int NM = LW / 16;
+    float s2[NM];
+    int id2[NM];
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
+    for (int u = 0; u < NM; ++u) {
       const int e = lane + 64 * u;
       const bool have = e < 4 * k;
       s2[u] = have ? ps[e / k][e % k] : RG_NEG_INF;
       const int64_t pv = have ? pi[e / k][e % k] : INT64_MAX;
       id2[u] = pv >= INT_MAX ? INT_MAX : (int)pv;
     }
-    wave_select<2>(s2, id2, k, lane, idx_base, out_s, out_i);
+    wave_select<NM>(s2, id2, k, lane, idx_base, out_s, out_i);
   }
   __syncthreads();
 }
@@ -427,7 +478,7 @@ static void wide_timing_report() {
 #define RG_WSTAMP(i_)
 static void wide_timing_report() {}
 #endif
-template <int D, bool SLICED, bool COOP>
+template <int D, bool SLICED, bool COOP, int LW = 32>
 __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __restrict__ Qn, const float* __restrict__ Kn,
                                                                 int* __restrict__ count,
                                                                 const int* __restrict__ cand, int64_t B, int64_t N, int cap,
@@ -439,8 +490,8 @@ __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __r
                                                                 float* __restrict__ part_s, int* __restrict__ part_i,
                                                                 int* __restrict__ cstat) {
   __shared__ float4 qs[D / 4];
-  __shared__ float ps[4][32];
-  __shared__ int64_t pi[4][32];
+  __shared__ float ps[4][LW];
+  __shared__ int64_t pi[4][LW];
   // COOP (up to 256 queries): rows fetched cooperatively through a per-wave LDS tile (coop_scores) -- a lane walking its
   // own 1-KiB row is a chain of ~8 memory latencies; SLICED also scans the bank through it when a list overflowed
   __shared__ __attribute__((aligned(16))) float tile[(COOP || SLICED) ? 4 : 1][(COOP || SLICED) ? 64 * RESCORE_LD : 4];
@@ -502,11 +553,12 @@ __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __r
   if constexpr (!SLICED) {
     if (threadIdx.x == 0) count[b * cs] = 0;  // every wave has read it: the next level starts from an empty list
   }
-  if (w == 0) {  // 4 k <= 128 partial winners: two per lane
-    float s[2];
-    int id[2];
+  if (w == 0) {  // 4 k <= 128 partial winners: two per lane (LW = 64: 4 k <= 256, four per lane)
+    constexpr int NM = LW / 16;
+    float s[NM];
+    int id[NM];
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
+    for (int u = 0; u < NM; ++u) {
       const int e = lane + 64 * u;
       const bool have = e < 4 * k;
       s[u] = have ? ps[e / k][e % k] : RG_NEG_INF;
@@ -515,7 +567,7 @@ __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __r
     }
     if constexpr (SLICED) {
       // (wave_select writes 64-bit ids: staged through LDS, stored as the 32-bit local ids the merge expects)
-      wave_select<2>(s, id, k, lane, 0, ps[0], pi[0]);
+      wave_select<NM>(s, id, k, lane, 0, ps[0], pi[0]);
       __builtin_amdgcn_wave_barrier();
       const int64_t slot = (b * gridDim.y + blockIdx.y) * k;
       if (lane < k) {
@@ -523,7 +575,7 @@ __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __r
         part_i[slot + lane] = pi[0][lane] >= INT_MAX ? INT_MAX : (int)pi[0][lane];
       }
     } else {
-      wave_select<2>(s, id, k, lane, final_level ? idx_base : 0, out_s + b * k, out_i + b * k);
+      wave_select<NM>(s, id, k, lane, final_level ? idx_base : 0, out_s + b * k, out_i + b * k);
     }
   }
   if constexpr (SLICED) {

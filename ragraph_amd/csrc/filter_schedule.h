@@ -244,6 +244,22 @@ static FilterSchedule filter_schedule(const FilterShape& in) {
     if (sc.bound_keys > sc.ends[0]) sc.bound_keys = sc.ends[0] / FILTER_PAD_KEYS * FILTER_PAD_KEYS;
     if (sc.bound_keys / (FILTER_STAGE_BYTES / (2 * D)) < k) sc.bound_keys = 0;  // every part needs a stage of its own
     sc.i8_levels = i8_ok && B >= 1024 ? (scored ? 3 : 2) : 0;  // (banks below 4 x 4096 keys come here with any batch)
+    if (k > 32) {
+      // Lists of 33 .. 64 keys (the wide entry; plans of k <= 32 never come here): a level admits ~1.3 k (its end / the previous
+      // end) keys per query and an int8 level i8_candf = 2 times that.  The cost-model branch below refuses a plan beyond half the
+      // list capacity; these fixed fractions get the same test per int8 level, earliest first -- at k = 10 a ratio of 8 is 208
+      // int8 candidates, at k = 64 it would be 1331 of 2048 slots on AVERAGE, and overflows (exact scans) the common case.
+      while (sc.i8_levels > 0) {
+        const int l0 = sc.nlev - sc.i8_levels;
+        if (l0 < 0) {
+          sc.i8_levels = sc.nlev;
+          continue;
+        }
+        const double before = l0 ? (double)sc.ends[l0 - 1] : (double)sc.n0;
+        if (1.3 * k * ((double)sc.ends[l0] / before) * 2.0 <= cap / 2) break;
+        --sc.i8_levels;
+      }
+    }
     filter_align_ends(sc, D);
     return sc;
   }
@@ -261,7 +277,11 @@ static FilterSchedule filter_schedule(const FilterShape& in) {
     int64_t nA = 0;
     if (bound) {
       nA = prefix_for(n0);
-      if (nA * 4 > N) break;
+      // (lists of 33 .. 64 keys: every part of the prefix is a ring stage of its own, so k parts are 4 - 16 k keys before the
+      // bound is worth anything -- at D = 64, 48 parts are worth 4096 keys and span 19 968.  A quarter of a 70 000-key bank
+      // holds no such prefix, no sample passes this test, and the call would run the default three levels behind a score slab
+      // with nothing for a prior to replace; half the bank -- the limit filter_call_plan itself sets -- does.  k <= 32: unchanged.)
+      if (nA * (k > 32 ? 2 : 4) > N) break;
       if (B <= 256)  // direct kernel: the prefix streams at ~5 TB/s (8.7 / 22 / 40 us for 54 k / 216 k / 216 k keys x 1 / 16 / 256 queries)
         first = 6.0 + (double)nA * 2.0 * D / 5.0e6 * (1.0 + (double)B / 320.0);
       else
@@ -432,6 +452,19 @@ static size_t filter_repair_bytes(int D, int k, size_t slot_bytes) {
          align_up(q * k * sizeof(float), 256) + align_up(q * k * sizeof(int64_t), 256) + 16 * 1024 /* ten arrays of <= 1 KiB, aligned */;
 }
 
+// Bytes of a call's candidate region.  Lists of 33 .. 64 keys (the wide entry) are plain by rule (filter_scored_lists: 4-byte
+// slots), which would leave the calls of 257 to about 350 queries without the idle room the repair behind a tight bound lives
+// in: their region is at least the repair's size, so every ring-kernel call of the wide entry honours a tight bound.  (k <= 32:
+// the lists and nothing else, as the workspace sizes pinned by the tests have it.)
+static size_t filter_cand_bytes(int64_t B, int cap, size_t slot_bytes, int D, int k) {
+  size_t bytes = (size_t)B * cap * slot_bytes;
+  if (k > 32 && B > FILTER_REPAIR_Q) {
+    const size_t need = filter_repair_bytes(D, k, slot_bytes);
+    if (bytes < need) bytes = need;
+  }
+  return bytes;
+}
+
 static void filter_drop_first_level(FilterSchedule& sc) {
   for (int l = 0; l + 1 < sc.nlev; ++l) sc.ends[l] = sc.ends[l + 1];
   --sc.nlev;
@@ -526,7 +559,7 @@ static FilterCall filter_call_plan(const FilterShape& in, FilterSchedule sc) {
   // level anyway.  The step against the three levels under the prior alone: 19.68 - 19.83 -> 18.30 - 18.31 ms (profiles/tight_prior.txt).
   {
     const size_t slot = c.scored_slots ? sizeof(int2) : sizeof(int);
-    const size_t idle = align_up((size_t)B * c.cap * slot, 256) + align_up((size_t)B * filter_bound_parts(k, INT64_MAX, 256) * sizeof(int), 256);
+    const size_t idle = align_up(filter_cand_bytes(B, c.cap, slot, D, k), 256) + align_up((size_t)B * filter_bound_parts(k, INT64_MAX, 256) * sizeof(int), 256);
     c.tight = c.spec && !in.exchange && B > 256 && in.tight == in.tight && in.tight > in.prior && in.tight < 2.f &&
               idle >= filter_repair_bytes(D, k, slot);
   }

@@ -197,7 +197,11 @@ __global__ void __launch_bounds__(256) verify_merged_prior_kernel(const float* _
 // FILTER_FIX_SLICES key slices (as many as keep ~256 workgroups busy), each workgroup leaves its slice's k winners in
 // part_s / part_i, and the query's last slice to finish (a ticket) merges them: 1.6 ms for one query.  Many overflowed
 // queries take one workgroup each as before.  A ZERO query is answered without a scan.
-template <int D>
+// LW = 64 (the wide entry, 33 <= k <= 64): a slice leaves up to 64 winners, so the scans are cut into HALF as many slices
+// (FILTER_FIX_SLICES * 32 / LW = 8) rather than carrying 16 x 64 = sixteen slots per lane of the merging wave: SL k <= 512
+// and the part_s / part_i buffers keep their size, the merge keeps its eight slots, and a path that ordinary banks never take
+// (it exists for adversarial clusters) gives up at most a factor of two on a lone overflowed query.
+template <int D, int LW = 32>
 __global__ void __launch_bounds__(256) topk_overflow_fixup_kernel(const float* __restrict__ Qn, const float* __restrict__ Kn,
                                                                   int64_t N, int k, int64_t idx_base,
                                                                   const int* __restrict__ overflow,
@@ -210,8 +214,8 @@ __global__ void __launch_bounds__(256) topk_overflow_fixup_kernel(const float* _
                                                                   int* __restrict__ stats) {
   __shared__ float4 qs[D / 4];
   __shared__ __attribute__((aligned(16))) float tile[4][64 * RESCORE_LD];
-  __shared__ float ps[4][32];
-  __shared__ int64_t pi[4][32];
+  __shared__ float ps[4][LW];
+  __shared__ int64_t pi[4][LW];
   __shared__ int ticket_s;
   const int n_over = *overflow;
   if (stats && blockIdx.x == 0 && threadIdx.x == 0) stats[20] = n_over;   // (final: every launch that counts runs before this one)
@@ -241,7 +245,7 @@ __global__ void __launch_bounds__(256) topk_overflow_fixup_kernel(const float* _
   if (n_over <= 0) return;
   int SL = 1;
   if (n_over <= FILTER_FIX_MAX_Q)
-    while (SL < FILTER_FIX_SLICES && 2 * SL * n_over <= (int)gridDim.x) SL *= 2;
+    while (SL < FILTER_FIX_SLICES * 32 / LW && 2 * SL * n_over <= (int)gridDim.x) SL *= 2;
   const int64_t chunk = ((N + SL - 1) / SL + 63) / 64 * 64;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int64_t item = blockIdx.x; item < (int64_t)n_over * SL; item += gridDim.x) {
@@ -252,14 +256,14 @@ __global__ void __launch_bounds__(256) topk_overflow_fixup_kernel(const float* _
     if (threadIdx.x < D / 4) qs[threadIdx.x] = reinterpret_cast<const float4*>(Qn + b * D)[threadIdx.x];
     __syncthreads();
     if (SL == 1) {
-      exact_scan_query<D>(qs, Kn, N, k, idx_base, tile, ps, pi, out_s + b * k, out_i + b * k);
+      exact_scan_query<D, LW>(qs, Kn, N, k, idx_base, tile, ps, pi, out_s + b * k, out_i + b * k);
       continue;
     }
     const int64_t lo = sl * chunk, hi = lo + chunk < N ? lo + chunk : N;
-    float* my_s = part_s + ((int64_t)o * SL + sl) * 32;
-    int64_t* my_i = part_i + ((int64_t)o * SL + sl) * 32;
+    float* my_s = part_s + ((int64_t)o * SL + sl) * LW;
+    int64_t* my_i = part_i + ((int64_t)o * SL + sl) * LW;
     if (lo < hi) {
-      exact_scan_query<D>(qs, Kn + lo * D, hi - lo, k, lo, tile, ps, pi, my_s, my_i);   // (indices local to the bank)
+      exact_scan_query<D, LW>(qs, Kn + lo * D, hi - lo, k, lo, tile, ps, pi, my_s, my_i);   // (indices local to the bank)
     } else if (threadIdx.x < k) {
       my_s[threadIdx.x] = RG_NEG_INF;
       my_i[threadIdx.x] = INT64_MAX;
@@ -279,7 +283,7 @@ __global__ void __launch_bounds__(256) topk_overflow_fixup_kernel(const float* _
         s8[u] = RG_NEG_INF;
         id8[u] = INT_MAX;
         if (e < SL * k) {
-          const int64_t at = ((int64_t)o * SL + e / k) * 32 + e % k;
+          const int64_t at = ((int64_t)o * SL + e / k) * LW + e % k;
           const int64_t pv = __builtin_nontemporal_load(part_i + at);
           if (pv < INT_MAX) {
             s8[u] = __builtin_nontemporal_load(part_s + at);

@@ -7,7 +7,7 @@
 
 namespace ragraph {
 
-// ---- canonical top-k of a wave's 64 NSL (score, id) pairs (score descending, id ascending; k <= 32) -------------------
+// ---- canonical top-k of a wave's 64 NSL (score, id) pairs (score descending, id ascending; k <= 64) -------------------
 // A pair travels as one 64-bit key whose unsigned order is the canonical order: the score's bits made monotone in the
 // upper word, ~id in the lower; an empty slot (-inf, INT_MAX) and a pair already taken are key 0, which decodes to
 // (-inf, INT64_MAX).  Round r: every lane's best remaining key, the wave's maximum of those -- four DPP steps inside
@@ -246,7 +246,7 @@ __device__ __forceinline__ void rescore_query(const float4* __restrict__ qrow, c
   const int first_keys = cand[lane * CS];  // (no dependence on n: the list has >= 64 slots; issued next to the count's load)
   float s[NS + 1];
   int id[NS + 1];
-  // the previous level's winners ride along as already-scored candidates (lane l holds entry l; k <= 32)
+  // the previous level's winners ride along as already-scored candidates (lane l holds entry l; k <= 64)
   s[NS] = RG_NEG_INF;
   id[NS] = INT_MAX;
   if (prev_s && lane < k) {

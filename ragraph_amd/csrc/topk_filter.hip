@@ -24,6 +24,8 @@
 // a few queries into key slices); *overflow only counts those rows.  The call never synchronises and reads nothing back.
 // Levels may run on an int8 copy of the bank instead (v_mfma_i32_16x16x64_i8, integer thresholds: filter_common.h), whose
 // candidate lists can carry the integer score that admitted each key (SCORED: topk_rescore_scored_kernel).
+// Lists of 33 .. 64 keys (ragraph_topk_cosine_filtered_wide_f32): the same launches of the MFMA kernels, which know no k, and
+// the LW = 64 instantiations of the kernels that carry a list (filter_rescore.h, filter_verify_fixup.h).
 //
 // Two filter kernels share one bank layout (filter_common.h: MFMA fragment order of v_mfma_f32_16x16x32_bf16):
 // topk_filter_direct_kernel (topk_filter_direct.hip) for up to 256 queries, and this file's RING kernel above that:
@@ -316,6 +318,7 @@ struct FilterWs {
   float* theta;         // [B] the first bound
   int* overflow_list;   // [B] queries the final level sends to the exact fallback
   int* fix_done;        // [FILTER_FIX_MAX_Q] tickets, [.. x FILTER_FIX_SLICES x 32] partial winners of the sliced fallback scans
+                        // (the wide entry: half the slices x 64 winners, the same bytes)
   float* fix_s;
   int64_t* fix_i;
   float* part_s;        // (B <= 64) sliced rescoring: [B][8][k] partial winners
@@ -341,7 +344,7 @@ static size_t filter_ws_carve(char* w, const FilterShape& in, const FilterCall& 
   f.count = reinterpret_cast<int*>(take((size_t)B * filter_count_stride(B) * sizeof(int)));
   f.flag = reinterpret_cast<unsigned char*>(take((size_t)B));
   // (a call that may keep scored lists -- {key, I} -- gets 8 bytes per slot)
-  f.cand = reinterpret_cast<int*>(take((size_t)B * c.cap * (c.scored_slots ? sizeof(int2) : sizeof(int))));
+  f.cand = reinterpret_cast<int*>(take(filter_cand_bytes(B, c.cap, c.scored_slots ? sizeof(int2) : sizeof(int), D, k)));
   f.gmax = reinterpret_cast<int*>(take((size_t)B * filter_bound_parts(k, INT64_MAX, 256) * sizeof(int)));
   f.theta = reinterpret_cast<float*>(take((size_t)B * sizeof(float)));
   f.overflow_list = reinterpret_cast<int*>(take((size_t)B * sizeof(int)));
@@ -359,13 +362,16 @@ static size_t filter_ws_carve(char* w, const FilterShape& in, const FilterCall& 
 
 // ---- the host queries: readers of the call plan ---------------------------------------------------------------------
 // The one argument check of the plan's readers and of the call: 0, or the error code of a shape no filtered call takes.
-static int filter_shape_code(int64_t B, int64_t N, int D, int k) {
+// One path per k: the entries built for lists of 32 take 1 <= k <= 32, the WIDE entries (lists of 64: the LW = 64 instantiations
+// of the list-carrying kernels) take 33 <= k <= 64.
+static int filter_shape_code(int64_t B, int64_t N, int D, int k, bool wide = false) {
   if (!filter_dim_ok(D)) return RAGRAPH_EUNSUPPORTED;
-  return B >= 1 && N >= 1 && k >= 1 && k <= 32 && k <= N ? RAGRAPH_OK : RAGRAPH_EINVAL;
+  const bool k_ok = wide ? (k >= 33 && k <= 64) : (k >= 1 && k <= 32);
+  return B >= 1 && N >= 1 && k_ok && k <= N ? RAGRAPH_OK : RAGRAPH_EINVAL;
 }
-#define RG_REQUIRE_FILTER_SHAPE(who, B, N, D, k)                                                                      \
+#define RG_REQUIRE_FILTER_SHAPE(who, B, N, D, k, wide)                                                                \
   do {                                                                                                                \
-    const int code__ = filter_shape_code(B, N, D, k);                                                                 \
+    const int code__ = filter_shape_code(B, N, D, k, wide);                                                           \
     RG_REQUIRE(code__ != RAGRAPH_EUNSUPPORTED, RAGRAPH_EUNSUPPORTED, who ": D=%d not in {64,128,256}", D);           \
     RG_REQUIRE(code__ == RAGRAPH_OK, RAGRAPH_EINVAL, who ": bad B/N/k");                                              \
   } while (0)
@@ -419,9 +425,9 @@ extern "C" int ragraph_topk_cosine_filtered_i8_levels(int64_t B, int64_t N, int 
   return filter_call_plan(in, filter_schedule(in)).i8_levels;
 }
 
-extern "C" int ragraph_topk_cosine_filtered_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]) {
+static int filter_plan_query(int64_t B, int64_t N, int D, int k, int64_t plan[7], bool wide) {
   RG_REQUIRE(plan, RAGRAPH_EINVAL, "topk_cosine_filtered_plan: null pointer");
-  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered_plan", B, N, D, k);
+  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered_plan", B, N, D, k, wide);
   FilterShape in = filter_query_shape(B, N, D, k, 1, false);
   filter_query_follow_tight(in);
   // (the plan of one whole bank IS its schedule: filter_schedule leaves such a bank bound_keys <= N / 4 or <= ends[0] < N / 2
@@ -433,6 +439,21 @@ extern "C" int ragraph_topk_cosine_filtered_plan(int64_t B, int64_t N, int D, in
   for (int l = 0; l < FILTER_MAX_LEVELS; ++l) plan[3 + l] = l < c.nlev ? c.level[l].key1 : 0;
   plan[6] = c.bound_keys;
   return c.nlev;
+}
+extern "C" int ragraph_topk_cosine_filtered_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]) {
+  return filter_plan_query(B, N, D, k, plan, false);
+}
+// The wide entry's queries (33 <= k <= 64): the same plan words, the same workspace layout -- the lists of the fixup scan
+// keep their size (half the slices of twice the winners), every other buffer is sized by k as ever.
+extern "C" int ragraph_topk_cosine_filtered_wide_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]) {
+  return filter_plan_query(B, N, D, k, plan, true);
+}
+extern "C" size_t ragraph_topk_cosine_filtered_wide_workspace_bytes(int64_t B, int64_t N, int D, int k) {
+  if (filter_shape_code(B, N, D, k, true) != RAGRAPH_OK) return 0;
+  // never less than the same shape needs at k = 32 (a handful of queries keep 8 sub-lists per query while 8 k <= 256 and 4
+  // beyond: the lists alone would make k = 33 the smaller call): a buffer sized for a wide call serves every shorter list
+  const size_t own = filter_workspace_bytes(B, N, D, k, 1), narrow = N >= 32 ? filter_workspace_bytes(B, N, D, 32, 1) : 0;
+  return own > narrow ? own : narrow;
 }
 
 // Would a sharded call of this shape speculate under a prior?  (Any valid one: the answer is the plan's, not the value's.)
@@ -645,7 +666,7 @@ static RescoreKind rescore_kind(int64_t B, int k, bool scored, bool few) {
 // Exact rescoring of a level's candidates (+ merge with the running result when `merge`) and canonical selection.  Every
 // kind lists the queries whose list overflowed for topk_overflow_fixup_kernel (scan_n = 0: the one-wave-per-query kernels'
 // own wave scanning a million keys took 94 ms).
-template <int D>
+template <int D, int LW>
 static int run_rescore(const FilterWs& f, const float* Kn, int64_t N, int64_t B, int cap, int k, int64_t idx_base, int merge,
                        int final_level, float* out_scores, int64_t* out_idx, int* overflow, RescoreKind kind, const FilterThr& thr,
                        int* cstat, hipStream_t st) {
@@ -654,11 +675,11 @@ static int run_rescore(const FilterWs& f, const float* Kn, int64_t N, int64_t B,
   const int cs = filter_count_stride(B);
   const int64_t scan_n = 0;
 #define RG_SCORED(SMALL_)                                                                                                        \
-  hipLaunchKernelGGL((topk_rescore_scored_kernel<D, SMALL_>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,    \
+  hipLaunchKernelGGL((topk_rescore_scored_kernel<D, SMALL_, LW>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,    \
                      reinterpret_cast<const int2*>(f.cand), B, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx,   \
                      overflow, f.overflow_list, f.flag, scan_n, thr, cstat)
 #define RG_WIDE(SLICED_, COOP_, GRID_, PART_S_, PART_I_)                                                                         \
-  hipLaunchKernelGGL((topk_rescore_wide_kernel<D, SLICED_, COOP_>), GRID_, dim3(256), 0, st, f.Qn, Kn, f.count, f.cand, B, N,    \
+  hipLaunchKernelGGL((topk_rescore_wide_kernel<D, SLICED_, COOP_, LW>), GRID_, dim3(256), 0, st, f.Qn, Kn, f.count, f.cand, B, N,    \
                      cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx, overflow, f.overflow_list, f.flag, PART_S_, \
                      PART_I_, cstat)
 #define RG_COOP(FEW_)                                                                                                            \
@@ -781,7 +802,7 @@ static FilterRepairWs filter_repair_carve(const FilterWs& f, int D, int k, bool 
 }
 
 // Step 6b of a call under a tight bound (the comment block in filter_verify_fixup.h tells the whole story).
-template <int D>
+template <int D, int LW>
 static int run_tight_repair(const FilteredArgs& a, const FilterCall& c, const FilterShape& in, const FilterWs& f, FilterThr thr,
                             const signed char* K8, int* stats, hipStream_t st) {
   const int64_t B = a.B, N = a.N;
@@ -813,7 +834,7 @@ static int run_tight_repair(const FilteredArgs& a, const FilterCall& c, const Fi
   int rc = run_pass<D>(r.f, a.Kb, K8, FILTER_REPAIR_Q, 0, N, thr2, FILTER_LIST_CAP, 0, lv.int8, c.repair_scored, in.env, in.cus, -1, st,
                        FilterGate{stats + 22, 1, FILTER_REPAIR_Q});
   if (rc != RAGRAPH_OK) return rc;
-  rc = run_rescore<D>(r.f, a.Kn, N, FILTER_REPAIR_Q, FILTER_LIST_CAP, k, 0, 0, 0, r.out_s, r.out_i, r.dummy,
+  rc = run_rescore<D, LW>(r.f, a.Kn, N, FILTER_REPAIR_Q, FILTER_LIST_CAP, k, 0, 0, 0, r.out_s, r.out_i, r.dummy,
                       rescore_kind(FILTER_REPAIR_Q, k, c.repair_scored, false), thr2, nullptr, st);
   if (rc != RAGRAPH_OK) return rc;
   hipLaunchKernelGGL(filter_repair_scatter_kernel, dim3(FILTER_REPAIR_Q), dim3(64), 0, st, r.list, r.out_s, r.out_i, r.f.flag, k,
@@ -827,13 +848,13 @@ static int run_tight_repair(const FilteredArgs& a, const FilterCall& c, const Fi
                    FilterGate{stats + 22, FILTER_REPAIR_Q + 1, INT_MAX});
   if (rc != RAGRAPH_OK) return rc;
   // the call's final rescoring: the level's lists (empty unless it ran) merged with the running rows
-  return run_rescore<D>(f, a.Kn, N, B, c.cap, k, a.idx_base, 1, 1, a.out_scores, a.out_idx, a.overflow,
+  return run_rescore<D, LW>(f, a.Kn, N, B, c.cap, k, a.idx_base, 1, 1, a.out_scores, a.out_idx, a.overflow,
                         rescore_kind(B, k, lv.scored, false), thr, nullptr, st);
 }
 
 // Steps 3 - 7 of a call (1, 2: filtered_entry): executes the plan `c` that filter_call_plan made of the shape `in` -- carve,
 // prepare, first bound, the levels, verify / fixup -- and decides nothing itself.
-template <int D>
+template <int D, int LW>
 static int run_filtered(const FilteredArgs& a, const FilterCall& c, const FilterShape& in) {
   hipStream_t st = as_stream(a.stream);
   const int64_t B = a.B, N = a.N;
@@ -955,7 +976,7 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
     }
     if (rc != RAGRAPH_OK) return rc;
     if (t_prof) t_prof->have = l + 1;
-    rc = run_rescore<D>(f, a.Kn, N, B, c.cap, k, a.idx_base, l > 0, l == c.level_final, out_scores, out_idx, a.overflow,
+    rc = run_rescore<D, LW>(f, a.Kn, N, B, c.cap, k, a.idx_base, l > 0, l == c.level_final, out_scores, out_idx, a.overflow,
                         rescore_kind(B, k, lv.scored, sharded && l > 0), thr, stats + 2 + l, st);
     if (rc != RAGRAPH_OK) return rc;
     if (l + 1 == c.nlev) break;
@@ -968,7 +989,7 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
   }
 
   // 6b. a tight bound: the soft verdict and the repair (filter_verify_fixup.h), every launch enqueued unconditionally
-  if (c.tight && (rc = run_tight_repair<D>(a, c, in, f, thr, v8.K8, stats, st)) != RAGRAPH_OK) return rc;
+  if (c.tight && (rc = run_tight_repair<D, LW>(a, c, in, f, thr, v8.K8, stats, st)) != RAGRAPH_OK) return rc;
 
   // 7. verify / fixup
   if (c.spec && !sharded) {   // (a shard's lists prove nothing alone: the owner of a row verifies the MERGED k-th best)
@@ -978,7 +999,7 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
   }
   // overflowed queries (none on ordinary banks) and the queries a prior was too high for: exact fp32 scan on the device --
   // no host read-back
-  hipLaunchKernelGGL(topk_overflow_fixup_kernel<D>, dim3(256), dim3(256), 0, st, f.Qn, a.Kn, N, k, a.idx_base,
+  hipLaunchKernelGGL((topk_overflow_fixup_kernel<D, LW>), dim3(256), dim3(256), 0, st, f.Qn, a.Kn, N, k, a.idx_base,
                      a.overflow, f.overflow_list, a.overflow_idx, out_scores, out_idx, f.fix_done, f.fix_s, f.fix_i, B, f.flag,
                      sharded ? nullptr : stats);
   RG_CHECK_LAUNCH("topk_cosine_filtered(overflow fallback)");
@@ -989,12 +1010,12 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
 // per-call switches are read here and nowhere else.  The schedule (its pow() search) is computed once for a single bank; a
 // shard among several that pool their first sample computes two -- the single bank's, which sizes the minimum workspace,
 // and its own.  filter_call_plan (cheap arithmetic) runs three times: twice for that size, once for the call.
-static int filtered_entry(const FilteredArgs& a) {
+static int filtered_entry(const FilteredArgs& a, bool wide = false) {
   const int64_t B = a.B, N = a.N, plan_N = a.plan_N;
   const int D = a.D, k = a.k;
   RG_REQUIRE(a.Q && a.Kn && a.Kb && a.out_scores && a.out_idx && a.overflow && a.ws, RAGRAPH_EINVAL, "topk_cosine_filtered: null pointer");
   RG_REQUIRE(a.n_shards >= 1, RAGRAPH_EINVAL, "topk_cosine_filtered: n_shards=%d", a.n_shards);
-  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered", B, N, D, k);
+  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered", B, N, D, k, wide);
   RG_REQUIRE(N < (int64_t)INT_MAX - 1024, RAGRAPH_EUNSUPPORTED, "topk_cosine_filtered: shard rows must fit int32");
   RG_REQUIRE(plan_N >= N && (a.exchange || plan_N - N <= 1024), RAGRAPH_EINVAL, "topk_cosine_filtered: plan_N must be the largest shard's size");
   RG_REQUIRE(!a.exchange || a.theta, RAGRAPH_EINVAL, "topk_cosine_filtered: an exchange needs the theta buffer");
@@ -1009,9 +1030,14 @@ static int filtered_entry(const FilteredArgs& a) {
   const FilterShape in{B, N, plan_N, D, k, a.n_shards, a.exchange != nullptr, t_prior, t_max_i8_levels, false, one.env, one.cus, t_tight};
   const FilterCall c = filter_call_plan(in, a.exchange && a.n_shards > 1 ? filter_schedule(in) : sc_one);
   if (c.exact_participant) return run_exact_participant(a, c);
-  if (D == 256) return run_filtered<256>(a, c, in);
-  if (D == 128) return run_filtered<128>(a, c, in);
-  return run_filtered<64>(a, c, in);
+  if (wide) {  // (single bank only: the wide entry has no exchange, so no exact participant either)
+    if (D == 256) return run_filtered<256, 64>(a, c, in);
+    if (D == 128) return run_filtered<128, 64>(a, c, in);
+    return run_filtered<64, 64>(a, c, in);
+  }
+  if (D == 256) return run_filtered<256, 32>(a, c, in);
+  if (D == 128) return run_filtered<128, 32>(a, c, in);
+  return run_filtered<64, 32>(a, c, in);
 }
 
 extern "C" int ragraph_topk_cosine_filtered_f32(const float* Q, int64_t B, const float* Kn, const float* Kp,
@@ -1020,6 +1046,17 @@ extern "C" int ragraph_topk_cosine_filtered_f32(const float* Q, int64_t B, const
                                                 int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream) {
   return filtered_entry({Q, B, Kn, Kp, Kb, N, D, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
                          N, nullptr, nullptr, nullptr, 1});
+}
+
+// Lists of 33 .. 64 keys: the same call -- schedule, statistics words, the thread's prior, tight bound and int8 cap -- through
+// the LW = 64 instantiations of the kernels that carry a list (rescoring, scored rounds, scans and their merges).  The MFMA
+// kernels compare against thresholds and append to lists: they are the same launches.
+extern "C" int ragraph_topk_cosine_filtered_wide_f32(const float* Q, int64_t B, const float* Kn, const float* Kp,
+                                                     const uint16_t* Kb, int64_t N, int D, int k, int64_t idx_base,
+                                                     float* out_scores, int64_t* out_idx, int* overflow,
+                                                     int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream) {
+  return filtered_entry({Q, B, Kn, Kp, Kb, N, D, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
+                         N, nullptr, nullptr, nullptr, 1}, true);
 }
 
 extern "C" int ragraph_topk_cosine_filtered_sharded_f32(const float* Q, int64_t B, const float* Kn, const float* Kp,

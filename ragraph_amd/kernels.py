@@ -329,6 +329,33 @@ def filter_helps(B: int, n_keys: int, D: int, k: int) -> bool:
 FILTER_MIN_B = int(os.environ.get("RAGRAPH_FILTER_MIN_B", "1"))  # banks of >= 64 k keys: filtered from this many queries
 
 
+def filter_wide_helps(B: int, n_keys: int, D: int, k: int) -> bool:
+    """filter_helps for lists of 33 .. 64 keys (the wide entry behind topk_cosine_filtered): True where the filtered call is
+    the faster way to the bits of topk_cosine, whose fp32 score slabs are all such a k had before.  Host arithmetic only."""
+    if os.environ.get("RAGRAPH_EXACT_FP32") == "1":
+        return False
+    if D not in (64, 128, 256) or not 32 < k <= 64:
+        return False
+    # filter_helps' rule at k = 32, class by class, kept where tools/filter_wide_probe.py measured the wide call faster than the
+    # slabs by more than the spread of the pair (MI355X, ms, slab vs wide at k = 33 / 41 / 64; profiles/filter_wide.txt):
+    #   N >= 65536, every batch size: 100 000 x 1M x 256: 1131 vs 34.2 / 1140 vs 37.8 / 1170 vs 49.5 (k = 32 filtered: 33.6);
+    #     4096 x 1M x 256: 46 vs 1.7 / 47 vs 1.8 / 48 vs 2.3;  256 x 1M: 2.42 vs 0.25 / 2.37 vs 0.28 / 2.44 vs 0.33;
+    #     1 / 16 / 64 x 1M at k = 64: 0.77 vs 0.31 / 0.82 vs 0.26 / 0.89 vs 0.32;  4096 x 4M x 64: 160 vs 1.6 / 162 vs 1.7 / 168 vs 2.0;
+    #     4096 x 200 000 x 128: 5.0 vs 0.46 / 5.1 vs 0.52 / 5.3 vs 0.62;  600 x 70 000 x 256: 0.49 vs 0.15 / 0.50 vs 0.18 / 0.57 vs 0.23;
+    #     256 x 70 000 x 256: 0.25 vs 0.13 / 0.27 vs 0.14 / 0.33 vs 0.21;  16 x 70 000 x 64: 1.59 / 1.38 / 1.22 times faster;
+    #   32768 <= N < 65536, from 128 queries: 128 x 40 000 x 256: 1.58 / 1.65 / 1.26 times faster; 2100 x 40 000: 2.39 / 2.08 / 1.99
+    #     (64 x 40 000, outside the rule: 1.55 / 1.40 times faster but 0.79 at k = 64: stays out);
+    #   8192 <= N < 32768: only banks of 20 000 keys up to k = 41 won -- 700 x 20 000 x 128: 1.56 / 1.55 times faster, k = 64: 0.86;
+    #     2048 x 20 000 x 64: 1.09 / 1.05, k = 64: a draw -- and 10 000 keys did not: 1024 x 10 000 x 256: 1.00 / 0.89 / 0.88;
+    #     8192 x 10 000 x 64: 1.00 / 0.98 / 0.97.  Nothing was measured between 10 000 and 20 000 keys or between k = 41 and 64:
+    #     those stay on the slabs.
+    if n_keys >= 32768:
+        return filter_helps(B, n_keys, D, 32)
+    if n_keys < 20000 or k > 41:
+        return False
+    return B >= (512 if D >= 128 else 2048)
+
+
 _EXCHANGE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)
 
 # Candidate statistics of a filtered call: the 16 ints its launches leave at the end of its workspace (include/ragraph_hip.h:
@@ -383,7 +410,10 @@ def topk_cosine_filtered(q: torch.Tensor, keys_normalized: torch.Tensor, keys_bf
     scores = torch.empty((B, k), dtype=torch.float32, device=q.device)
     idx = torch.empty((B, k), dtype=torch.int64, device=q.device)
     overflow = torch.empty(1, dtype=torch.int32, device=q.device)
-    if exchange is None:
+    wide = exchange is None and 32 < k <= 64   # (lists of 33 .. 64 keys: the wide entry -- one path per k)
+    if wide:
+        nbytes = L.ragraph_topk_cosine_filtered_wide_workspace_bytes(B, max(plan_n, Nk), D, k)
+    elif exchange is None:
         nbytes = L.ragraph_topk_cosine_filtered_workspace_bytes(B, max(plan_n, Nk), D, k)
     else:  # (the sharded schedule -- planned for (plan_n, n_shards) -- can need another level-0 scratch)
         nbytes = L.ragraph_topk_cosine_filtered_sharded_workspace_bytes(B, max(plan_n, Nk), D, k,
@@ -394,9 +424,9 @@ def topk_cosine_filtered(q: torch.Tensor, keys_normalized: torch.Tensor, keys_bf
     off = L.ragraph_topk_cosine_filtered_stats_offset(ws.numel())
     stats = ws[off:off + 128].view(torch.int32)   # (32 words; valid until the next filtered call on this stream)
     if exchange is None:
-        N.check(L.ragraph_topk_cosine_filtered_f32(q.data_ptr(), B, kn.data_ptr(), kp, keys_bf16.data_ptr(), Nk, D, k,
-                                                   idx_base, scores.data_ptr(), idx.data_ptr(), overflow.data_ptr(), None,
-                                                   ws.data_ptr(), ws.numel(), _stream()),
+        entry = L.ragraph_topk_cosine_filtered_wide_f32 if wide else L.ragraph_topk_cosine_filtered_f32
+        N.check(entry(q.data_ptr(), B, kn.data_ptr(), kp, keys_bf16.data_ptr(), Nk, D, k, idx_base, scores.data_ptr(),
+                      idx.data_ptr(), overflow.data_ptr(), None, ws.data_ptr(), ws.numel(), _stream()),
                 "topk_cosine_filtered")
         return (scores, idx, overflow, stats) if return_stats else (scores, idx, overflow)
     theta = torch.empty(B, dtype=torch.float32, device=q.device)

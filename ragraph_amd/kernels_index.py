@@ -444,6 +444,11 @@ class KeyIndex:
                 self.last_prior = prior
                 return s, i
             fhelps = None  # (fp32 kernels: the shard's own exact top-k, no exchange needed)
+        if exchange is None and 32 < k <= TOPK_MAX:
+            # lists of 33 .. 64 keys on one bank: the wide filtered entry behind ops.topk_cosine_filtered, where the ops' own rule
+            # says it pays (an ops object without the rule keeps the fp32 score slabs); everything below -- the overflow poll,
+            # the re-probe, the learned bounds per (bank, k) -- applies to it as to k <= 32
+            fhelps = getattr(ops, "filter_wide_helps", None)
         self._poll_overflow()
         self._maybe_reprobe(B)
         self._queries += B
@@ -487,7 +492,9 @@ class KeyIndex:
                         for b0 in range(0, B, self.MAX_FILTERED_BATCH)]
                 return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
             cap, had_i8 = self._cap_i8()
-            had_i8 = had_i8 and ops.filtered_i8_levels(B, kn.shape[0], D, k) > 0   # (did THIS call have int8 levels?)
+            # (did THIS call have int8 levels?  The plan queries answer for k <= 32; a wide call under an open cap is taken to
+            # have had them: an overflowing bank then leaves int8 first and the filter at the next verdict, the usual order)
+            had_i8 = had_i8 and (k > 32 or ops.filtered_i8_levels(B, kn.shape[0], D, k) > 0)
             stats = None
             prior = self._prior_for(B, k)
             tight = self._tight_for(B, k, prior)
