@@ -3,6 +3,7 @@
 Same constructor and forward signatures as the reference (including its `feture_size` spelling); hyper-parameters are
 the reference's hard-coded constants exposed as attributes.
 """
+import functools
 import os
 
 import torch
@@ -64,10 +65,10 @@ class RAGraph(nn.Module):
         if mixed and (self.query_shard is not None or hasattr(tgb, "retrieve_reduced_rows")):
             raise K.RagraphNativeError("structure-aware retrieval (structure_weight != 0) runs on one GPU with the whole "
                                        "bank: the query-sharded and key-sharded forwards do not mix position codes")
-        if self.query_shard is not None and not self.training and self.flavour == "node":
-            hybrid = (getattr(tgb, "values_replicated", False) and hasattr(tgb, "retrieve_reduced_rows")
-                      and (tgb.collective or tgb.emulate_world > 1))
-            sliced = self._forward_sliced_encode(features, g, hybrid)
+        shards_queries = self.query_shard is not None and not self.training and self.flavour == "node"
+        own_rows = not self.training and self.flavour == "node" and self._finishes_own_rows(tgb)
+        if shards_queries:
+            sliced = self._forward_sliced_encode(features, g, hybrid=own_rows)
             if sliced is not None:
                 return sliced
         pretrain_embedddings = self.pretrain_model.inference(features, g)                      # RAGraph.py:40
@@ -80,39 +81,31 @@ class RAGraph(nn.Module):
         # structure-aware retrieval: the query rows' position codes (ToyGraphBase.py:49-50 of the few-shot flavour); raises
         # here, before any retrieval kernel, when the bank holds no codes
         pos = tgb.search_positions(g, None, anchors) if mixed else None
-        if self.query_shard is not None and not self.training and self.flavour == "node":
-            if (getattr(tgb, "values_replicated", False) and hasattr(tgb, "retrieve_reduced_rows")
-                    and (tgb.collective or tgb.emulate_world > 1)):
-                return self._forward_hybrid(queries, pretrain_embedddings, g)
-            return self._forward_query_shard(queries, pretrain_embedddings, g)
-        if (not self.training and self.flavour == "node" and getattr(tgb, "values_replicated", False)
-                and hasattr(tgb, "retrieve_reduced_rows") and (tgb.collective or tgb.emulate_world > 1)):
+        if own_rows:
             return self._forward_key_shard(queries, pretrain_embedddings, g)
+        if shards_queries:
+            return self._forward_query_shard(queries, pretrain_embedddings, g)
         # The k-hop propagation needs only the embeddings, not the retrieval: on a large graph (inference) it is enqueued on
         # a side stream, where its SpMM launches fill the latency-bound rescoring phases between the retrieval's matrix
         # passes instead of running behind them (c2: 0.4 ms of 37.5).  Same kernels, same bits; one fork / join.
-        side = None
+        def hops():
+            return self._pool(Propagation.aggregate_k_hop_features(g, pretrain_embedddings, self.query_graph_hop), g)  # :51
+
+        join = None
         # (training too: the encoder's output is detached -- preprompt.py:62 -- so the hops carry no tape; only a caller that
         # does ask gradients of the embeddings keeps them on the main stream, inside autograd's stream bookkeeping)
         if (self.finetune and not (torch.is_grad_enabled() and pretrain_embedddings.requires_grad) and queries.is_cuda
                 and queries.shape[0] >= self.OVERLAP_MIN_NODES):
             # (small forwards gain nothing from the fork, captured in a HIP graph or not: Cora-sized replay 0.163 ms
             # without, 0.172 with the hops on a parallel branch -- round 3)
-            main = torch.cuda.current_stream()
-            side = self._side_stream(queries.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                query_embeddings = self._pool(
-                    Propagation.aggregate_k_hop_features(g, pretrain_embedddings, self.query_graph_hop), g)
-        if (side is not None and not add_noise and not torch.is_grad_enabled() and self.flavour == "node"
+            join = self._fork(hops, queries.device)
+        if (join is not None and not add_noise and not torch.is_grad_enabled() and self.flavour == "node"
                 and type(tgb).retrieve_reduced is ToyGraphBase.retrieve_reduced
                 and os.environ.get("RAGRAPH_GATHER_MIX", "1") != "0"):   # (=0: the separate entries, A/B)
             # a large inference forward: the winners' value sum goes straight into the prompt fusion (:48-49 + :53 in one
             # launch -- the [n, D] sum is never written, the axpby launch is gone); same bits as the separate entries below
             _, idx = tgb.topk(queries, tgb.retrieve_num, pos) if mixed else tgb.topk(queries, tgb.retrieve_num)   # :43
-            main.wait_stream(side)
-            query_embeddings.record_stream(main)
-            hidden, rag_label = K.gather_reduce_mix(tgb.resource_values, tgb.resource_labels, idx, query_embeddings,
+            hidden, rag_label = K.gather_reduce_mix(tgb.resource_values, tgb.resource_labels, idx, join(),
                                                     1 - self.retrieve_weight, self.retrieve_weight)
             return A.softmax_mix(self.decoder(hidden), rag_label, self.label_weight)           # :54-57
         if add_noise:
@@ -124,15 +117,17 @@ class RAGraph(nn.Module):
             rag_embedding, rag_label, _ = tgb.retrieve_reduced(queries)                        # :43,48-49 fused
         if not self.finetune:
             return rag_label                                                                   # :60-63
-        if side is not None:
-            main.wait_stream(side)
-            query_embeddings.record_stream(main)
-        else:
-            query_embeddings = self._pool(
-                Propagation.aggregate_k_hop_features(g, pretrain_embedddings, self.query_graph_hop), g)  # :51
+        query_embeddings = join() if join is not None else hops()
         return self._fuse_decode(query_embeddings, rag_embedding, rag_label)                   # :53-57
 
     OVERLAP_MIN_NODES = 16384   # below: the fork / join costs more than the overlap gives
+
+    @staticmethod
+    def _finishes_own_rows(tgb) -> bool:
+        """Does this bank finish only ITS rows of the batch (ragraph_amd.sharded.ShardedToyGraphBase with the values
+        replicated, in a group of ranks or emulating one)?  Then the forward is _forward_key_shard."""
+        return (getattr(tgb, "values_replicated", False) and hasattr(tgb, "retrieve_reduced_rows")
+                and (tgb.collective or tgb.emulate_world > 1))
 
     def _side_stream(self, device):
         st = getattr(self, "_side", None)
@@ -140,6 +135,22 @@ class RAGraph(nn.Module):
             st = torch.cuda.Stream(device=device)
             self._side = st
         return st
+
+    def _fork(self, fn, device):
+        """Enqueue fn() -- it returns one tensor -- on the model's side stream, behind what the current stream holds so far.
+        Returns join(): the current stream waits for the side stream and takes the tensor over (record_stream: the caching
+        allocator must not hand its memory to the side stream's next allocation while this stream still reads it)."""
+        main = torch.cuda.current_stream()
+        side = self._side_stream(device)
+        side.wait_stream(main)
+        with torch.cuda.stream(side):
+            out = fn()
+
+        def join():
+            main.wait_stream(side)
+            out.record_stream(main)
+            return out
+        return join
 
     def _fuse_decode(self, query_embeddings, rag_embedding, rag_label):
         """RAGraph.py:53-57: prompt fusion -> task decoder -> label mix.  An inference forward of a small batch (Cora,
@@ -174,16 +185,10 @@ class RAGraph(nn.Module):
         q = self.pretrain_model.inference_rows(features, g, qlo, qhi)   # my queries, main stream
         if q is None:
             return None
-        main = torch.cuda.current_stream()
-        side = self._side_stream(x.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            emb = self.pretrain_model.inference(features, g)
-            query_embeddings = Propagation.aggregate_k_hop_features(g, emb, self.query_graph_hop, rows=(qlo, qhi))
+        join = self._fork(lambda: Propagation.aggregate_k_hop_features(g, self.pretrain_model.inference(features, g),
+                                                                       self.query_graph_hop, rows=(qlo, qhi)), x.device)
         rag_embedding, rag_label, _ = tgb.retrieve_reduced(q)
-        main.wait_stream(side)
-        query_embeddings.record_stream(main)
-        return qs.gather_rows(self._fuse_decode(query_embeddings, rag_embedding, rag_label), n)
+        return qs.gather_rows(self._fuse_decode(join(), rag_embedding, rag_label), n)
 
     def _forward_query_shard(self, queries, emb, g):
         """Multi-GPU inference with a replicated bank: the cheap graph part runs on every rank, the retrieval and the
@@ -200,69 +205,30 @@ class RAGraph(nn.Module):
 
 
     def _forward_key_shard(self, queries, emb, g):
-        """Multi-GPU inference with a row-sharded KEY bank (ragraph_amd.sharded.ShardedToyGraphBase, values replicated):
-        every rank filters ALL queries against its shard; everything behind that is per query and runs on the rank's
-        slice of the nodes only -- merge of the per-shard lists (one all_to_all), value / label gather, the last
-        propagation hop, fusion + decoder -- and one all_gather of the [n, C] outputs completes the step.  Row for row
-        the arithmetic of forward()."""
-        tgb = self.toy_graph_base
-        n = queries.shape[0]
-        lo, hi = tgb.tail_bounds(n)
-        side = None
-        if self.finetune and queries.is_cuda and n >= self.OVERLAP_MIN_NODES:  # (see forward(): propagation on a side stream)
-            main = torch.cuda.current_stream()
-            side = self._side_stream(queries.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                query_embeddings = Propagation.aggregate_k_hop_features(g, emb, self.query_graph_hop, rows=(lo, hi))
-        # (the filtered call may run under the group's speculative first bound: its proof -- the merged k-th best of every row
-        # against the prior, pooled over the ranks -- is read AFTER the rest of the tail has been enqueued, just before the
-        # output leaves; a miss anywhere repeats the retrieval without the prior on every rank alike)
-        rag_embedding, rag_label, _ = tgb.retrieve_reduced_rows(queries, defer_verify=True)
-        if side is not None:
-            main.wait_stream(side)
-            query_embeddings.record_stream(main)
-        elif self.finetune:
-            query_embeddings = Propagation.aggregate_k_hop_features(g, emb, self.query_graph_hop, rows=(lo, hi))
-        out = self._fuse_decode(query_embeddings, rag_embedding, rag_label) if self.finetune else rag_label
-        if not tgb.confirm():
-            rag_embedding, rag_label, _ = tgb.retrieve_reduced_rows(queries)
-            out = self._fuse_decode(query_embeddings, rag_embedding, rag_label) if self.finetune else rag_label
-        return tgb.gather_output_rows(out, n)
-
-
-    def _forward_hybrid(self, queries, emb, g):
-        """Multi-GPU inference on Q query groups x S key shards (ragraph_amd.sharded.HybridLayout): `query_shard` splits the
-        batch over the query groups, `toy_graph_base` is the row-sharded bank of this rank's key group.  A rank filters its
-        group's slice of the queries against its key shard (exchanges with the S - 1 partners of its group only), finishes
-        its share of those rows -- merge, gathers, last hop, decoder -- and two all_gathers of [., C] outputs (key group,
-        query axis) put the whole result on every rank.  Row for row the arithmetic of forward()."""
+        """Multi-GPU inference with a row-sharded KEY bank (ragraph_amd.sharded.ShardedToyGraphBase, values replicated), on
+        Q query groups x S key shards (ragraph_amd.sharded.HybridLayout): `query_shard` splits the batch over the query groups
+        (None: one group, pure key sharding), `toy_graph_base` is the bank of this rank's key group.  A rank filters its
+        group's slice of the queries against its key shard (exchanges with the S - 1 partners of its group only); everything
+        behind that is per query and runs on the rank's share of those rows only -- merge of the per-shard lists (one
+        all_to_all), value / label gather, the last propagation hop, fusion + decoder -- and the all_gathers of the [., C]
+        outputs (key group, then query axis) put the whole result on every rank.  Row for row the arithmetic of forward()."""
         from .sharded import HybridLayout as H
 
         qs, tgb = self.query_shard, self.toy_graph_base
         n = queries.shape[0]
-        qlo, qhi, lo, hi = H.rows(qs, tgb, n)
-        rows = (qlo + lo, qlo + hi)
-        side = None
+        qlo, _, lo, hi = H.rows(qs, tgb, n)
+
+        def hops():
+            return Propagation.aggregate_k_hop_features(g, emb, self.query_graph_hop, rows=(qlo + lo, qlo + hi))
+
         if self.finetune and queries.is_cuda and n >= self.OVERLAP_MIN_NODES:  # (see forward(): propagation on a side stream)
-            main = torch.cuda.current_stream()
-            side = self._side_stream(queries.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                query_embeddings = Propagation.aggregate_k_hop_features(g, emb, self.query_graph_hop, rows=rows)
-        # (speculative first bound: decided, proven and withdrawn inside the KEY group -- see _forward_key_shard; the verdict is
-        # read before any collective of the query axis, so the query groups never disagree on how many of those run)
-        rag_embedding, rag_label, _ = H.retrieve_reduced_rows(qs, tgb, queries, defer_verify=True)
-        if side is not None:
-            main.wait_stream(side)
-            query_embeddings.record_stream(main)
-        elif self.finetune:
-            query_embeddings = Propagation.aggregate_k_hop_features(g, emb, self.query_graph_hop, rows=rows)
-        out = self._fuse_decode(query_embeddings, rag_embedding, rag_label) if self.finetune else rag_label
-        if not tgb.confirm():
-            rag_embedding, rag_label, _ = H.retrieve_reduced_rows(qs, tgb, queries)
-            out = self._fuse_decode(query_embeddings, rag_embedding, rag_label) if self.finetune else rag_label
-        return H.gather_output_rows(qs, tgb, out, n)
+            hops = self._fork(hops, queries.device)
+        hops = functools.cache(hops)   # (joined or computed behind the first retrieval; a repeat after a missed prior reuses them)
+
+        def tail(rag_embedding, rag_label):
+            return self._fuse_decode(hops(), rag_embedding, rag_label) if self.finetune else rag_label
+
+        return H.gather_output_rows(qs, tgb, H.retrieve_rows_with_tail(qs, tgb, queries, tail), n)
 
 
 class RAGraphGraph(RAGraph):

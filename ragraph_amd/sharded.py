@@ -185,24 +185,40 @@ class HybridLayout:
     def query_shard(self) -> "QueryShard":
         return QueryShard(self.query_group, force_collectives=True)
 
+    # The entry points for (query shard, bank of my key group).  qs = None is the layout with ONE query group: pure key sharding.
     @staticmethod
     def rows(qs: "QueryShard", tgb: "ShardedToyGraphBase", B: int):
         """(qlo, qhi, lo, hi): my query group answers rows [qlo, qhi) of the batch, and within the group I finish rows
         [qlo + lo, qlo + hi)."""
-        qlo, qhi = qs.bounds(B)
+        qlo, qhi = (0, B) if qs is None else qs.bounds(B)
         lo, hi = tgb.tail_bounds(qhi - qlo)
         return qlo, qhi, lo, hi
+
+    @staticmethod
+    def _group_queries(qs, search_keys):
+        if qs is None:
+            return search_keys
+        qlo, qhi = qs.bounds(search_keys.shape[0])
+        return search_keys[qlo:qhi].contiguous()
 
     @staticmethod
     def retrieve_reduced_rows(qs: "QueryShard", tgb: "ShardedToyGraphBase", search_keys, k=None, defer_verify: bool = False):
         """(sum_k V[idx], mean_k L[idx], idx) of MY rows of the batch: my group's slice of the queries against the group's
         key shards (exchanges and the all_to_all stay inside the key group)."""
-        qlo, qhi = qs.bounds(search_keys.shape[0])
-        return tgb.retrieve_reduced_rows(search_keys[qlo:qhi].contiguous(), k, defer_verify=defer_verify)
+        return tgb.retrieve_reduced_rows(HybridLayout._group_queries(qs, search_keys), k, defer_verify=defer_verify)
+
+    @staticmethod
+    def retrieve_rows_with_tail(qs: "QueryShard", tgb: "ShardedToyGraphBase", search_keys, tail, k=None):
+        """tail(sum_k V[idx], mean_k L[idx]) of MY rows of the batch, proven (ShardedToyGraphBase.retrieve_rows_with_tail: the
+        speculative first bound is decided, proven and withdrawn inside the KEY group, and the verdict is read before any
+        collective of the query axis, so the query groups never disagree on how many of those run)."""
+        return tgb.retrieve_rows_with_tail(HybridLayout._group_queries(qs, search_keys), tail, k)
 
     @staticmethod
     def gather_output_rows(qs: "QueryShard", tgb: "ShardedToyGraphBase", local: torch.Tensor, B: int) -> torch.Tensor:
         """[hi - lo, C] per rank -> [B, C] on every rank: the key group's rows first, then the query groups' slices."""
+        if qs is None:
+            return tgb.gather_output_rows(local, B)
         qlo, qhi = qs.bounds(B)
         return qs.gather_rows(tgb.gather_output_rows(local, qhi - qlo), B)
 
@@ -307,22 +323,22 @@ class ShardedToyGraphBase:
         from .kernels_index import KeyIndex  # torch-only helper: copies for the faster kernels, made on first use
         self._index = KeyIndex(self.keys_normalized, ops)
         self.emulate_world = int(emulate_world)
+        self.n_shards = self.emulate_world if self.emulate_world > 1 else self.world   # the shard count of the exchanges
+        self.exchanges = self.collective or self.emulate_world > 1                     # does this bank exchange at all?
         self._out_shard = None
         self.exchange_count = {}   # phase -> how many exchanges of that phase this rank has taken part in (diagnostic)
         self.prior = GroupPrior()  # the speculative first bound: one decision per call for the whole group
-        self._pending = None       # (pinned words, event, k, speculative) of a call whose verification was deferred
+        self._pending = None       # (pinned words, event, k, speculative) of a call whose verdict confirm() has not read yet
         self.reruns = 0            # calls repeated without the prior because a query missed it (diagnostic)
-        self._suppress = False     # the next call runs without a prior (it repeats a call that missed)
-        self._verify_scores = None
 
         def exchange_fn(phase, theta, scores):
             return self._exchange(phase, theta, scores)
 
-        exchange_fn.n_shards = self.emulate_world if self.emulate_world > 1 else self.world
+        exchange_fn.n_shards = self.n_shards
         self._exchange_fn = exchange_fn
         # rows this shard SEARCHES: its unique rows when KeyIndex collapses exact duplicates (the reference's bank recipe stores
         # most rows many times over; every shard judges its own rows) -- plan_n is the largest of those over the ranks
-        n_local = self._index.search_rows(min_unique=64) if hasattr(self._index, "search_rows") else int(keys.shape[0])
+        n_local = self._index.search_rows(min_unique=64)
         if plan_n:
             self.plan_n = max(int(plan_n), n_local) if n_local != int(keys.shape[0]) else int(plan_n)
         elif self.collective:
@@ -341,49 +357,67 @@ class ShardedToyGraphBase:
         the global k-th best (k-th of a subset): one all_gather of [B, m] scores, 4 m B per query and rank, + a k-th
         selection over [B, G m] (theta_sharpen).  Because phase 0 pools the shards' samples, each shard scans only 1 / G
         of the prefix (n_shards below)."""
-        G = self.emulate_world if self.emulate_world > 1 else self.world
-        if G <= 1 and not self.collective:
+        if not self.exchanges:
             return
+        G = self.n_shards
         self.exchange_count[phase] = self.exchange_count.get(phase, 0) + 1
         _beat(f"exchange phase {phase} (#{self.exchange_count[phase]})")
         k = scores.shape[1]
         m = min(k, 2 * (-(-k // G)))
         while G * m > 64 and m > -(-k // G):
             m -= 1
-        local = scores[:, :m].contiguous()
-        B = local.shape[0]
-        if self.emulate_world > 1:
-            gathered = local.unsqueeze(0).expand(G, B, m).contiguous()
+        self.ops.theta_sharpen(self._gather_shards(scores[:, :m].contiguous()), theta, k)
+
+    def _gather_shards(self, t, rows=None):
+        """[B, m] of this shard -> [G, n, m] (shard-major): every shard's rows of ALL queries on every rank (rows None: one
+        all_gather), or of MY rows (lo, hi) of the batch (one all_to_all: a rank receives its rows from every shard)."""
+        G, (B, m) = self.n_shards, t.shape
+        lo, hi = rows or (0, B)
+        if self.emulate_world > 1:   # (timing only: this shard's numbers stand in for the other shards')
+            return t[lo:hi].unsqueeze(0).expand(G, hi - lo, m).contiguous()
+        out = torch.empty((G * (hi - lo), m), dtype=t.dtype, device=t.device)
+        if rows is None:
+            all_gather_into(out, t, self.group)
         else:
-            gathered = torch.empty((G, B, m), dtype=local.dtype, device=local.device)
-            all_gather_into(gathered.view(G * B, m), local, self.group)
-        self.ops.theta_sharpen(gathered, theta, k)
+            send = [b - a for a, b in (shard_bounds(B, G, r) for r in range(G))]   # rows of my lists that go to rank r
+            all_to_all_single(out, t, [hi - lo] * G, send, self.group)
+        return out.view(G, hi - lo, m)
+
+    def _merge(self, s, i, rows=None):
+        """This shard's lists [B, k] -> (scores, idx, merged scores) of `rows` of the batch (_gather_shards): the group's lists
+        in the canonical order, and the scores on which the verdict on a prior is taken.  Shards that cannot hold k winners of a
+        query pad with sentinels that lose every comparison (-inf, INT64_MAX)."""
+        ms, mi = self.ops.topk_merge(self._gather_shards(s.contiguous(), rows), self._gather_shards(i.contiguous(), rows))
+        if self.emulate_world > 1:
+            # (timing only: the merge launch of a real rank, whose verdict is taken on what it returns -- a shard's own list
+            # under the pooled bound is far shorter than k --; the rows handed out are this shard's)
+            lo, hi = rows or (0, s.shape[0])
+            return s[lo:hi].contiguous(), i[lo:hi].contiguous(), ms
+        return ms, mi, ms
 
     # ---- the speculative first bound of a sharded call: chosen, proven and withdrawn by the whole group ------------------
+    @property
+    def _stats_index(self):
+        """The index whose statistics are read: the one the kernels stream (KeyIndex.search_index)."""
+        return self._index.search_index
+
     def _choose_prior(self, B: int, k: int):
         """The prior of THIS call (None: a bound pass), the same on every rank: GroupPrior's state is fed pooled numbers
         only, and whether the shape speculates at all comes from the shared plan."""
-        G = self.emulate_world if self.emulate_world > 1 else self.world
-        spec = getattr(self._index.search_index if hasattr(self._index, "search_index") else self._index, "sharded_speculates", None)
-        if self._suppress:          # (the repeat of a call whose prior a query missed: decided by confirm() on every rank alike)
-            self._suppress = False
-            return None
-        if spec is None or not spec(B, k, self.plan_n, G):
+        if not self._stats_index.sharded_speculates(B, k, self.plan_n, self.n_shards):
             return None
         return self.prior.prior_for(B, k)
 
-    def _post_verify(self, merged_s, k: int, prior, defer: bool) -> bool:
+    def _post_verify(self, merged_s, k: int, prior) -> None:
         """Behind the merge: this rank's rows' merged k-th best scores against the prior (a row is proven iff it reaches the
         prior; an all-zero query -- every score +0 -- is answered by index order and needs no proof), the smallest / largest of
         them, this shard's candidates per query and overflowed lists; ONE all_reduce MAX of five floats makes them the group's.
-        The words travel to a pinned buffer behind an event: confirm() reads them (at once unless `defer`)."""
+        The words travel to a pinned buffer behind an event: confirm() reads them."""
         speculative = prior is not None
-        if self._verify_scores is not None:   # (emulation: see _topk_rows_once)
-            merged_s, self._verify_scores = self._verify_scores, None
-        ix = self._index.search_index if hasattr(self._index, "search_index") else self._index
+        ix = self._stats_index
         native = getattr(self.ops, "verify_merged_prior", None)
         if native is not None and merged_s.is_cuda:   # one launch (csrc/topk_filter.hip: verify_merged_prior_kernel)
-            st, ov = getattr(ix, "last_stats", None), getattr(ix, "last_over", None)
+            st, ov = ix.last_stats, ix.last_over
             words = native(merged_s, prior, st if torch.is_tensor(st) else None, ov if torch.is_tensor(ov) else None)
         else:                                          # the same five numbers with torch ops (the CPU tests' oracle shim)
             kth, top = merged_s[:, k - 1], merged_s[:, 0]
@@ -407,19 +441,16 @@ class ShardedToyGraphBase:
             self._pending = (self._host_words, self._event, k, speculative)
         else:
             self._pending = (words, None, k, speculative)
-        return True if defer else self.confirm()
 
     def _cand_per_query(self, device):
-        ix = self._index.search_index if hasattr(self._index, "search_index") else self._index
-        st = getattr(ix, "last_stats", None)
+        st = self._stats_index.last_stats
         if st is None or not torch.is_tensor(st) or st.numel() < 8:
             return torch.tensor(-1.0, device=device)
         w = st[:8].to(torch.float32)
         return (w[2:5] / w[5:8].clamp(min=1.0)).sum()
 
     def _lists_over(self, device):
-        ix = self._index.search_index if hasattr(self._index, "search_index") else self._index
-        ov = getattr(ix, "last_over", None)
+        ov = self._stats_index.last_over
         if ov is None or not torch.is_tensor(ov):
             return torch.tensor(0.0, device=device)
         return ov.reshape(-1)[0].to(device=device, dtype=torch.float32)
@@ -427,7 +458,8 @@ class ShardedToyGraphBase:
     def confirm(self) -> bool:
         """The pooled verdict on the last sharded call: True = its result stands.  False = a query's merged k-th best fell
         below the speculative prior somewhere in the group: EVERY rank sees the same words, withdraws the prior and repeats
-        the call (the caller does: topk / topk_rows themselves unless asked to defer)."""
+        the call with no_prior=True (topk / topk_rows / retrieve_rows_with_tail do that themselves; a caller that asked
+        topk_rows to defer the verdict must)."""
         p = self._pending
         if p is None:
             return True
@@ -440,55 +472,54 @@ class ShardedToyGraphBase:
         ok = self.prior.record(p[2], p[3], int(w[0]), -w[1], w[2], w[3], int(w[4]))
         if not ok:
             self.reruns += 1
-            self._suppress = True
         return ok
 
-    @staticmethod
-    def _check_k(k: int) -> None:
-        """The sharded merge (exchanges, topk_merge of the gathered lists) is written for the fused kernels' lists.  k is the
-        same on every rank, so every rank raises here, before any collective."""
+    def _topk(self, search_keys, k, own_rows: bool, defer: bool = False, no_prior: bool = False):
+        """THE sharded call: the group's canonical top-k of all queries on every rank, or (own_rows) of this rank's rows of the
+        batch.  Where the shards exchange bounds it may run under the group's speculative first bound: choose the prior, run
+        once, prove the merged rows; on a miss run once more with a bound pass (withdrawn on every rank alike) and prove that.
+        defer: the first verdict is left to the caller's confirm().  no_prior: this call repeats one that missed."""
+        if self._pending is not None:
+            raise RagraphNativeError("ShardedToyGraphBase: the deferred verdict on the previous sharded call was never read -- "
+                                     "its rows are unproven; call confirm() (and repeat the call with no_prior=True when it "
+                                     "returns False) before the next call, or use retrieve_rows_with_tail")
+        k = self.retrieve_num if k is None else k
+        # The sharded merge (exchanges, topk_merge of the gathered lists) is written for the fused kernels' lists.  k is the
+        # same on every rank, so every rank raises here, before any collective.
         if k > TOPK_MAX:
             raise RagraphNativeError(f"ShardedToyGraphBase: k={k} exceeds the sharded top-k limit of {TOPK_MAX} "
                                      "(TOPK_MAX); larger k needs an unsharded ToyGraphBase")
+        q = search_keys.reshape(1, -1) if search_keys.dim() == 1 else search_keys
+        B = q.shape[0]
+        mine = self.tail_bounds(B) if own_rows else None
+        kl = min(k, self.keys_normalized.shape[0])
+        if not self.exchanges or kl < k:
+            # no exchange, nothing to prove: the shard's exact list (a shard smaller than k pads with sentinels that lose every
+            # comparison), merged over ALL rows where there is a group
+            s, i = self._index.topk(q, kl, idx_base=self.idx_base, exchange=None, plan_n=self.plan_n, prior=None)
+            if kl < k:
+                pad_s = torch.full((B, k - kl), float("-inf"), dtype=s.dtype, device=s.device)
+                pad_i = torch.full((B, k - kl), torch.iinfo(torch.int64).max, dtype=i.dtype, device=i.device)
+                s, i = torch.cat([s, pad_s], 1), torch.cat([i, pad_i], 1)
+            if self.exchanges:
+                s, i, _ = self._merge(s, i)
+            return (s[mine[0]:mine[1]].contiguous(), i[mine[0]:mine[1]].contiguous()) if own_rows else (s, i)
+
+        def once(prior):
+            s, i = self._index.topk(q, k, idx_base=self.idx_base, exchange=self._exchange_fn, plan_n=self.plan_n, prior=prior)
+            s, i, merged = self._merge(s, i, mine)
+            self._post_verify(merged, k, prior)
+            return s, i
+
+        out = once(None if no_prior else self._choose_prior(B, k))
+        if not defer and not self.confirm():
+            out = once(None)
+            self.confirm()
+        return out
 
     def topk(self, search_keys, k=None):
         """Global canonical top-k: (scores [B,k], idx [B,k]) identical on every rank."""
-        k = self.retrieve_num if k is None else k
-        self._check_k(k)
-        q = search_keys.reshape(1, -1) if search_keys.dim() == 1 else search_keys
-        n_local = self.keys_normalized.shape[0]
-        kl = min(k, n_local)
-        sharded = self.collective or self.emulate_world > 1
-        exch = self._exchange_fn if sharded and kl == k else None
-        prior = self._choose_prior(q.shape[0], k) if exch is not None else None
-        s, i = self._topk_all(q, k, kl, exch, prior)
-        if exch is not None and not self._post_verify(s, k, prior, defer=False):
-            self._suppress = False
-            s, i = self._topk_all(q, k, kl, exch, None)   # (withdrawn on every rank alike: a bound pass)
-            self._post_verify(s, k, None, defer=False)
-        return s, i
-
-    def _topk_all(self, q, k, kl, exch, prior):
-        sharded = self.collective or self.emulate_world > 1
-        s, i = self._index.topk(q, kl, idx_base=self.idx_base, exchange=exch, plan_n=self.plan_n, prior=prior)
-        if kl < k:  # a shard smaller than k: pad with sentinels that lose every comparison
-            pad_s = torch.full((q.shape[0], k - kl), float("-inf"), dtype=s.dtype, device=s.device)
-            pad_i = torch.full((q.shape[0], k - kl), torch.iinfo(torch.int64).max, dtype=i.dtype, device=i.device)
-            s, i = torch.cat([s, pad_s], 1), torch.cat([i, pad_i], 1)
-        if self.emulate_world > 1:  # (timing only) the merge launch a real rank would run over the G gathered lists
-            G = self.emulate_world
-            self._verify_scores, _ = self.ops.topk_merge(s.unsqueeze(0).expand(G, *s.shape).contiguous(),
-                                                         i.unsqueeze(0).expand(G, *i.shape).contiguous())
-            return s, i
-        if not self.collective:
-            return s, i
-        # shards that cannot hold k winners of a query pad with sentinels that lose every comparison (-inf, INT64_MAX)
-        B = s.shape[0]
-        gs = torch.empty((self.world * B, k), dtype=s.dtype, device=s.device)   # rank-major concatenation
-        gi = torch.empty((self.world * B, k), dtype=i.dtype, device=i.device)
-        all_gather_into(gs, s.contiguous(), self.group)
-        all_gather_into(gi, i.contiguous(), self.group)
-        return self.ops.topk_merge(gs.view(self.world, B, k), gi.view(self.world, B, k))
+        return self._topk(search_keys, k, own_rows=False)
 
     # ---- key-sharded bank, query-sharded tail -----------------------------------------------------------------------
     # Everything behind the per-shard filter is per query: merge, value / label gather, fusion, decoder.  With the
@@ -497,59 +528,39 @@ class ShardedToyGraphBase:
     # B k 12 (G - 1)), the merge, the gathers and the decoder run on B / G rows, and one all_gather of the [B, C] outputs
     # (RAGraph.forward) completes the step.  Same bits as the replicated tail: every step is per row.
     def tail_bounds(self, B: int):
-        G = self.emulate_world if self.emulate_world > 1 else self.world
-        return shard_bounds(B, G, 0 if self.emulate_world > 1 else self.rank)
+        return shard_bounds(B, self.n_shards, 0 if self.emulate_world > 1 else self.rank)
 
-    def topk_rows(self, search_keys, k=None, defer_verify: bool = False):
+    def topk_rows(self, search_keys, k=None, defer_verify: bool = False, no_prior: bool = False):
         """Global canonical top-k of THIS RANK'S rows of the batch: (scores, idx) [hi - lo, k], (lo, hi) = tail_bounds.
         defer_verify: the caller enqueues more work first and calls confirm() itself before it hands out anything -- when that
-        returns False it repeats this call (RAGraph._forward_key_shard / _forward_hybrid)."""
-        k = self.retrieve_num if k is None else k
-        self._check_k(k)
-        q = search_keys.reshape(1, -1) if search_keys.dim() == 1 else search_keys
-        B = q.shape[0]
-        lo, hi = self.tail_bounds(B)
-        n_local = self.keys_normalized.shape[0]
-        sharded = self.collective or self.emulate_world > 1
-        if not sharded or min(k, n_local) < k:
-            s, i = self.topk(q, k)
-            return s[lo:hi].contiguous(), i[lo:hi].contiguous()
-        prior = self._choose_prior(B, k)
-        ms, mi = self._topk_rows_once(q, k, lo, hi, prior)
-        if not self._post_verify(ms, k, prior, defer=defer_verify):
-            self._suppress = False
-            ms, mi = self._topk_rows_once(q, k, lo, hi, None)   # (withdrawn on every rank alike: a bound pass)
-            self._post_verify(ms, k, None, defer=False)
-        return ms, mi
+        returns False it repeats this call with no_prior=True (retrieve_rows_with_tail is that protocol; the next sharded call
+        raises while the verdict is unread)."""
+        return self._topk(search_keys, k, own_rows=True, defer=defer_verify, no_prior=no_prior)
 
-    def _topk_rows_once(self, q, k, lo, hi, prior):
-        B = q.shape[0]
-        s, i = self._index.topk(q, k, idx_base=self.idx_base, exchange=self._exchange_fn, plan_n=self.plan_n, prior=prior)
-        if self.emulate_world > 1:  # (timing only) the merge a real rank runs over the G lists of its rows
-            G = self.emulate_world
-            ss, ii = s[lo:hi], i[lo:hi]
-            # (the verdict on the prior is taken on what the merge returns, as on a real rank: G copies of this shard's list
-            # stand in for the other shards' -- a shard's own list under the pooled bound is far shorter than k)
-            self._verify_scores, _ = self.ops.topk_merge(ss.unsqueeze(0).expand(G, *ss.shape).contiguous(),
-                                                         ii.unsqueeze(0).expand(G, *ii.shape).contiguous())
-            return ss.contiguous(), ii.contiguous()
-        G = self.world
-        bounds = [shard_bounds(B, G, r) for r in range(G)]
-        send = [b - a for a, b in bounds]                    # rows of my lists that go to rank r (its slice of the batch)
-        recv = [hi - lo] * G                                 # every shard sends me its lists for my rows
-        gs = torch.empty((G * (hi - lo), k), dtype=s.dtype, device=s.device)   # shard-major
-        gi = torch.empty((G * (hi - lo), k), dtype=i.dtype, device=i.device)
-        all_to_all_single(gs, s.contiguous(), recv, send, self.group)
-        all_to_all_single(gi, i.contiguous(), recv, send, self.group)
-        return self.ops.topk_merge(gs.view(G, hi - lo, k), gi.view(G, hi - lo, k))
-
-    def retrieve_reduced_rows(self, search_keys, k=None, defer_verify: bool = False):
+    def retrieve_reduced_rows(self, search_keys, k=None, defer_verify: bool = False, no_prior: bool = False):
         """(sum_k V[idx], mean_k L[idx], idx) for this rank's rows of the batch (values replicated)."""
         if not self.values_replicated:
             raise ValueError("retrieve_reduced_rows: needs the values / labels replicated on every rank")
-        _, idx = self.topk_rows(search_keys, k, defer_verify=defer_verify)
+        _, idx = self.topk_rows(search_keys, k, defer_verify=defer_verify, no_prior=no_prior)
         sum_v, mean_l = self.ops.gather_reduce(self.resource_values, self.resource_labels, idx)
         return sum_v, mean_l, idx
+
+    def retrieve_rows_with_tail(self, search_keys, tail, k=None):
+        """tail(sum_k V[idx], mean_k L[idx]) for this rank's rows of the batch -- `tail` maps the rank's retrieved rows to its
+        output rows (RAGraph: fusion + decoder).  The filtered call may run under the group's speculative first bound: its
+        proof -- the merged k-th best of every row against the prior, pooled over the ranks -- is read AFTER the tail has been
+        enqueued, just before the output leaves; a miss anywhere repeats retrieval and tail without the prior on every rank
+        alike.  What this returns is proven."""
+        sum_v, mean_l, _ = self.retrieve_reduced_rows(search_keys, k, defer_verify=True)
+        try:
+            out = tail(sum_v, mean_l)
+        except BaseException:
+            self._pending = None   # (no row leaves: nothing to prove)
+            raise
+        if not self.confirm():
+            sum_v, mean_l, _ = self.retrieve_reduced_rows(search_keys, k, no_prior=True)
+            out = tail(sum_v, mean_l)
+        return out
 
     def gather_output_rows(self, local: torch.Tensor, B: int) -> torch.Tensor:
         """[hi - lo, C] per rank -> [B, C] on every rank (QueryShard.gather_rows over this bank's group)."""

@@ -1,6 +1,6 @@
 """One rank of tests/test_gpu_two_rank.py::test_four_ranks_hybrid_layout: FOUR real processes on the real HIP library, as 2 query
 groups x 2 key shards (ragraph_amd.sharded.HybridLayout), all on cuda:0 under a gloo group (device tensors staged through the
-host).  Each rank builds the same seeded workload, computes the single-process forward, runs RAGraph._forward_hybrid and
+host).  Each rank builds the same seeded workload, computes the single-process forward, runs RAGraph._forward_key_shard (query_shard set) and
 reports whether the gathered [n, C] output equals the single-process one bit for bit.  Started by tests/conftest.py BEFORE the
 pytest process touches the GPU.   usage: hybrid_worker.py RANK WORLD PORT OUT"""
 import datetime
@@ -49,7 +49,7 @@ def main():
         model.toy_graph_base = tgb
         model.query_shard = layout.query_shard()
         with torch.no_grad():
-            got = model(feats, adj)                      # -> _forward_hybrid
+            got = model(feats, adj)                      # -> _forward_key_shard
         res["layout"] = layout.name
         res["q_s"] = [layout.q, layout.s]
         res["hybrid_forward_equal"] = bool(torch.equal(got, want))

@@ -477,3 +477,98 @@ def test_sharded_speculative_prior_world(tmp_path, world, S):
         assert not np.isnan(g["auto_prior"][0])
         assert list(g["low"]) == [1, 1, 0, 0]                                              # stands: one call, no phase 0
         assert list(g["one"]) == [2, 1, 1, 1] and list(g["high"]) == [2, 1, 1, 1]          # missed: repeated once, with a bound pass
+
+
+def _tail_worker(rank, world, port, S, N, D, B, k, out_dir):
+    """retrieve_rows_with_tail (the bank's defer / confirm / repeat protocol) under forced priors: far below every merged k-th
+    best, between the two lowest of this key group's rows, above all.  S = world: pure key sharding, no query shard."""
+    import datetime
+
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
+    try:
+        from ragraph_amd.sharded import HybridLayout, ShardedToyGraphBase
+
+        layout = HybridLayout(S)
+        rng = np.random.default_rng(5)
+        keys = cref.normalize_rows(rng.standard_normal((N, D), dtype=np.float32))
+        vals = torch.from_numpy(rng.standard_normal((N, D), dtype=np.float32))
+        labs = torch.from_numpy(np.eye(3, dtype=np.float32)[rng.integers(0, 3, N)])
+        lo, hi = layout.key_rows(N)
+        tgb = ShardedToyGraphBase(torch.from_numpy(keys[lo:hi]), vals, labs, lo, k, group=layout.key_group,
+                                  ops=FilteredOracleOps, values_replicated=True)
+        qs = layout.query_shard() if S < world else None
+        q = rng.standard_normal((B, D), dtype=np.float32)
+        rs, _ = cref.topk_cosine(q, keys, k)
+        kth = rs[:, k - 1]
+        qlo, qhi, rlo, rhi = HybridLayout.rows(qs, tgb, B)
+        group_kth = np.sort(kth[qlo:qhi])
+        out = {"rows": np.array([qlo + rlo, qlo + rhi])}
+        for tag, prior in (("low", float(kth.min()) - 0.05), ("one", float(0.5 * (group_kth[0] + group_kth[1]))),
+                           ("high", float(kth.max()) + 0.05)):
+            tgb.prior.forced = prior
+            tails = []
+
+            def tail(sum_v, mean_l):
+                tails.append(sum_v.shape[0])
+                return mean_l
+
+            before = (tgb.reruns, tgb.exchange_count.get(0, 0), FilteredOracleOps.spec_calls)
+            ml = HybridLayout.retrieve_rows_with_tail(qs, tgb, torch.from_numpy(q), tail)
+            out[tag + "_ml"] = HybridLayout.gather_output_rows(qs, tgb, ml, B).numpy()
+            out[tag + "_tails"] = np.array(tails)
+            out[tag] = np.array([tgb.reruns - before[0], tgb.exchange_count.get(0, 0) - before[1],
+                                 FilteredOracleOps.spec_calls - before[2]])
+        np.savez(os.path.join(out_dir, f"w{rank}.npz"), **out)
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world,S", [(2, 2), (4, 2)])
+def test_retrieve_rows_with_tail_world(tmp_path, world, S):
+    """The bank's retrieve-with-tail entry point (key shards at world 2, hybrid 2 x 2 at world 4): the gathered output is the
+    single-process rows bit for bit whatever the forced prior; the tail runs once where the prior stands and twice where a row
+    missed it, on every rank alike; repeats and phase-0 exchanges are the same on the ranks of a key group."""
+    N, D, B, k = 1501, 64, 48, 10
+    mp.spawn(_tail_worker, args=(world, _free_port(), S, N, D, B, k, str(tmp_path)), nprocs=world, join=True)
+    rng = np.random.default_rng(5)
+    keys = cref.normalize_rows(rng.standard_normal((N, D), dtype=np.float32))
+    vals = rng.standard_normal((N, D), dtype=np.float32)
+    labs = np.eye(3, dtype=np.float32)[rng.integers(0, 3, N)]
+    q = rng.standard_normal((B, D), dtype=np.float32)
+    _, ri = cref.topk_cosine(q, keys, k)
+    _, rml = cref.gather_reduce(vals, labs, ri)
+    got = [dict(np.load(tmp_path / f"w{r}.npz")) for r in range(world)]
+    for r, g in enumerate(got):
+        lo, hi = (int(x) for x in g["rows"])
+        partner = got[(r // S) * S + (r % S + 1) % S]
+        for tag, runs in (("low", 1), ("one", 2), ("high", 2)):
+            assert np.array_equal(g[tag + "_ml"], rml), (tag, r)
+            assert list(g[tag + "_tails"]) == [hi - lo] * runs, (tag, r)        # this rank's rows, once or twice
+            assert np.array_equal(g[tag], partner[tag]), (tag, r)                 # the key group acted as one
+            assert list(g[tag]) == [runs - 1, runs - 1, 1], (tag, r)             # repeats, phase-0 exchanges, speculative calls
+
+
+def test_unread_deferred_verdict_raises():
+    """topk_rows(defer_verify=True) hands out unproven rows: the next sharded call refuses to run until confirm() has read the
+    verdict (one process, an emulated rank of 2 over the oracle shim)."""
+    from ragraph_amd._native import RagraphNativeError
+    from ragraph_amd.sharded import ShardedToyGraphBase
+
+    N, D, B, k = 1501, 64, 23, 10
+    rng = np.random.default_rng(5)
+    keys = cref.normalize_rows(rng.standard_normal((N, D), dtype=np.float32))
+    vals = torch.from_numpy(rng.standard_normal((N, D), dtype=np.float32))
+    labs = torch.from_numpy(np.eye(3, dtype=np.float32)[rng.integers(0, 3, N)])
+    q = torch.from_numpy(rng.standard_normal((B, D), dtype=np.float32))
+    tgb = ShardedToyGraphBase(torch.from_numpy(keys), vals, labs, 0, k, ops=FilteredOracleOps, values_replicated=True,
+                              emulate_world=2)
+    s, i = tgb.topk_rows(q, defer_verify=True)
+    lo, hi = tgb.tail_bounds(B)
+    assert s.shape == (hi - lo, k)
+    for call in (lambda: tgb.topk_rows(q), lambda: tgb.topk(q), lambda: tgb.retrieve_reduced_rows(q, defer_verify=True)):
+        with pytest.raises(RagraphNativeError, match=r"confirm\(\)"):
+            call()
+    assert tgb.confirm() is True
+    s2, i2 = tgb.topk_rows(q)                     # the verdict read: the bank answers again
+    assert torch.equal(i2, i) and torch.equal(s2, s)

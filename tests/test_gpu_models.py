@@ -555,6 +555,67 @@ def test_key_sharded_forward_with_query_sharded_tail_one_rank_rccl(dev):
     assert torch.equal(got, want)
 
 
+def test_sharded_forwards_with_and_without_fork_one_rank_rccl(dev):
+    """Every sharded forward -- key-sharded, hybrid 1 x 1, query-sharded -- under ONE 1-rank RCCL group, with the side-stream
+    fork of the propagation off (the class threshold) and on (threshold lowered on the instance: 3000 nodes then fork in every
+    branch, the sliced encode of the query-sharded layout included): each of the six outputs is the plain forward bit for bit."""
+    import socket
+
+    import torch.distributed as dist
+
+    from ragraph_amd.data import synthetic_big_graph
+    from ragraph_amd.graph import CSRGraph
+    from ragraph_amd.preprompt import PrePrompt
+    from ragraph_amd.RAGraph import RAGraph
+    from ragraph_amd.sharded import HybridLayout, QueryShard, ShardedToyGraphBase
+
+    torch.manual_seed(3)
+    n, F, D, C, N, k = 3000, 32, 128, 3, 70000, 10
+    model = RAGraph(PrePrompt(F, D, "prelu", 1, 0.3).to(dev), None, F, C, D, device=dev).eval()
+    model.toy_graph_base.retrieve_num = k
+    keys = torch.nn.functional.normalize(torch.randn(N, D, device=dev), dim=-1)
+    vals = torch.randn(N, D, device=dev)
+    labs = torch.nn.functional.one_hot(torch.randint(0, C, (N,), device=dev), C).float()
+    model.toy_graph_base.add_resources(keys, vals, labs)
+    adj = CSRGraph.from_edge_index_sym_normalized(synthetic_big_graph(n, 6, seed=2, device=dev), n)
+    X = torch.randn(n, F, device=dev)
+    assert n < RAGraph.OVERLAP_MIN_NODES
+    with torch.no_grad():
+        want = model(X, adj)
+    with socket.socket() as sck:
+        sck.bind(("127.0.0.1", 0))
+        port = sck.getsockname()[1]
+    dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1)
+    try:
+        plain = model.toy_graph_base
+        layout = HybridLayout(1)
+        layouts = {
+            "key-sharded": (ShardedToyGraphBase(keys, vals, labs, 0, k, force_collectives=True, values_replicated=True), None),
+            "hybrid 1x1": (ShardedToyGraphBase(keys, vals, labs, 0, k, group=layout.key_group, force_collectives=True,
+                                               values_replicated=True), layout.query_shard()),
+            "query-sharded": (plain, QueryShard(force_collectives=True)),
+        }
+        forks = []
+        fork = model._fork
+        model._fork = lambda *a: (forks.append(1), fork(*a))[1]
+        got = {}
+        for name, (bank, qs) in layouts.items():
+            model.toy_graph_base, model.query_shard = bank, qs
+            for threshold in (None, 1024):
+                if threshold is not None:
+                    model.OVERLAP_MIN_NODES = threshold
+                del forks[:]
+                with torch.no_grad():
+                    got[name, threshold] = model(X, adj)
+                assert len(forks) == (threshold is not None), (name, threshold)
+                model.__dict__.pop("OVERLAP_MIN_NODES", None)
+        torch.cuda.synchronize()
+    finally:
+        dist.destroy_process_group()
+    for case, out in got.items():
+        assert torch.equal(out, want), case
+
+
 def test_bank_save_load_roundtrip(dev, tmp_path):
     from ragraph_amd.ragraph_utils import ToyGraphBase
 
