@@ -79,9 +79,18 @@ static void ring_timing_report(int, int) {}
 #ifndef RG_RING_FOLD   // (-DRG_RING_FOLD=0: the D = 64 int8 levels without the folded thresholds -- A/B builds)
 #define RG_RING_FOLD 1
 #endif
-template <int D, int QW, bool BOUND = false, bool I8 = false, bool SCORED = false, bool PIPE = false>
+// SKEW (int8 levels of six groups, one set of accumulators): the wave's groups are two SETS, A = groups 0-2 and B = groups 3-5,
+// each with its OWN wave-uniform hit decision.  A set's maxima and compares are issued between the OTHER set's MFMAs -- A's
+// while B's last two steps of the sub-tile run, B's under A's first step of the next sub-tile (into A's accumulators, free by
+// then) -- so at most three vector instructions sit between a set's last MFMA and the next MFMA, where the one decision over
+// all six groups left 17 (13 maxima, 4 compares) behind the sub-tile's last MFMA.  A set's candidate path runs at its own
+// decision, before its accumulators are written again.  Inside a stage only: the stage's last sub-tile decides both sets
+// behind its last MFMA.
+template <int D, int QW, bool BOUND = false, bool I8 = false, bool SCORED = false, bool PIPE = false, bool SKEW = false>
 __global__ void __launch_bounds__(512, 2) topk_filter_kernel(FilterParams p) {
   using C = FilterCfg<I8 ? D / 2 : D>;
+  static_assert(!SKEW || (I8 && !BOUND && !PIPE && QW == 96 && D != 64 && C::KSTEPS >= 4 && C::KSTEPS % 2 == 0),
+                "SKEW: int8 filter levels of six groups without the folded thresholds, whole pairs of steps per sub-tile");
   static_assert(!PIPE || (I8 && !BOUND && C::KSTEPS >= QW / 16 + 2), "PIPE: int8 filter levels, one step per query group + 2");
   static_assert(!(I8 && BOUND), "the bound pass runs on the bf16 copy");
   static_assert(I8 || !SCORED, "scored lists carry the int8 levels' integer sums");
@@ -421,6 +430,7 @@ __global__ void __launch_bounds__(512, 2) topk_filter_kernel(FilterParams p) {
       RG_FT(t1);
       // epilogue of sub-tile u: a[h][gq][r] = approximate score of key 16 h + 4 g + r of the sub-tile for query j of group gq
       using acc_t = typename std::conditional<I8, i32x4, f32x4>::type;
+      [[maybe_unused]] const int stage_key0_skew = (int)((p.stage_base + st0 + s) * C::STAGE_KEYS);
       auto pass_mask = [&](const acc_t (&a)[2][NG], int gq, [[maybe_unused]] int th_i8) {  // float scores against thr, integer sums against th_i8
         unsigned mk = 0;
         if constexpr (I8) {
@@ -451,10 +461,12 @@ __global__ void __launch_bounds__(512, 2) topk_filter_kernel(FilterParams p) {
       // instructions and every copy of it sits in the stage loop's instruction stream
       // (SCORED: the lane's largest sum and the class of the keys' granule ride in the entry's upper 24 bits as (I << 1) | class
       // -- |I| <= 127^2 * 256 < 2^22)
-      auto push_groups = [&](const unsigned (&km)[NG], const int (&mi)[NG], unsigned off, [[maybe_unused]] int cls_of) {
+      // (SKEW: set_g0 >= 0 pushes the one batch that starts at group set_g0 -- a set is a batch of three)
+      auto push_groups = [&](const unsigned (&km)[NG], const int (&mi)[NG], unsigned off, [[maybe_unused]] int cls_of, int set_g0 = -1) {
         constexpr int GB = NG < 4 ? NG : (NG % 4 == 0 ? 4 : 3);  // groups per check: at most 64 GB = 256 entries < CAND_BUF
 #pragma unroll
         for (int g0 = 0; g0 < NG; g0 += GB) {
+          if (set_g0 >= 0 && g0 != set_g0) continue;
           unsigned long long bm[GB];
           int tot = 0;
 #pragma unroll
@@ -602,6 +614,40 @@ __global__ void __launch_bounds__(512, 2) topk_filter_kernel(FilterParams p) {
         }
         phit = false;
       };
+      // SKEW: a group's maximum in two pieces -- the first half's four sums (complete one step before the sub-tile's last), then
+      // the second half's with the compare, whose lane mask stays in a scalar pair (smask) for the decision and the hit path
+      [[maybe_unused]] int smi[NG];
+      [[maybe_unused]] unsigned long long smask[NG];
+      [[maybe_unused]] auto skew_half0 = [&](const acc_t (&a)[2][NG], int gq) {
+        smi[gq] = max(max(max(as_bits(a[0][gq][0]), as_bits(a[0][gq][1])), as_bits(a[0][gq][2])), as_bits(a[0][gq][3]));
+        asm volatile("" : "+v"(smi[gq]));  // (stays beside its MFMA: hipcc would sink it to its use, behind the set's last MFMA)
+      };
+      [[maybe_unused]] auto skew_half1 = [&](const acc_t (&a)[2][NG], int gq) {
+        smi[gq] = max(max(smi[gq], as_bits(a[1][gq][0])), as_bits(a[1][gq][1]));
+        smi[gq] = max(max(smi[gq], as_bits(a[1][gq][2])), as_bits(a[1][gq][3]));
+        smask[gq] = __builtin_amdgcn_ballot_w64(smi[gq] >= thr_i[gq]);
+      };
+      // the candidate path of one set (groups g0 .. g0 + 2) of sub-tile u
+      [[maybe_unused]] auto skew_decide = [&](const acc_t (&a)[2][NG], int u, int g0) {
+        if ((smask[g0] | smask[g0 + 1] | smask[g0 + 2]) != 0ull) {
+          const int key_base = stage_key0_skew + 32 * u + 4 * g;
+          unsigned km[NG];
+#pragma unroll
+          for (int gq = 0; gq < NG; ++gq) {
+            km[gq] = 0;
+            if (gq >= g0 && gq < g0 + 3)
+              if (smask[gq] != 0ull) km[gq] = pass_mask(a, gq, thr_i[gq]);
+          }
+          if (stage_key0_skew + C::STAGE_KEYS > (int)p.N) {
+            unsigned vm = 0;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) vm |= (key_base + (r & 3) + 16 * (r >> 2) < (int)p.N) ? (1u << r) : 0u;
+#pragma unroll
+            for (int gq = 0; gq < NG; ++gq) km[gq] &= vm;
+          }
+          push_groups(km, smi, (unsigned)(key_base - key_org), cls_cur, g0);
+        }
+      };
       // ---- SUBS sub-tiles of 32 keys x QW queries, KSTEPS fragments each (k-step major: both 16-key halves of a step);
       // one A fragment feeds all NG query groups.
       // A step is only 64 cycles of MFMA, less than an LDS round trip, so the fragment reads run FOUR steps ahead of
@@ -626,9 +672,13 @@ __global__ void __launch_bounds__(512, 2) topk_filter_kernel(FilterParams p) {
       } else if constexpr (FOLD) {                                                                         \
         _Pragma("unroll") for (int gq = 0; gq < NG; ++gq)                                                  \
           acc[0][gq] = acc[1][gq] = __builtin_bit_cast(acc_t, ntq[gq]);                                    \
-      } else {                                                                                             \
-        _Pragma("unroll") for (int gq = 0; gq < NG; ++gq) acc[0][gq] = acc[1][gq] = acc_t{0, 0, 0, 0};     \
+      } else {  /* (SKEW: set B's after its epilogue, inside the step) */                                  \
+        _Pragma("unroll") for (int gq = 0; gq < (SKEW ? NG / 2 : NG); ++gq) acc[0][gq] = acc[1][gq] = acc_t{0, 0, 0, 0}; \
       }                                                                                                    \
+    }                                                                                                      \
+    if constexpr (SKEW && r_ == C::KSTEPS - 1) { /* (here, under the MFMAs in flight: behind the decision it would sit in front of the next MFMA) */ \
+      if (lead && lane == 0)                                                                               \
+        __hip_atomic_store(prog + wave, s * C::SUBS + u_ + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
     }                                                                                                      \
     if constexpr ((n_) + 3 < C::NSTEP) RG_FWAIT(3, n_);                                                     \
     else if constexpr ((n_) + 2 < C::NSTEP) RG_FWAIT(2, n_);                                                \
@@ -639,6 +689,33 @@ __global__ void __launch_bounds__(512, 2) topk_filter_kernel(FilterParams p) {
       _Pragma("unroll") for (int gq = 0; gq < NG; ++gq)                                                     \
         accp[set_][(n_) & 1][gq] = __builtin_bit_cast(acc_t, __builtin_amdgcn_mfma_i32_16x16x64_i8(         \
             a_, bqi[gq][((n_) >> 1) % C::KS32], __builtin_bit_cast(i32x4, accp[set_][(n_) & 1][gq]), 0, 0, 0)); \
+    } else if constexpr (I8 && SKEW) {                                                                     \
+      /* the order below IS the issue order on the pinned steps (sched_barrier(0) between the pieces): one MFMA, then the */ \
+      /* other set's two maxima instructions (+ compare): what fits beside an MFMA's 16 cycles                          */ \
+      const i32x4 a_ = __builtin_bit_cast(i32x4, fr[(n_)&3]);                                               \
+      constexpr bool last_ = r_ == C::KSTEPS - 1, prev_ = r_ == C::KSTEPS - 2, bepi_ = r_ == 0 && u_ > 0;    \
+      if constexpr (last_ || prev_ || bepi_) __builtin_amdgcn_sched_barrier(0);                             \
+      _Pragma("unroll") for (int gq = 0; gq < NG / 2; ++gq) {                                               \
+        acc[(n_) & 1][gq] = __builtin_bit_cast(acc_t, __builtin_amdgcn_mfma_i32_16x16x64_i8(                \
+            a_, bqi[gq][((n_) >> 1) % C::KS32], __builtin_bit_cast(i32x4, acc[(n_) & 1][gq]), 0, 0, 0));    \
+        if constexpr (last_) skew_half0(acc, NG / 2 + gq);                                                  \
+        if constexpr (bepi_) skew_half1(acc, NG / 2 + gq);                                                  \
+        if constexpr (last_ || bepi_) __builtin_amdgcn_sched_barrier(0);                                    \
+        else if (prev_ && gq == NG / 2 - 1) __builtin_amdgcn_sched_barrier(0);                              \
+      }                                                                                                    \
+      if constexpr (bepi_) {                                                                               \
+        skew_decide(acc, u_ - 1, NG / 2);                                                                  \
+      }                                                                                                    \
+      if constexpr (r_ == 0) {                                                                             \
+        _Pragma("unroll") for (int gq = NG / 2; gq < NG; ++gq) acc[0][gq] = acc[1][gq] = acc_t{0, 0, 0, 0}; \
+      }                                                                                                    \
+      _Pragma("unroll") for (int gq = NG / 2; gq < NG; ++gq) {                                              \
+        acc[(n_) & 1][gq] = __builtin_bit_cast(acc_t, __builtin_amdgcn_mfma_i32_16x16x64_i8(                \
+            a_, bqi[gq][((n_) >> 1) % C::KS32], __builtin_bit_cast(i32x4, acc[(n_) & 1][gq]), 0, 0, 0));    \
+        if constexpr (prev_) skew_half0(acc, gq - NG / 2);                                                  \
+        if constexpr (last_) skew_half1(acc, gq - NG / 2);                                                  \
+        if constexpr (last_ || prev_) __builtin_amdgcn_sched_barrier(0);                                    \
+      }                                                                                                    \
     } else if constexpr (I8) {                                                                             \
       const i32x4 a_ = __builtin_bit_cast(i32x4, fr[(n_)&3]);                                               \
       _Pragma("unroll") for (int gq = 0; gq < NG; ++gq)                                                     \
@@ -667,6 +744,12 @@ __global__ void __launch_bounds__(512, 2) topk_filter_kernel(FilterParams p) {
       if constexpr (r_ == C::KSTEPS - 1) {                                                                 \
         if (lead && lane == 0)                                                                             \
           __hip_atomic_store(prog + wave, s * C::SUBS + u_ + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
+      }                                                                                                    \
+    } else if constexpr (SKEW && r_ == C::KSTEPS - 1) {                                                    \
+      skew_decide(acc, u_, 0);                                                                             \
+      if constexpr (u_ == C::SUBS - 1) { /* the stage's last sub-tile: set B decides here, unskewed */      \
+        _Pragma("unroll") for (int gq = NG / 2; gq < NG; ++gq) skew_half1(acc, gq);                         \
+        skew_decide(acc, u_, NG / 2);                                                                      \
       }                                                                                                    \
     } else if constexpr (r_ == C::KSTEPS - 1) {                                                            \
       epilogue(u_, acc);                                                                                   \

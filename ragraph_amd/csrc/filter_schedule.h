@@ -45,6 +45,7 @@ struct FilterEnv {
   int i8;            // RAGRAPH_FILTER_I8 = n: the last n levels run on the int8 copy (0: none); -1: the rule
   int scored;        // RAGRAPH_FILTER_SCORED = 0 / 1: scored candidate lists off / on; -1: the rule
   int pipe;          // RAGRAPH_FILTER_PIPE (filter_pass_variant; default 1)
+  int skew;          // RAGRAPH_FILTER_SKEW (filter_pass_variant; default 1; 0: six groups with one decision per sub-tile)
   int partner_lead;  // RAGRAPH_FILTER_PARTNER_LEAD (0 = equal priorities, the hardware's age order; default 1)
   int i8_qw;         // RAGRAPH_FILTER_I8_QW: queries per wave of the int8 levels (0: the rule)
   int scored_shards;    // RAGRAPH_FILTER_SCORED_SHARDS: sharded banks of up to this many shards keep scored lists (default 2)
@@ -60,6 +61,7 @@ static FilterEnv filter_env() {
   static const int scored_shards = filter_env_int("RAGRAPH_FILTER_SCORED_SHARDS", 2);
   static const int spec_two_shards = filter_env_int("RAGRAPH_FILTER_SPEC_SHARDS_TWO_LEVELS", 2);
   return {filter_env_int("RAGRAPH_FILTER_I8", -1), filter_env_int("RAGRAPH_FILTER_SCORED", -1), filter_env_int("RAGRAPH_FILTER_PIPE", 1),
+          filter_env_int("RAGRAPH_FILTER_SKEW", 1),
           filter_env_int("RAGRAPH_FILTER_PARTNER_LEAD", 1), filter_env_int("RAGRAPH_FILTER_I8_QW", 0), scored_shards, spec_two_shards,
           filter_env_int("RAGRAPH_FILTER_TIGHT_LEVELS", 1)};
 }

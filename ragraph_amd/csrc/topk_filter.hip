@@ -484,7 +484,7 @@ static RingPlan ring_plan_cached(int64_t qtiles, int64_t NS, int CUS, int lb_min
 }
 
 // Ring-kernel launch shared by the filter levels and the bound pass (B > 256: the direct kernel takes smaller batches).
-template <int D, int QW, bool BOUND, bool I8 = false, bool SCORED = false, bool PIPE = false>
+template <int D, int QW, bool BOUND, bool I8 = false, bool SCORED = false, bool PIPE = false, bool SKEW = false>
 static int launch_ring(FilterParams p, int64_t B, int CUS, int prof_slot, hipStream_t st) {
   using C = FilterCfg<I8 ? D / 2 : D>;
   p.qtiles = cdiv(B, (int64_t)C::WAVES * QW);
@@ -501,12 +501,12 @@ static int launch_ring(FilterParams p, int64_t B, int CUS, int prof_slot, hipStr
   p.depth[0] = pl.depth[0];
   p.depth[1] = pl.depth[1];
   static DeviceOnce lds_once;  // per template instance and device (common.h)
-  if (hipError_t e = raise_dynamic_lds(lds_once, &topk_filter_kernel<D, QW, BOUND, I8, SCORED, PIPE>, (int)C::LDS_BYTES); e != hipSuccess) {
+  if (hipError_t e = raise_dynamic_lds(lds_once, &topk_filter_kernel<D, QW, BOUND, I8, SCORED, PIPE, SKEW>, (int)C::LDS_BYTES); e != hipSuccess) {
     set_error("topk_cosine_filtered: cannot raise dynamic LDS limit: %s", hipGetErrorString(e));
     return RAGRAPH_EDEVICE;
   }
   if (t_prof && prof_slot >= 0) (void)hipEventRecord(t_prof->ev[2 * prof_slot], st);
-  hipLaunchKernelGGL((topk_filter_kernel<D, QW, BOUND, I8, SCORED, PIPE>), dim3((unsigned)CUS), dim3(C::THREADS), C::LDS_BYTES, st, p);
+  hipLaunchKernelGGL((topk_filter_kernel<D, QW, BOUND, I8, SCORED, PIPE, SKEW>), dim3((unsigned)CUS), dim3(C::THREADS), C::LDS_BYTES, st, p);
   if (t_prof && prof_slot >= 0) (void)hipEventRecord(t_prof->ev[2 * prof_slot + 1], st);
   RG_CHECK_LAUNCH("topk_cosine_filtered(filter)");
   ring_stamps_report(BOUND, I8);
@@ -520,7 +520,7 @@ static int launch_ring(FilterParams p, int64_t B, int CUS, int prof_slot, hipStr
 struct PassVariant {
   bool direct;
   int qw;
-  bool bound, i8, scored, pipe;
+  bool bound, i8, scored, pipe, skew;
 };
 static PassVariant filter_pass_variant(int D, int64_t B, int64_t key0, int64_t key1, bool bound, bool int8, bool scored, int cus,
                                        const FilterEnv& env) {
@@ -562,11 +562,15 @@ static PassVariant filter_pass_variant(int D, int64_t B, int64_t key0, int64_t k
   // it only draws level (13.03 vs 13.03 - 13.13 ms: six groups in one set of accumulators stay).  RAGRAPH_FILTER_PIPE=0/2: A/B
   if (D == 256 && ((env.pipe == 1 && !long128 && !long96) || env.pipe == 2)) v.pipe = true;
   else v.qw = long128 ? 128 : (long96 ? 96 : 64);
+  // D = 256, six groups: the two sets' epilogues under each other's MFMAs (filter_ring.h, SKEW: 3 vector instructions between a
+  // set's last MFMA and the next MFMA instead of 17) -- 100 000 x 1M: the launch 16.30 -> 15.98 ms, the step 17.92 -> 17.61
+  // (three interleaved pairs, profiles/ring_group_skew.txt).  RAGRAPH_FILTER_SKEW=0: one decision per sub-tile -- A/B and tests
+  v.skew = D == 256 && !v.pipe && v.qw == 96 && env.skew != 0;
   return v;
 }
 
 // The ring kernel's instantiations: the bound pass and the bf16 levels at 64 queries per wave (D = 64: also 128), the int8
-// levels at 64 / 96 / 128 with plain or scored lists, and at D = 256 the pipelined form of 64.
+// levels at 64 / 96 / 128 with plain or scored lists, and at D = 256 the pipelined form of 64 and the skewed form of 96.
 template <int D>
 static int launch_ring_variant(const PassVariant& v, const FilterParams& p, int64_t B, int cus, int prof_slot, hipStream_t st) {
   RG_REQUIRE(!v.direct && (v.qw == 64 || (v.i8 ? !v.pipe && (v.qw == 96 || v.qw == 128) : D == 64 && !v.bound && v.qw == 128)) &&
@@ -578,10 +582,14 @@ static int launch_ring_variant(const PassVariant& v, const FilterParams& p, int6
       if (v.qw == 128) return launch_ring<D, 128, false>(p, B, cus, prof_slot, st);
     return launch_ring<D, 64, false>(p, B, cus, prof_slot, st);
   }
-  if constexpr (D == 256)
+  if constexpr (D == 256) {
     if (v.pipe)
       return v.scored ? launch_ring<D, 64, false, true, true, true>(p, B, cus, prof_slot, st)
                       : launch_ring<D, 64, false, true, false, true>(p, B, cus, prof_slot, st);
+    if (v.skew)
+      return v.scored ? launch_ring<D, 96, false, true, true, false, true>(p, B, cus, prof_slot, st)
+                      : launch_ring<D, 96, false, true, false, false, true>(p, B, cus, prof_slot, st);
+  }
 #define RG_RING_I8(QW_) \
   return v.scored ? launch_ring<D, QW_, false, true, true>(p, B, cus, prof_slot, st) : launch_ring<D, QW_, false, true>(p, B, cus, prof_slot, st)
   if (v.qw == 128) RG_RING_I8(128);
