@@ -364,6 +364,35 @@ int ragraph_filter_profile_levels(ragraph_filter_profile* p, float* ms_host, int
 int ragraph_topk_merge_f32(const float* scores, const int64_t* idx, int G, int64_t B, int k, float* out_scores,
                            int64_t* out_idx, void* stream);
 
+/* a1 + a2 CONTINUED over rows appended to a bank  -- the reference's bank only ever grows (ToyGraphBase.py:116-119 appends
+ * one resource graph at a time, finetune-rag.py:97 the validation set), and every copy, grouping and learnt bound of the
+ * faster paths belongs to the rows they were made from.  This entry takes the finished canonical list of a search over
+ * those rows (the SEED) and continues it exactly over a short TAIL of newer rows (ragraph_amd/csrc/topk_tail.hip):
+ *   Q        [B,D] raw queries, normalised inside exactly as ragraph_topk_cosine_f32 normalises them.
+ *   Kn_tail  [T,D] the tail's rows, already normalised by ragraph_normalize_rows_f32.  1 <= T <= RAGRAPH_TOPK_TAIL_MAX; T < k
+ *            is legal (the seed fills the rest of the list).
+ *   seed_scores / seed_idx [B,k]  a canonical list (score descending, index ascending) over OTHER keys, every index below
+ *            idx_base_tail; its end may be padded with -inf / INT64_MAX as a shard's list is.
+ *   out_scores / out_idx [B,k]  the canonical top-k of the seed's entries together with the tail's keys; tail key j carries
+ *            index idx_base_tail + j.  out must not alias seed.
+ *   A tail key's score is the fmaf chain of ragraph_topk_cosine_f32 (natural column order from +0): the bits that entry
+ *   returns for the key, so out has the bits of one search over all rows.  A tail key that ties the seed's k-th entry has the
+ *   higher index and never displaces it: the seed's k-th score is a strict entry threshold from the first key on.  NaN is
+ *   never selected; an all-zero query scores 0 against every key.
+ *   D in {64,128,256}, 1 <= k <= RAGRAPH_TOPK_MAX, B >= 1; RAGRAPH_EINVAL / RAGRAPH_EUNSUPPORTED (another D) before any launch.
+ *   ONE launch for every B: a workgroup takes 16 queries and the tail, keeps its winners in LDS and merges them with the seed.
+ *   Only a long tail under few queries (more than 32 tiles of 16 KiB -- 512 rows at D = 256 -- and at most one query group of 16 per CU)
+ *   is cut into slices over several workgroups, whose lists the last workgroup of a query group to finish (a ticket) merges
+ *   with the seed -- still one launch, behind one memset node that clears the tickets (the workspace carries no state from
+ *   call to call).  No score slab, no stacked copy of the lists, no list in scratch.  ws:
+ *   ragraph_topk_cosine_tail_workspace_bytes (the slices' lists and the tickets; 256 bytes for an unsliced call); no
+ *   allocation, no synchronisation, no read-back: capturable. */
+#define RAGRAPH_TOPK_TAIL_MAX 65536
+size_t ragraph_topk_cosine_tail_workspace_bytes(int64_t B, int64_t T, int D, int k);
+int ragraph_topk_cosine_tail_f32(const float* Q, int64_t B, const float* Kn_tail, int64_t T, int D, int k,
+                                 int64_t idx_base_tail, const float* seed_scores, const int64_t* seed_idx,
+                                 float* out_scores, int64_t* out_idx, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * a3  banks of duplicates  -- the reference's own bank recipe makes most rows bit-identical:
  *     RAGraph_node/ragraph_utils/ToyGraphBase.py:91-119 appends 1 + num_augment_scale passes per resource graph, :98 draws

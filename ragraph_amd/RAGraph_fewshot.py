@@ -71,10 +71,9 @@ class ToyGraphBaseFewShot(ToyGraphBase):
         return self._positions.view()
 
     def add_resources(self, keys, values, labels, positions=None):
-        super().add_resources(keys, values, labels)
         if positions is None:
             positions = torch.zeros(keys.shape[0], self.num_anchors, device=self.device)
-        self._positions.append(positions)
+        super().add_resources(keys, values, labels, positions)   # (one path: the normalised caches grow with the bank)
 
     def similarity_scores(self, search_keys, search_adj, anchors=None):
         """ToyGraphBase.py:49-61: structure_weight * cos(position codes) + semantic_weight * cos(embeddings)."""

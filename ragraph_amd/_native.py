@@ -23,6 +23,7 @@ OK, EINVAL, EUNSUPPORTED, EWORKSPACE, EDEVICE = 0, -1, -2, -3, -4
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_LEAKY, ACT_ELU = 0, 1, 2, 3, 4
 TOPK_MAX = 64                # the fused kernels' list limit (RAGRAPH_TOPK_MAX)
 TOPK_ORDERED_MAX = 4096      # ordered top-k over exact fp32 score slabs (RAGRAPH_TOPK_ORDERED_MAX)
+TOPK_TAIL_MAX = 65536        # rows one seeded tail pass takes (RAGRAPH_TOPK_TAIL_MAX)
 POSITION_CODES_LDS_MAX = 40000     # nodes one anchor's distance vector may have in LDS (ragraph_position_codes_csr_f32)
 POSITION_CODES_LONG_ROW = 512      # RAGRAPH_POSITION_CODES_LONG_ROW: rows with more edges go to a whole workgroup
 
@@ -77,6 +78,8 @@ SIGNATURES = {
     "ragraph_topk_cosine_mix_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _f32, _f32, _i32, _i64, _vp, _vp, _vp,
                                           _sz, _vp]),
     "ragraph_topk_merge_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "ragraph_topk_cosine_tail_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "ragraph_topk_cosine_tail_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ragraph_dedup_rows_workspace_bytes": (_sz, [_i64]),
     "ragraph_dedup_rows_f32": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ragraph_topk_expand_groups_f32": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp]),

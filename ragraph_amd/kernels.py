@@ -620,6 +620,40 @@ def topk_merge(scores: torch.Tensor, idx: torch.Tensor):
     return out_s, out_i
 
 
+TOPK_TAIL_MAX = N.TOPK_TAIL_MAX   # rows one topk_cosine_tail call takes (RAGRAPH_TOPK_TAIL_MAX)
+
+
+def topk_cosine_tail(q: torch.Tensor, keys_tail: torch.Tensor, seed_scores: torch.Tensor, seed_idx: torch.Tensor,
+                     idx_base_tail: int):
+    """The canonical top-k of a finished list and more keys: `seed_scores` / `seed_idx` [B, k] is the canonical list of a
+    search over other rows (all indices below idx_base_tail; its end may be -inf / INT64_MAX padding), `keys_tail` [T, D] rows
+    from normalize_rows() appended behind them (row j carries index idx_base_tail + j), `q` the RAW queries of the seed's
+    search.  Returns (scores, idx) [B, k]: the bits of one search over all rows (ragraph_topk_cosine_tail_f32: one launch, a
+    memset node in front of it when a long tail under few queries is cut into slices).  D in {64, 128, 256}, k <= TOPK_MAX,
+    1 <= T <= TOPK_TAIL_MAX; T < k is fine."""
+    L = _ready()
+    q = _f32c(q, "topk_cosine_tail.q")
+    kt = _f32c(keys_tail, "topk_cosine_tail.keys_tail")
+    ss = _f32c(seed_scores, "topk_cosine_tail.seed_scores")
+    si = _idxc(seed_idx, "topk_cosine_tail.seed_idx")
+    if q.dim() != 2 or kt.dim() != 2 or q.shape[1] != kt.shape[1]:
+        raise RagraphNativeError(f"topk_cosine_tail: bad shapes {tuple(q.shape)} x {tuple(kt.shape)}")
+    if ss.dim() != 2 or ss.shape != si.shape or ss.shape[0] != q.shape[0]:
+        raise RagraphNativeError(f"topk_cosine_tail: seed {tuple(ss.shape)} / {tuple(si.shape)} for {q.shape[0]} queries")
+    B, D = q.shape
+    T, k = kt.shape[0], ss.shape[1]
+    scores = torch.empty((B, k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((B, k), dtype=torch.int64, device=q.device)
+    if B == 0:
+        return scores, idx
+    # (+ 4096: the statistics words of a filtered call sit in the LAST bytes of the shared workspace and are read back after the fact)
+    ws = _workspace(L.ragraph_topk_cosine_tail_workspace_bytes(B, T, D, k) + 4096, q.device)
+    N.check(L.ragraph_topk_cosine_tail_f32(q.data_ptr(), B, kt.data_ptr(), T, D, k, idx_base_tail, ss.data_ptr(), si.data_ptr(),
+                                           scores.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws.numel() - 4096, _stream()),
+            "topk_cosine_tail")
+    return scores, idx
+
+
 def dedup_rows(keys_normalized: torch.Tensor):
     """Groups of bit-identical bank rows (ragraph_dedup_rows_f32; the reference's bank recipe stores most rows several
     hundred thousand times over, ToyGraphBase.py:91-119 + Augmentation.py:9-20).  Returns (U, largest group, uniq_row [U]

@@ -9,10 +9,16 @@ from ._native import TOPK_MAX
 
 
 class KeyIndex:
-    """One bank version on the device: the normalised keys plus the copies the faster kernels stream (packed fp32 for
+    """One bank on the device: the normalised keys plus the copies the faster kernels stream (packed fp32 for
     the LDS-DMA ring, bf16 for the filter), made on first use, and the dispatch to the fastest exact top-k for a batch.
     `ops` supplies the kernels (default: this module); an object without the optional entries (the CPU tests' oracle
-    shim) simply always takes topk_cosine."""
+    shim) simply always takes topk_cosine.
+
+    A bank that grows (extend) is a SEALED part -- the rows the copies, the duplicate groups and the int8 verdict were made
+    from -- and a short TAIL of rows appended since: topk searches the sealed rows exactly as it would a bank of only those
+    rows, then continues the finished lists over the tail (ops.topk_cosine_tail: the same fmaf chains, the same canonical
+    order, so the bits of one search over all rows).  seal() folds the tail in: it drops what was derived from the ROWS and
+    keeps what was learnt from the QUERIES (priors, demotions, re-probe clocks).  DESIGN.md section 4.19."""
 
     MAX_FILTERED_BATCH = 262144
     # int8 levels only for banks whose int8 copy is accurate enough: max |dk| of the dequantised rows.  Gaussian-like unit
@@ -77,6 +83,15 @@ class KeyIndex:
     DEDUP_MIN_ROWS = 2048
     DEDUP_MAX_UNIQUE = 0.9
     DEDUP_MAX_GROUP = 64
+    # The tail is folded in (seal) once it holds more than min(TAIL_MAX_ROWS, sealed_rows // TAIL_DIVISOR) rows, or when a call
+    # asks for more keys than the sealed part has.  TAIL_DIVISOR is derived, not measured: a small bank then grows by at least
+    # a ninth between two re-seals, so the rows re-converted over its life are a geometric sum -- at most nine times its final
+    # size -- and a 40-row bank that receives 40 more re-seals at once.  TAIL_MAX_ROWS is measured: the largest swept tail
+    # whose call takes at most 1.10 x the call without one at 4096 and at 100 000 queries against 1M x 256 keys
+    # (profiles/bank_append.txt: 512 rows cost 5 %, 4096 rows 17 - 18 %; the tail defers a rebuild, it is not a second search
+    # path).  RAGRAPH_BANK_TAIL=0: extend seals at once -- the bank of one version this class was before (A/B, escape hatch).
+    TAIL_DIVISOR = 8
+    TAIL_MAX_ROWS = 512
 
     def __init__(self, keys_normalized: torch.Tensor, ops=None, dedup: bool = True):
         if ops is None:
@@ -90,7 +105,12 @@ class KeyIndex:
         self._width = pad(self.dim) if pad is not None else self.dim   # None: no fused kernel for this width
         if self._width is not None and self._width != self.dim:
             keys_normalized = ops.pad_cols(keys_normalized, self._width)
-        self.keys_normalized = keys_normalized
+        self.keys_normalized = keys_normalized      # all rows, sealed and tail
+        self._store = keys_normalized               # padded widths: the growable padded matrix keys_normalized is a prefix of
+        self._sealed_rows = int(keys_normalized.shape[0])
+        self._tail_rows = 0
+        self._dedup = dedup
+        self.tail_enabled = os.environ.get("RAGRAPH_BANK_TAIL", "1") != "0"
         self._packed = None
         self._bf16 = None
         self._filter_off = False  # set when this bank defeats the filter (see _poll_overflow)
@@ -123,6 +143,66 @@ class KeyIndex:
         self.duplicate_stats = None   # (rows, unique rows, largest group) once judged
 
     @property
+    def sealed_rows(self) -> int:
+        """Rows the copies, groups and verdicts of this index cover."""
+        return self._sealed_rows
+
+    @property
+    def tail_rows(self) -> int:
+        """Rows appended since (searched by the seeded tail pass)."""
+        return self._tail_rows
+
+    @staticmethod
+    def _capturing() -> bool:
+        return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+    def _sealed_keys(self) -> torch.Tensor:
+        return self.keys_normalized[:self._sealed_rows] if self._tail_rows else self.keys_normalized
+
+    def extend(self, keys_normalized: torch.Tensor) -> None:
+        """The bank grew: `keys_normalized` is its new, longer normalised matrix, whose first sealed_rows + tail_rows rows
+        are bit-equal to what this index holds (the caller's contract; checked by shape only).  The new rows join the tail;
+        nothing is rebuilt and no counter, history, demotion or pending statistics word is touched.  A padded width keeps its
+        own growable padded matrix and pads the new rows only."""
+        n_old, n_new = self._sealed_rows + self._tail_rows, int(keys_normalized.shape[0])
+        if keys_normalized.dim() != 2 or keys_normalized.shape[1] != self.dim or n_new < n_old:
+            raise ValueError(f"KeyIndex.extend: {tuple(keys_normalized.shape)} does not continue a bank of {n_old} x {self.dim}")
+        if self._width is not None and self._width != self.dim:
+            if self._store.shape[0] < n_new:
+                grown = self._store.new_zeros((max(n_new, 2 * self._store.shape[0]), self._width))
+                grown[:n_old] = self._store[:n_old]
+                self._store = grown
+            self._store[n_old:n_new, :self.dim] = keys_normalized[n_old:]
+            self.keys_normalized = self._store[:n_new]
+        else:
+            self.keys_normalized = self._store = keys_normalized
+        self._tail_rows = n_new - self._sealed_rows
+        if not self.tail_enabled or getattr(self.ops, "topk_cosine_tail", None) is None:
+            self.seal()
+        else:
+            self._maybe_seal()
+
+    def _maybe_seal(self, k: int = 0) -> None:
+        """The sealing rule (at extend and at the start of topk); never while a stream is being captured."""
+        if self._tail_rows and not self._capturing() and (
+                self._tail_rows > min(self.TAIL_MAX_ROWS, self._sealed_rows // self.TAIL_DIVISOR) or k > self._sealed_rows):
+            self.seal()
+
+    def seal(self) -> None:
+        """Fold the tail into the sealed part.  Dropped: what was derived from the rows (the bf16 / int8 and packed copies, the
+        duplicate groups, the int8 copy's verdict), rebuilt lazily as for a new bank.  Kept: what was learnt from the queries
+        (_spec with its priors and tight-bound state, _i8_off / _filter_off, _demoted and the re-probe clocks, _queries,
+        _overflowed) -- a learnt prior is a lower bound of a k-th best score, which more rows can only raise, and every
+        answer is proven anyway."""
+        if not self._tail_rows:
+            return
+        self._sealed_rows += self._tail_rows
+        self._tail_rows = 0
+        self._bf16 = self._packed = None
+        self._collapsed = None if self._dedup else False
+        self._i8_ok = self.i8_classes = None
+
+    @property
     def overflowed_queries(self) -> int:
         """Queries of polled filtered calls that went to the exact scan (diagnostic)."""
         return self._overflowed + (self._collapsed[0].overflowed_queries if self._collapsed else 0)
@@ -139,11 +219,11 @@ class KeyIndex:
             self._judge_duplicates()
         if self._collapsed and self._collapsed[0].keys_normalized.shape[0] < min_unique:
             self._collapsed = False
-        return int(self.search_index.keys_normalized.shape[0])
+        return int(self.search_index._sealed_keys().shape[0])
 
     def _judge_duplicates(self):
-        """Once per bank version (never while a HIP graph is being captured: one read-back)."""
-        kn = self.keys_normalized
+        """Once per sealed part (never while a HIP graph is being captured: one read-back)."""
+        kn = self._sealed_keys()
         dedup = getattr(self.ops, "dedup_rows", None)
         if dedup is None or kn.shape[0] < self.DEDUP_MIN_ROWS:
             self._collapsed = False
@@ -366,7 +446,7 @@ class KeyIndex:
         if self._i8_ok is None and not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
             # (the copy has two scales, csrc/filter_common.h: the NORMAL granules' error decides, unless more than a quarter
             # of the granules are HEAVY ones with a useless bound -- a bank of heavy-tailed rows throughout)
-            c = self.ops.int8_copy_classes(self._bf16, self.keys_normalized.shape[0])
+            c = self.ops.int8_copy_classes(self._bf16, self._sealed_rows)
             many_heavy = 4 * c["heavy_granules"] > c["granules"] and c["err_heavy"] > self.I8_MAX_ERR
             self._i8_ok = c["err"] <= self.I8_MAX_ERR and not many_heavy
             self.i8_classes = c
@@ -390,10 +470,35 @@ class KeyIndex:
         sharpens its per-query bounds across the shards through `exchange` (kernels.topk_cosine_filtered), and every
         decision that changes which collectives run is taken from plan_n -- the largest shard's size -- so that all
         ranks take it alike.  prior (with exchange only): the speculative first bound the owner of the sharded bank chose for
-        THIS call on every rank alike (it removes the bound pass and exchange 0; the owner proves the merged rows)."""
-        ops, kn = self.ops, self.keys_normalized
+        THIS call on every rank alike (it removes the bound pass and exchange 0; the owner proves the merged rows).
+        With a tail: the sealed rows are searched as a bank of their own (every rule below unchanged), then one
+        ops.topk_cosine_tail call continues the lists over the tail; idx_base applies to both parts.  Calls without a seeded
+        pass -- k > TOPK_MAX, banks wider than every fused kernel -- run over all rows as ever; a shard of a sharded bank
+        (exchange) seals first."""
+        ops = self.ops
         if q.shape[1] != self.dim:
             raise ValueError(f"KeyIndex.topk: queries of {q.shape[1]} columns against a bank of {self.dim}")
+        if self._tail_rows:
+            if exchange is not None:
+                self.seal()
+            else:
+                self._maybe_seal(k)
+        if not self._tail_rows or k > TOPK_MAX or self._width is None:
+            return self._search(self.keys_normalized, q, k, idx_base, exchange, plan_n, prior)
+        if self._width != self.dim:
+            q = ops.pad_cols(q, self._width)
+        if k > self._sealed_rows:   # (only while capturing: the rule above seals otherwise) exact over all rows, no seed
+            return ops.topk_cosine(q, self.keys_normalized, k, idx_base=idx_base)
+        s, i = self._search(self._sealed_keys(), q, k, idx_base)
+        step = getattr(ops, "TOPK_TAIL_MAX", 65536)   # (a longer tail only exists under capture: one call per TOPK_TAIL_MAX rows)
+        for t0 in range(self._sealed_rows, self._sealed_rows + self._tail_rows, step):
+            t1 = min(t0 + step, self._sealed_rows + self._tail_rows)
+            s, i = ops.topk_cosine_tail(q, self.keys_normalized[t0:t1], s, i, idx_base + t0)
+        return s, i
+
+    def _search(self, kn: torch.Tensor, q: torch.Tensor, k: int, idx_base: int = 0, exchange=None, plan_n: int = 0, prior=None):
+        """topk over the rows kn: the sealed part (q already at the padded width then), or all rows of a bank without a tail."""
+        ops = self.ops
         if k > TOPK_MAX and exchange is None:
             # ordered large k (exact fp32 score slabs) over the full bank: duplicate rows score alike and the lower row wins,
             # so no collapse is needed; the prior, counters and pending overflow word are left as they are
@@ -488,7 +593,7 @@ class KeyIndex:
             if B > self.MAX_FILTERED_BATCH:
                 # the candidate lists take 8 KiB per query: slabs of 256 k queries keep the workspace at 2 GiB (the edge
                 # flavour asks for all 4 M nodes at once) at the throughput of one big call
-                outs = [self.topk(q[b0:b0 + self.MAX_FILTERED_BATCH], k, idx_base)
+                outs = [self._search(kn, q[b0:b0 + self.MAX_FILTERED_BATCH], k, idx_base)
                         for b0 in range(0, B, self.MAX_FILTERED_BATCH)]
                 return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
             cap, had_i8 = self._cap_i8()

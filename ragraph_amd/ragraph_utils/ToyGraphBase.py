@@ -1,9 +1,11 @@
 """Mirror of RAGraph_node/ragraph_utils/ToyGraphBase.py (and the graph flavour): the toy-graph vector library.
 
 Bank layout in HBM: keys [N,D] fp32 (unit rows, as stored by the reference, ToyGraphBase.py:109), values [N,D],
-labels [N,C] one-hot fp32, plus `keys_normalized` -- F.normalize(keys) computed ONCE per bank version; the reference
+labels [N,C] one-hot fp32, plus `keys_normalized` -- F.normalize(keys) computed ONCE per row; the reference
 recomputes it on every retrieve (SimilarityFunctions.py:11; 2 GB of traffic per call at 1M x 256).
-Storage grows geometrically (the reference re-allocates with torch.cat per resource graph, ToyGraphBase.py:116-119).
+Storage grows geometrically (the reference re-allocates with torch.cat per resource graph, ToyGraphBase.py:116-119), and so
+do the normalised caches once they exist: an append normalises the NEW rows into them and hands the longer matrix to the
+bank's K.KeyIndex (KeyIndex.extend: the new rows are its tail), instead of dropping caches and index.
 """
 from __future__ import annotations
 
@@ -31,6 +33,18 @@ class _Bank:
             self.buf = new
         self.buf[self.n:need] = rows
         self.n = need
+
+    def reserve(self, m: int) -> Tensor:
+        """Room for m more rows (old rows carried over bit for bit when the store reallocates): the view to fill them in."""
+        need = self.n + m
+        if need > self.buf.shape[0]:
+            new = torch.empty((max(need, 2 * self.buf.shape[0], 1024), self.buf.shape[1]), dtype=torch.float32,
+                              device=self.buf.device)
+            new[:self.n] = self.buf[:self.n]
+            self.buf = new
+        out = self.buf[self.n:need]
+        self.n = need
+        return out
 
     def view(self) -> Tensor:
         if _Bank.reads is not None:   # (a training step being prepared for capture: ragraph_amd.capture)
@@ -83,9 +97,10 @@ class ToyGraphBase:
         self._labels = _Bank(num_class, self.device)
         self.num_anchors, self.dis_q = 10, 10             # ToyGraphBase.py:27-28
         self._positions = _Bank(self.num_anchors, self.device)   # position-aware codes of the sampled toy graphs (:114,119)
-        self._keys_normalized = None  # cache, invalidated by every append
+        self._keys_normalized = None  # cache: the current N-row tensor (made on first use; an append extends it by its rows), or None
         self._positions_normalized = None   # the same for the codes (read only when structure_weight != 0)
-        self._index = None            # K.KeyIndex of this bank version (packed / bf16 copies made on first use)
+        self._kn_store = self._pn_store = None   # the growable stores the two caches are prefixes of
+        self._index = None            # K.KeyIndex of this bank (packed / bf16 copies made on first use; an append extends it)
         # RAGraph_node/ragraph_utils/ToyGraphBase.py:28-29.  With structure_weight == 0 retrieval is the semantic top-k and
         # its scores are NOT scaled by semantic_weight, as in the reference's active code (:66-67); otherwise the score is
         # structure_weight * cos(position codes) + semantic_weight * cos(embeddings) (RAGraph_node_fewshot/.../ToyGraphBase.py:47-65)
@@ -118,13 +133,36 @@ class ToyGraphBase:
     def add_resources(self, keys: Tensor, values: Tensor, labels: Tensor, positions: Tensor | None = None) -> None:
         """Append rows to the bank (what ToyGraphBase.py:116-119 does with torch.cat)."""
         assert keys.shape[0] == values.shape[0] == labels.shape[0]
+        n0, p0 = self._keys.n, self._positions.n
         self._keys.append(keys)
         self._values.append(values)
         self._labels.append(labels)
         if positions is not None:
             assert positions.shape[0] == keys.shape[0]
             self._positions.append(positions)
-        self._keys_normalized = self._positions_normalized = self._index = None
+        # caches that exist grow by the new rows (normalised alone: a row's norm tree sees no other row); one that was never
+        # read stays None and is made whole on first use
+        if self._keys_normalized is not None:
+            self._keys_normalized = self._extend_normalized(self._kn_store, self._keys, n0)
+            if self._index is not None:
+                self._index.extend(self._keys_normalized)
+        else:
+            self._index = None
+        if self._positions_normalized is not None:
+            self._positions_normalized = self._extend_normalized(self._pn_store, self._positions, p0)
+
+    @staticmethod
+    def _extend_normalized(store: _Bank, raw: _Bank, n0: int) -> Tensor:
+        """Normalise raw's rows [n0, raw.n) into the store behind its n0 rows; the store's current view."""
+        if raw.n > n0:
+            K.normalize_rows(raw.buf[n0:raw.n], out=store.reserve(raw.n - n0))
+        return store.buf[:store.n]
+
+    @staticmethod
+    def _adopt_normalized(rows: Tensor) -> _Bank:
+        store = _Bank(rows.shape[1], rows.device)
+        store.buf, store.n = rows, rows.shape[0]
+        return store
 
     def set_resources(self, keys: Tensor, values: Tensor, labels: Tensor, positions: Tensor | None = None) -> None:
         """Adopt caller-owned device tensors as the bank without copying (e.g. a 1M-row synthetic bank).  Without
@@ -138,20 +176,25 @@ class ToyGraphBase:
             self._positions = _Bank(self._positions.buf.shape[1], self.device)
         for b, t in stores:
             b.buf, b.n = t.to(self.device, torch.float32).contiguous(), t.shape[0]
-        self._keys_normalized = self._positions_normalized = self._index = None
+        self._reset_caches()
+
+    def _reset_caches(self) -> None:
+        self._keys_normalized = self._positions_normalized = self._index = self._kn_store = self._pn_store = None
 
     @property
     def keys_normalized(self) -> Tensor:
         if self._keys_normalized is None:
             self._keys_normalized = K.normalize_rows(self.resource_keys)
+            self._kn_store = self._adopt_normalized(self._keys_normalized)
         return self._keys_normalized
 
     @property
     def positions_normalized(self) -> Tensor:
-        """F.normalize(resource_positions), once per bank version (cosine_similarity re-normalises them on every call,
+        """F.normalize(resource_positions), once per row (cosine_similarity re-normalises them on every call,
         RAGraph_node_fewshot/ragraph_utils/ToyGraphBase.py:51-53).  An all-zero code row stays zero."""
         if self._positions_normalized is None:
             self._positions_normalized = K.normalize_rows(self.resource_positions)
+            self._pn_store = self._adopt_normalized(self._positions_normalized)
         return self._positions_normalized
 
     def _require_positions(self) -> None:
@@ -300,6 +343,7 @@ class ToyGraphBase:
         if not append:  # fresh stores: the old ones may be tensors adopted from the caller (set_resources)
             self._keys, self._values, self._labels, self._positions = (
                 _Bank(b.buf.shape[1], self.device) for b in (self._keys, self._values, self._labels, self._positions))
+            self._reset_caches()
         positions = blob.get("positions")
         if positions is not None and positions.shape[0] != blob["keys"].shape[0]:
             positions = None   # a bank saved without codes
