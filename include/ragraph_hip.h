@@ -85,6 +85,8 @@ int ragraph_normalize_rows_f32(const float* X, int64_t n, int D, float* out, voi
  *   (torch.topk would rank NaN first) -- inputs are finite by contract.
  */
 #define RAGRAPH_TOPK_MAX 64
+/* the longest list a FILTERED call returns (ragraph_topk_cosine_filtered_wide128_f32); RAGRAPH_TOPK_MAX is the fused fp32 kernels' */
+#define RAGRAPH_TOPK_FILTER_MAX 128
 size_t ragraph_topk_cosine_workspace_bytes(int64_t B, int64_t N, int D, int k);
 int ragraph_topk_cosine_f32(const float* Q, int64_t B, const float* Kn, int64_t N, int D, int k, int64_t idx_base,
                             float* out_scores, int64_t* out_idx, void* ws, size_t ws_bytes, void* stream);
@@ -144,7 +146,7 @@ int ragraph_topk_cosine_mix_f32(const float* Q, int64_t B, const float* Kn, int6
  *   rescored with the natural-order fp32 fmaf chain and selected in canonical order, which gives the exact top-k of
  *   everything seen so far and a tighter bound for the next level (large batches: [0,N/32), [N/32,N/4), [N/4,N); small
  *   ones: fewer, steeper levels -- ragraph_topk_cosine_filtered_plan).  The result has the same bits as
- *   ragraph_topk_cosine_f32.  D in {64,128,256}, k <= 32; lists of 33 .. 64 keys: the _wide entries below.
+ *   ragraph_topk_cosine_f32.  D in {64,128,256}, k <= 32; lists of 33 .. 64 keys: the _wide entries below, 65 .. 128: _wide128.
  *   Kb   bf16 copy of Kn made by ragraph_keys_to_bf16 (ragraph_keys_bf16_rows(N) rows x D, uint16 storage: the bf16 rows
  *        padded to a multiple of 256 keys, a tail row, the int8 rows, their tail row, the int8 copy's granule table, and
  *        256 rows of slack that the last stage of an int8 level may read).  The int8 rows come in two classes of granules
@@ -245,6 +247,20 @@ int ragraph_topk_cosine_filtered_wide_plan(int64_t B, int64_t N, int D, int k, i
 int ragraph_topk_cosine_filtered_wide_f32(const float* Q, int64_t B, const float* Kn, const float* Kp, const uint16_t* Kb,
                                           int64_t N, int D, int k, int64_t idx_base, float* out_scores, int64_t* out_idx,
                                           int* overflow, int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream);
+/* Once more for lists of 65 <= k <= min(N, RAGRAPH_TOPK_FILTER_MAX = 128) keys: the same arguments, bits (those of
+ * ragraph_topk_cosine_bank_f32, canonical order), statistics words and thread-local prior, tight bound and int8 cap; no read-back,
+ * HIP-graph capturable.  The MFMA kernels are the same launches; the kernels that carry a list run in their form for 128 winners
+ * (two entries of a wave's list per lane).  Candidate lists are always plain here (RAGRAPH_FILTER_SCORED is not honoured beyond
+ * k = 64).  One path per k: RAGRAPH_EINVAL for k <= 64 and k > 128, RAGRAPH_EUNSUPPORTED and a size of 0 for another D -- before
+ * any pointer is touched.  _wide128_workspace_bytes is never less than _wide_workspace_bytes of the same shape at k = 64. */
+size_t ragraph_topk_cosine_filtered_wide128_workspace_bytes(int64_t B, int64_t N, int D, int k);
+int ragraph_topk_cosine_filtered_wide128_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]);
+/* ... and how many of that plan's levels, the last ones, run on the int8 copy (the calling thread's cap applied; 0 for a shape
+ * the entry refuses): a level is planned for 1.3 k (end / previous end) <= 1024 candidates, an int8 level for half that. */
+int ragraph_topk_cosine_filtered_wide128_i8_levels(int64_t B, int64_t N, int D, int k);
+int ragraph_topk_cosine_filtered_wide128_f32(const float* Q, int64_t B, const float* Kn, const float* Kp, const uint16_t* Kb,
+                                             int64_t N, int D, int k, int64_t idx_base, float* out_scores, int64_t* out_idx,
+                                             int* overflow, int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream);
 
 /* a1 over a ROW-SHARDED bank (one shard per GPU; the reference is single-GPU, so no reference line beyond the retrieval
  * itself -- SimilarityFunctions.py:6-16 + ToyGraphBase.py:66-67).  As ragraph_topk_cosine_filtered_f32 on this shard's

@@ -176,6 +176,8 @@ __global__ void __launch_bounds__(256) filter_theta_kernel(FilterThr t, int64_t 
 // share a part k^2 / 2G ~ 1.2 times on average); with G = k parts (round 1: the minimum of k maxima) only of
 // prefix / (ln k + 1).  Sharded banks: the k largest, descending, also go to scores[B,k] and travel through the same
 // exchange as a level's exact scores (the k-th largest of the union of all shards' values bounds the global k-th best).
+// NPL: part maxima per lane -- 2 (G <= 128), or 4 (G <= 256: lists of 65 .. 128 keys).
+template <int NPL = 2>
 __global__ void __launch_bounds__(256) filter_bound_scores_kernel(FilterThr t, int64_t B, float* __restrict__ scores,
                                                                   float* __restrict__ theta) {
   // one wave per query: lane l holds parts l and l + 64 (G <= 128) and ranks them by counting (ties by part index)
@@ -184,26 +186,26 @@ __global__ void __launch_bounds__(256) filter_bound_scores_kernel(FilterThr t, i
   if (q >= B) return;
   const float eps = filter_eps(t, q);
   const int G = t.ngroups;
-  float v[2];
-  int rank[2] = {0, 0};
+  float v[NPL];
+  int rank[NPL] = {};
 #pragma unroll
-  for (int u = 0; u < 2; ++u) {
+  for (int u = 0; u < NPL; ++u) {
     const int g = lane + 64 * u;
     v[u] = g < G ? __fsub_rn(ord2f(t.gmax[q * G + g]), eps) : RG_NEG_INF;
   }
 #pragma unroll
-  for (int w = 0; w < 2; ++w) {
+  for (int w = 0; w < NPL; ++w) {
     if (64 * w >= G) break;  // (wave-uniform)
     const int on = G - 64 * w < 64 ? G - 64 * w : 64;
     for (int o = 0; o < on; ++o) {
       const float x = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v[w]), o));   // (o: wave-uniform)
       const int xi = o + 64 * w;
 #pragma unroll
-      for (int u = 0; u < 2; ++u) rank[u] += (x > v[u] || (x == v[u] && xi < lane + 64 * u)) ? 1 : 0;
+      for (int u = 0; u < NPL; ++u) rank[u] += (x > v[u] || (x == v[u] && xi < lane + 64 * u)) ? 1 : 0;
     }
   }
 #pragma unroll
-  for (int u = 0; u < 2; ++u) {
+  for (int u = 0; u < NPL; ++u) {
     if (lane + 64 * u < G && rank[u] < t.k) {
       if (scores) scores[q * t.k + rank[u]] = v[u];
       if (rank[u] == t.k - 1) theta[q] = v[u];

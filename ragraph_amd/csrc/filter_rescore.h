@@ -6,12 +6,19 @@
 // flag[b] == 2 (filter_prep_kernel: a ZERO query).  Intermediate levels leave it alone (nothing passed for it; its running
 // result is never used); the final level writes its answer -- every score +0, the canonical order is the index order --
 // and the query is neither counted in *overflow nor listed for the scan.  Returns true when the wave is done with the query.
+template <int LW = 64>
 __device__ __forceinline__ bool zero_query_level(unsigned char fl, int final_level, int k, int64_t idx_base, int lane,
                                                  float* __restrict__ out_s, int64_t* __restrict__ out_i) {
   if (fl != 2) return false;
   if (final_level && lane < k) {
     out_s[lane] = 0.f;
     out_i[lane] = idx_base + lane;
+  }
+  if constexpr (LW > 64) {
+    if (final_level && lane + 64 < k) {
+      out_s[lane + 64] = 0.f;
+      out_i[lane + 64] = idx_base + lane + 64;
+    }
   }
   return true;
 }
@@ -24,7 +31,8 @@ __device__ __forceinline__ bool zero_query_level(unsigned char fl, int final_lev
 // whose bounds were sharpened across the shards): a 16-row tile instead of 64, so that four times as many waves fit a
 // CU -- such a level is a chain of memory latencies per query, and occupancy is what hides them; the rare longer list
 // takes the lane-private row reads.
-template <int D, int CPL, bool FEWTILE = false>
+// LW: 64 (every k <= 64: a lane per winner) or 128 (lists of 65 .. 128 keys: two winners per lane, rescore_common.h).
+template <int D, int CPL, bool FEWTILE = false, int LW = 64>
 __global__ void __launch_bounds__(128, FEWTILE ? 4 : 1) topk_rescore_coop_kernel(const float* __restrict__ Qn, const float* __restrict__ Kn,
                                                                 int* __restrict__ count,
                                                                 const int* __restrict__ cand, int64_t B, int cap, int cs, int k,
@@ -49,15 +57,17 @@ __global__ void __launch_bounds__(128, FEWTILE ? 4 : 1) topk_rescore_coop_kernel
   __builtin_amdgcn_wave_barrier();
   if (lane == 0 && n >= 0) count[b * cs] = 0;  // the next level starts from an empty list (ordered behind the read through n)
   if (lane == 0) note_candidates(cstat, b, n);
-  if (zero_query_level(fl, final_level, k, idx_base, lane, out_s + b * k, out_i + b * k)) return;
+  if (zero_query_level<LW>(fl, final_level, k, idx_base, lane, out_s + b * k, out_i + b * k)) return;
   if (n > cap) {
     over = true;
     n = cap;
   }
+  if constexpr (LW <= 64) {  // (the one-wave scan keeps a lane per entry; no caller passes scan_n > 0 any more)
   if (final_level && over && scan_n > 0) {  // (wave-uniform) calls of up to 16384 queries: the query's wave scans the bank
     if (lane == 0) atomicAdd(overflow, 1);  // itself, and the call needs no fallback launch
     exact_scan_wave<D>(qs[w], Kn, scan_n, k, idx_base, lane, out_s + b * k, out_i + b * k);
     return;
+  }
   }
   if (lane == 0) {
     if (final_level) {
@@ -75,9 +85,9 @@ __global__ void __launch_bounds__(128, FEWTILE ? 4 : 1) topk_rescore_coop_kernel
   const int64_t* pi = prev_i ? prev_i + b * k : nullptr;
   const int* cb = cand + b * cap;
 #define RG_RESCORE(NS_, COOP_) \
-  rescore_query<D, NS_, COOP_>(qs[w], Kn, cb, n, lane, k, base, ps, pi, out_s + b * k, out_i + b * k, tile[w])
+  rescore_query<D, NS_, COOP_, false, 1, LW>(qs[w], Kn, cb, n, lane, k, base, ps, pi, out_s + b * k, out_i + b * k, tile[w])
   if (n <= 16)
-    rescore_query<D, 1, true, true>(qs[w], Kn, cb, n, lane, k, base, ps, pi, out_s + b * k, out_i + b * k, tile[w]);
+    rescore_query<D, 1, true, true, 1, LW>(qs[w], Kn, cb, n, lane, k, base, ps, pi, out_s + b * k, out_i + b * k, tile[w]);
   else if (n <= 64) RG_RESCORE(1, !FEWTILE);
   else if (n <= 128) RG_RESCORE(2, !FEWTILE);
   else if (n <= 256) RG_RESCORE(4, !FEWTILE);
@@ -391,18 +401,23 @@ __global__ void __launch_bounds__(128) topk_rescore_scored_kernel(const float* _
 // notices from the count after the fact and stops filtering that bank.  All 256 threads of the workgroup must call.
 // LW: the list width the call is built for (32: k <= 32; 64: the wide entry's 33 <= k <= 64) -- the rows of ps / pi, and how
 // many of the 4 k partial winners a lane of the merging wave holds (4 LW / 64).
+// LW = 128 (65 <= k <= 128): a wave's sorted list keeps TWO entries per lane -- entry p in lane p & 63 of slot p >> 6, both in
+// registers (named scalars, no indexing: no scratch).  An insertion counts the entries ahead of the newcomer in each slot
+// (ballot + popcount), shifts both slots up by one lane and carries slot 0's lane 63 into slot 1's lane 0.
 template <int D, int LW = 32>
 __device__ __forceinline__ void exact_scan_query(const float4* qs /* LDS: the query row */, const float* __restrict__ Kn,
                                                  int64_t N, int k, int64_t idx_base, float (*tile)[64 * RESCORE_LD],
                                                  float (*ps)[LW], int64_t (*pi)[LW], float* __restrict__ out_s,
                                                  int64_t* __restrict__ out_i) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (zero_query_answer<D>(qs, w == 0 ? k : 0, idx_base, lane, out_s, out_i)) {  // (no scan; every wave takes the same branch,
-    __syncthreads();                                                             // wave 0 writes)
+  if (zero_query_answer<D, (LW > 64 ? 128 : 64)>(qs, w == 0 ? k : 0, idx_base, lane, out_s, out_i)) {  // (no scan; every wave takes the
+    __syncthreads();                                                             // same branch, wave 0 writes)
     return;
   }
   float es = RG_NEG_INF;  // lane p < k: entry p of this wave's sorted list
   int ei = INT_MAX;
+  [[maybe_unused]] float es1 = RG_NEG_INF;  // (LW = 128) entry 64 + lane
+  [[maybe_unused]] int ei1 = INT_MAX;
   float kth_s = RG_NEG_INF;
   int kth_i = INT_MAX;
   for (int64_t base = (int64_t)w * 64; base < N; base += 256) {
@@ -414,21 +429,57 @@ __device__ __forceinline__ void exact_scan_query(const float4* qs /* LDS: the qu
       pend &= pend - 1;
       const float s = __shfl(sc, src);
       const int id = __shfl(key, src);
-      const unsigned long long ahead = __ballot(lane < k && cand_better(es, ei, s, id));
-      const int pos = __popcll(ahead);
-      const float us = __shfl_up(es, 1);
-      const int ui = __shfl_up(ei, 1);
-      if (pos < k) {
-        if (lane == pos) {
-          es = s;
-          ei = id;
-        } else if (lane > pos && lane < k) {
-          es = us;
-          ei = ui;
+      if constexpr (LW <= 64) {
+        const unsigned long long ahead = __ballot(lane < k && cand_better(es, ei, s, id));
+        const int pos = __popcll(ahead);
+        const float us = __shfl_up(es, 1);
+        const int ui = __shfl_up(ei, 1);
+        if (pos < k) {
+          if (lane == pos) {
+            es = s;
+            ei = id;
+          } else if (lane > pos && lane < k) {
+            es = us;
+            ei = ui;
+          }
+        }
+        kth_s = __shfl(es, k - 1);
+        kth_i = __shfl(ei, k - 1);
+      } else {
+        const int pos = __popcll(__ballot(lane < k && cand_better(es, ei, s, id))) +
+                        __popcll(__ballot(lane + 64 < k && cand_better(es1, ei1, s, id)));
+        if (pos < k) {  // (wave-uniform)
+          float us = __shfl_up(es, 1), us1 = __shfl_up(es1, 1);
+          int ui = __shfl_up(ei, 1), ui1 = __shfl_up(ei1, 1);
+          const float cs = __shfl(es, 63);
+          const int ci = __shfl(ei, 63);
+          if (lane == 0) {
+            us1 = cs;
+            ui1 = ci;
+          }
+          if (lane == pos) {
+            es = s;
+            ei = id;
+          } else if (lane > pos && lane < k) {
+            es = us;
+            ei = ui;
+          }
+          if (lane + 64 == pos) {
+            es1 = s;
+            ei1 = id;
+          } else if (lane + 64 > pos && lane + 64 < k) {
+            es1 = us1;
+            ei1 = ui1;
+          }
+        }
+        if (k <= 64) {  // (wave-uniform)
+          kth_s = __shfl(es, k - 1);
+          kth_i = __shfl(ei, k - 1);
+        } else {
+          kth_s = __shfl(es1, k - 65);
+          kth_i = __shfl(ei1, k - 65);
         }
       }
-      kth_s = __shfl(es, k - 1);
-      kth_i = __shfl(ei, k - 1);
       pend &= __ballot(key >= 0 && cand_better(sc, key, kth_s, kth_i));
     }
   }
@@ -436,8 +487,12 @@ __device__ __forceinline__ void exact_scan_query(const float4* qs /* LDS: the qu
     ps[w][lane] = lane < k ? es : RG_NEG_INF;
     pi[w][lane] = (lane < k && ei != INT_MAX) ? (int64_t)ei : INT64_MAX;
   }
+  if constexpr (LW > 64) {
+    ps[w][lane + 64] = lane + 64 < k ? es1 : RG_NEG_INF;
+    pi[w][lane + 64] = (lane + 64 < k && ei1 != INT_MAX) ? (int64_t)ei1 : INT64_MAX;
+  }
   __syncthreads();
-  if (w == 0) {  // 4 k <= 128 partial winners: two per lane (LW = 64: 4 k <= 256, four per lane)
+  if (w == 0) {  // 4 k <= 128 partial winners: two per lane (LW = 64: 4 k <= 256, four per lane; LW = 128: 512, eight)
     constexpr int NM = LW / 16;
     float s2[NM];
     int id2[NM];
@@ -449,7 +504,7 @@ __device__ __forceinline__ void exact_scan_query(const float4* qs /* LDS: the qu
       const int64_t pv = have ? pi[e / k][e % k] : INT64_MAX;
       id2[u] = pv >= INT_MAX ? INT_MAX : (int)pv;
     }
-    wave_select<NM>(s2, id2, k, lane, idx_base, out_s, out_i);
+    wave_select<NM, (LW > 64 ? 128 : 64)>(s2, id2, k, lane, idx_base, out_s, out_i);
   }
   __syncthreads();
 }
@@ -497,6 +552,7 @@ __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __r
   __shared__ __attribute__((aligned(16))) float tile[(COOP || SLICED) ? 4 : 1][(COOP || SLICED) ? 64 * RESCORE_LD : 4];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t b = blockIdx.x;
+  constexpr int LWS = LW > 64 ? 128 : 64;  // the form of the helpers that know a lane per winner (64) or two (128)
   RG_WSTAMP(0);
   if (threadIdx.x < D / 4) qs[threadIdx.x] = reinterpret_cast<const float4*>(Qn + b * D)[threadIdx.x];
   __syncthreads();
@@ -521,7 +577,7 @@ __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __r
                                 // workgroup reading the whole bank, 5 - 7 ms per query where the sliced launch takes 0.5 - 1.7)
       // a ZERO query (flagged by the prepare launch) is answered here -- scores +0, rows in order -- and is neither listed
       // nor counted in *overflow: no kernel of the call counts zero queries (the one-wave kernels' zero_query_level alike)
-      const bool zero = zero_query_answer<D>(qs, w == 0 ? k : 0, idx_base, lane, out_s + b * k, out_i + b * k);
+      const bool zero = zero_query_answer<D, LWS>(qs, w == 0 ? k : 0, idx_base, lane, out_s + b * k, out_i + b * k);
       if (threadIdx.x == 0) {
         count[b * cs] = 0;
         if (!zero) {
@@ -540,8 +596,8 @@ __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __r
   const int* cb = cand + b * cap + lo0 + lo;
   const float* pps = (!SLICED && prev_s && w == 0) ? prev_s + b * k : nullptr;
   const int64_t* ppi = (!SLICED && prev_i && w == 0) ? prev_i + b * k : nullptr;
-#define RG_RESCORE(NS_) rescore_query<D, NS_, COOP>(qs, Kn, cb, nw, lane, k, 0, pps, ppi, ps[w], pi[w], tile[w])
-  if (COOP && nw <= 16) rescore_query<D, 1, true, true>(qs, Kn, cb, nw, lane, k, 0, pps, ppi, ps[w], pi[w], tile[w]);
+#define RG_RESCORE(NS_) rescore_query<D, NS_, COOP, false, 1, LWS>(qs, Kn, cb, nw, lane, k, 0, pps, ppi, ps[w], pi[w], tile[w])
+  if (COOP && nw <= 16) rescore_query<D, 1, true, true, 1, LWS>(qs, Kn, cb, nw, lane, k, 0, pps, ppi, ps[w], pi[w], tile[w]);
   else if (nw <= 64) RG_RESCORE(1);
   else if (nw <= 128) RG_RESCORE(2);
   else if (nw <= 256) RG_RESCORE(4);
@@ -553,7 +609,7 @@ __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __r
   if constexpr (!SLICED) {
     if (threadIdx.x == 0) count[b * cs] = 0;  // every wave has read it: the next level starts from an empty list
   }
-  if (w == 0) {  // 4 k <= 128 partial winners: two per lane (LW = 64: 4 k <= 256, four per lane)
+  if (w == 0) {  // 4 k <= 128 partial winners: two per lane (LW = 64: 4 k <= 256, four per lane; LW = 128: 512, eight)
     constexpr int NM = LW / 16;
     float s[NM];
     int id[NM];
@@ -567,15 +623,21 @@ __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __r
     }
     if constexpr (SLICED) {
       // (wave_select writes 64-bit ids: staged through LDS, stored as the 32-bit local ids the merge expects)
-      wave_select<NM>(s, id, k, lane, 0, ps[0], pi[0]);
+      wave_select<NM, LWS>(s, id, k, lane, 0, ps[0], pi[0]);
       __builtin_amdgcn_wave_barrier();
       const int64_t slot = (b * gridDim.y + blockIdx.y) * k;
       if (lane < k) {
         part_s[slot + lane] = ps[0][lane];
         part_i[slot + lane] = pi[0][lane] >= INT_MAX ? INT_MAX : (int)pi[0][lane];
       }
+      if constexpr (LW > 64) {
+        if (lane + 64 < k) {
+          part_s[slot + lane + 64] = ps[0][lane + 64];
+          part_i[slot + lane + 64] = pi[0][lane + 64] >= INT_MAX ? INT_MAX : (int)pi[0][lane + 64];
+        }
+      }
     } else {
-      wave_select<NM>(s, id, k, lane, final_level ? idx_base : 0, out_s + b * k, out_i + b * k);
+      wave_select<NM, LWS>(s, id, k, lane, final_level ? idx_base : 0, out_s + b * k, out_i + b * k);
     }
   }
   if constexpr (SLICED) {
@@ -604,7 +666,7 @@ __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __r
     if (threadIdx.x < S) cnt[threadIdx.x] = 0;
     if (threadIdx.x == 0) cnt[FILTER_TICKET_SLOT] = 0;
     if (final_level && over_q) {  // (block-uniform) the fixup launch behind this one scans the bank for it, in key slices
-      const bool zero = zero_query_answer<D>(qs, w == 0 ? k : 0, idx_base, lane, out_s + b * k, out_i + b * k);   // (see above)
+      const bool zero = zero_query_answer<D, LWS>(qs, w == 0 ? k : 0, idx_base, lane, out_s + b * k, out_i + b * k);   // (see above)
       if (threadIdx.x == 0 && !zero) {
         overflow_list[atomicAdd(overflow, 1)] = (int)b;
         flag[b] = 1;
@@ -631,13 +693,14 @@ __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __r
       int id[2];
 #pragma unroll
       for (int u = 0; u < 2; ++u) part_entry(lane + 64 * u, s[u], id[u]);
-      wave_select<2>(s, id, k, lane, final_level ? idx_base : 0, out_s + b * k, out_i + b * k);
+      wave_select<2, LWS>(s, id, k, lane, final_level ? idx_base : 0, out_s + b * k, out_i + b * k);
     } else {
-      float s[5];
-      int id[5];
+      constexpr int NF = LW > 64 ? 6 : 5;  // (S k <= 256 and the previous k: 320 entries; LW = 128: S <= 2, 3 k <= 384)
+      float s[NF];
+      int id[NF];
 #pragma unroll
-      for (int u = 0; u < 5; ++u) part_entry(lane + 64 * u, s[u], id[u]);
-      wave_select<5>(s, id, k, lane, final_level ? idx_base : 0, out_s + b * k, out_i + b * k);
+      for (int u = 0; u < NF; ++u) part_entry(lane + 64 * u, s[u], id[u]);
+      wave_select<NF, LWS>(s, id, k, lane, final_level ? idx_base : 0, out_s + b * k, out_i + b * k);
     }
     RG_WSTAMP(9);
   }

@@ -83,6 +83,8 @@ static bool filter_scored_lists(int64_t B, int D, int k, const FilterEnv& env) {
   // 0.148 -> 0.136.  Up to 64 queries the direct kernel keeps several sub-lists per query and several workgroups rescore
   // each: one wave per query measured slower there (one query 0.075 -> 0.080 ms).
   if (B < 65) return false;
+  if (k > 64) return false;  // (lists of 65 .. 128 keys: the scored rounds keep a lane per previous winner -- plain lists, whatever
+                             // RAGRAPH_FILTER_SCORED says)
   if (env.scored >= 0) return env.scored != 0;
   return D == 256 && k <= 16;
 }
@@ -109,17 +111,30 @@ constexpr int64_t FILTER_BOUND_MIN_KEYS = 8192;
 // Parts of the bound pass's prefix: 4 k (at most 128), as many as the prefix has stages (a part is at least one ring stage;
 // sub-tiles of the direct kernel are finer), never fewer than k.
 static int filter_bound_parts(int k, int64_t bound_keys, int D, int64_t B = 1 << 20, int n_shards = 1) {
-  if (B <= 64) return k;  // a handful of queries: the minimum of k part maxima, taken inside the filter launch's prologue
+  // Lists of 65 .. 128 keys: up to 256 parts (four part maxima per lane of the selection) at every batch size -- 128 parts
+  // are exactly k at k = 128, the minimum of k maxima is worth prefix / (ln k + 1) = prefix / 5.9, and a level may have a ratio
+  // of at most 6: no schedule would fit between the two.
+  if (B <= 64 && k <= 64) return k;  // a handful of queries: the minimum of k part maxima, taken inside the filter launch's prologue
                           // (filter_threshold) -- the extra selection launch would cost more than the shorter prefix saves
   int64_t g = 4 * (int64_t)k;
-  if (g > 128) g = 128;
+  if (g > (k > 64 ? 256 : 128)) g = k > 64 ? 256 : 128;
   if (n_shards > 1) g = (g + n_shards - 1) / n_shards;  // (pooled through the exchange: 4 k parts over all shards)
   const int64_t avail = bound_keys == INT64_MAX ? g : bound_keys / (FILTER_STAGE_BYTES / (2 * D));
   if (g > avail) g = avail;
   return (int)(g < k ? k : g);
 }
 // prefix keys per key of exact sample the bound is worth (see filter_bound_scores_kernel)
+// Lists of 65 .. 128 keys have at most 256 parts for k values, fewer than 4 k: the k-th largest of G part maxima over n keys
+// sits where a key's tail probability p has G (1 - (1 - p)^(n / G)) = k, i.e. p n = -G ln(1 - k / G), while the exact k-th best
+// of n0 keys has p n0 = k: the prefix is worth n0 = n x / -ln(1 - x) keys, x = k / G (x = 1/4: 1.15 and x = 1/2: 1.39 -- the
+// 1.2 and 1.5 below), growing to the ln k + 1 of the minimum of k maxima as x -> 1; taken with 10 % of margin.
 static double filter_bound_eff(int k, int parts) {
+  if (k > 64 && parts < 4 * k) {
+    const double worst = log((double)k) + 1.0;
+    if (parts <= k) return worst;
+    const double x = (double)k / (double)parts, eff = 1.1 * -log(1.0 - x) / x;
+    return eff < worst ? (eff > 1.2 ? eff : 1.2) : worst;
+  }
   if (parts >= 4 * k || parts >= 128) return 1.2;
   if (parts >= 2 * k) return 1.5;
   return log((double)k) + 1.0;
@@ -190,11 +205,23 @@ static FilterSchedule filter_schedule(const FilterShape& in) {
   const bool i8_direct = (D == 128 || D == 256 || (D == 64 && i8_direct_d64)) && B <= 256 && N * n_shards >= 65536 && i8_direct_env;
   // bound_keys / eff_div ~ the exact sample the bound is worth: planned for 4 k parts, corrected below if the prefix is
   // too short for that many
-  const double eff_div = filter_bound_eff(k, B <= 64 ? k : 4 * k);
+  const double eff_div = filter_bound_eff(k, k > 64 ? 256 : (B <= 64 ? k : 4 * k));
   auto prefix_for = [&](int64_t n0) {  // prefix whose bound is worth the exact k-th best of n0 keys
+    if (k > 64) {
+      // Lists of 65 .. 128 keys: p parts need p ring stages, and fewer parts are worth less per key (filter_bound_eff) -- the
+      // shortest prefix over every part count the prefix itself has room for.
+      const int64_t stage = FILTER_STAGE_BYTES / (2 * D);
+      int64_t best = INT64_MAX;
+      for (int p = 256; p >= k; --p) {
+        int64_t need = filter_round_up((int64_t)((double)n0 * filter_bound_eff(k, p)));
+        if (need < p * stage) need = filter_round_up(p * stage);
+        if (filter_bound_parts(k, need, D, B) >= p && need < best) best = need;
+      }
+      return best;
+    }
     int64_t nA = filter_round_up((int64_t)((double)n0 * eff_div));
     const int parts = filter_bound_parts(k, nA, D, B);
-    if (parts < 4 * k && parts < 128) nA = filter_round_up((int64_t)((double)n0 * filter_bound_eff(k, parts)));
+    if (parts < 4 * k && (parts < 128 || (k > 64 && parts < 256))) nA = filter_round_up((int64_t)((double)n0 * filter_bound_eff(k, parts)));
     return nA;
   };
   if (B > FILTER_SLAB_MAX_B || N < 4 * 4096) {
@@ -232,6 +259,22 @@ static FilterSchedule filter_schedule(const FilterShape& in) {
       fracs[0] = a;
       fracs[1] = b;
       if (nfr == 2 && b < 2) nfr = 1;
+    }
+    if (k > 64) {
+      // Lists of 65 .. 128 keys: a level may admit 1.3 k (end / previous end) <= cap / 2 keys, a ratio of 6 at k = 128, and the
+      // fixed fractions break that wherever the sample is not N / 64 (the last level of a 130 000-key bank would have a ratio
+      // of 8).  Three levels of EQUAL ratio (N / n0)^(1/3) <= 4 instead -- on the banks whose sample is N / 64 these are the
+      // ends N / 16 and N / 4 the fractions give.
+      nfr = 0;
+      const double r3 = pow((double)N / (double)n0, 1.0 / 3.0);
+      double e = (double)n0;
+      for (int l = 0; l < 2; ++l) {
+        e *= r3;
+        const int64_t ei = filter_round_up((int64_t)e);
+        if (ei * 2 >= N || ei <= prev) break;
+        sc.ends[sc.nlev++] = ei;
+        prev = ei;
+      }
     }
     for (int fi = 0; fi < nfr; ++fi) {
       const int64_t frac = fracs[fi];
@@ -295,7 +338,11 @@ static FilterSchedule filter_schedule(const FilterShape& in) {
     for (int L = 1; L <= FILTER_MAX_LEVELS; ++L) {
       if (force_L > 0 && L != force_L) continue;
       const double r = pow((double)N / (double)n0, 1.0 / L);
-      if (1.3 * k * r > cap / 2 && !(force_n0 > 0 && force_L > 0)) continue;
+      // (lists of 65 .. 128 keys: the prefix must lie inside the first level -- cut down to it, the bound would be worth less than
+      // the n0 keys the first level's ratio is planned from; and they plan against 97 % of half a list: the ends are rounded to
+      // whole pads and stages behind this test)
+      if (k > 64 && bound && L > 1 && (double)nA > (double)n0 * r - 512.0) continue;
+      if (1.3 * k * r > (k > 64 ? 0.97 : 1.0) * (cap / 2) && !(force_n0 > 0 && force_L > 0)) continue;
       // a level: launches + the rescoring kernels' latency floor, plus ~0.4 - 0.5 ns per candidate (1 KB row gather each)
       if (B <= 256) {
         // Direct kernel.  On the int8 copy its pass streams half the bytes and does half the matrix work (one query: 78 ->
@@ -304,7 +351,9 @@ static FilterSchedule filter_schedule(const FilterShape& in) {
         // (int8 wins at every batch size from 1 to 256 on the 1M x 256 bank -- 0.106 -> 0.074, 0.124 -> 0.091, 0.139 -> 0.109,
         // 0.192 -> 0.153 ms -- so where it is eligible the model only chooses ITS schedule; the two constants are not
         // comparable across the dtypes)
-        for (int q8 = i8_direct ? 1 : 0; q8 <= (i8_direct ? 1 : 0); ++q8) {
+        // (lists of 65 .. 128 keys: three times 1.3 k r passes half a list from a ratio of 2 at k = 128 -- the bf16 schedule stays
+        // in the race, or large banks would be left without any plan that fits)
+        for (int q8 = i8_direct && k <= 64 ? 1 : 0; q8 <= (i8_direct ? 1 : 0); ++q8) {
           const double cands = 1.3 * k * r * (q8 ? 3.0 : 1.0);
           // (a handful of queries keep S sub-lists of `cap` slots each: filter_cap)
           if (cands > cap * (q8 ? rescore_slices(B, k) : 1) / 2 && !(force_n0 > 0 && force_L > 0)) continue;
@@ -343,7 +392,7 @@ static FilterSchedule filter_schedule(const FilterShape& in) {
           e = l + 1 == L ? (double)N : e * r;
           const bool q8 = l >= L - i8;
           const double cands = 1.3 * k * r * (q8 ? i8_candf : 1.0);
-          if (cands > cap / 2 && !(force_n0 > 0 && force_L > 0)) fits = false;
+          if (cands > (k > 64 ? 0.97 : 1.0) * (cap / 2) && !(force_n0 > 0 && force_L > 0)) fits = false;
           cost += 60.0 + (e - e_prev) * (double)B * 2.0 * D / (q8 ? 2.4e9 : 1.25e9) +
                   (double)B * cands * per_cand * (q8 && scored ? scored_cand : 1.0);
           e_prev = e;
@@ -371,9 +420,13 @@ static FilterSchedule filter_schedule(const FilterShape& in) {
   }
   sc.n0 = best_n0;
   sc.i8_levels = mid_i8 ? best_L : best_i8;
-  sc.slab0 = 1;
+  // (lists of 65 .. 128 keys: the row top-k behind the slab stops at 64 -- an exact level 0 is ragraph_topk_cosine_bank_f32, whose
+  // own slabs end in the ordered large-k selection)
+  sc.slab0 = k > 64 ? 0 : 1;
   sc.nlev = 0;
   const double r = pow((double)N / (double)best_n0, 1.0 / best_L);
+  // (lists of 65 .. 128 keys: the mid-sized banks' all-int8 plan only where its levels keep to half a list)
+  if (k > 64 && mid_i8 && 1.3 * k * r * 2.0 > cap / 2) sc.i8_levels = best_i8;
   double e = (double)best_n0;
   for (int l = 0; l + 1 < best_L; ++l) {
     e *= r;
@@ -545,7 +598,10 @@ static FilterCall filter_call_plan(const FilterShape& in, FilterSchedule sc) {
     // One bank whose schedule has a bound pass to save: theta = prior for every query, every level filters with max(prior,
     // the running k-th best), and the verify launch behind the last level sends the queries the prior was too high for to
     // the exact scan.
-    c.spec = prior_ok && sc.bound_keys > 0 && N == plan_N;
+    // (Lists of 65 .. 128 keys speculate whatever their first bound is: k parts of one ring stage each are 8 - 33 k keys, which
+    // the smaller banks do not have inside their first half, and the exact level 0 such a plan falls back to -- fp32 score
+    // slabs over n0 keys -- is the dearer thing for a prior to replace.)
+    c.spec = prior_ok && (sc.bound_keys > 0 || k > 64) && N == plan_N;
     if (c.spec) drop_first_level_under_prior();
   }
   // A TIGHT bound t (ragraph_topk_cosine_filtered_set_tight_prior) on top of the prior p: one bank, the ring kernel's batch sizes,

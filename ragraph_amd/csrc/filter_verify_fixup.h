@@ -120,6 +120,8 @@ __global__ void __launch_bounds__(64) filter_repair_gather_kernel(const float* _
   if (lane == 0) theta2[row] = live ? theta[q] : 0.f;
 }
 
+// LW = 128 (lists of 65 .. 128 keys): a lane copies two entries of the row.
+template <int LW = 64>
 __global__ void __launch_bounds__(64) filter_repair_scatter_kernel(const int* __restrict__ list, const float* __restrict__ s2,
                                                                    const int64_t* __restrict__ i2,
                                                                    const unsigned char* __restrict__ flag2, int k,
@@ -136,6 +138,12 @@ __global__ void __launch_bounds__(64) filter_repair_scatter_kernel(const int* __
   if (lane < k) {
     out_s[q * k + lane] = s2[(int64_t)row * k + lane];
     out_i[q * k + lane] = i2[(int64_t)row * k + lane];
+  }
+  if constexpr (LW > 64) {
+    if (lane + 64 < k) {
+      out_s[q * k + lane + 64] = s2[(int64_t)row * k + lane + 64];
+      out_i[q * k + lane + 64] = i2[(int64_t)row * k + lane + 64];
+    }
   }
 }
 
@@ -201,6 +209,7 @@ __global__ void __launch_bounds__(256) verify_merged_prior_kernel(const float* _
 // (FILTER_FIX_SLICES * 32 / LW = 8) rather than carrying 16 x 64 = sixteen slots per lane of the merging wave: SL k <= 512
 // and the part_s / part_i buffers keep their size, the merge keeps its eight slots, and a path that ordinary banks never take
 // (it exists for adversarial clusters) gives up at most a factor of two on a lone overflowed query.
+// LW = 128 (65 <= k <= 128): a quarter of the slices (4 x 128 winners, the same bytes and the same eight slots of the merge).
 template <int D, int LW = 32>
 __global__ void __launch_bounds__(256) topk_overflow_fixup_kernel(const float* __restrict__ Qn, const float* __restrict__ Kn,
                                                                   int64_t N, int k, int64_t idx_base,
@@ -291,7 +300,7 @@ __global__ void __launch_bounds__(256) topk_overflow_fixup_kernel(const float* _
           }
         }
       }
-      wave_select<8>(s8, id8, k, lane, idx_base, out_s + b * k, out_i + b * k);
+      wave_select<8, (LW > 64 ? 128 : 64)>(s8, id8, k, lane, idx_base, out_s + b * k, out_i + b * k);
     }
   }
 }

@@ -7,7 +7,7 @@
 
 namespace ragraph {
 
-// ---- canonical top-k of a wave's 64 NSL (score, id) pairs (score descending, id ascending; k <= 64) -------------------
+// ---- canonical top-k of a wave's 64 NSL (score, id) pairs (score descending, id ascending; k <= LW) -------------------
 // A pair travels as one 64-bit key whose unsigned order is the canonical order: the score's bits made monotone in the
 // upper word, ~id in the lower; an empty slot (-inf, INT_MAX) and a pair already taken are key 0, which decodes to
 // (-inf, INT64_MAX).  Round r: every lane's best remaining key, the wave's maximum of those -- four DPP steps inside
@@ -31,7 +31,10 @@ __device__ __forceinline__ void select_dpp_max(unsigned& hi, unsigned& lo) {
   lo = take ? olo : lo;
 }
 
-template <int NSL>
+// LW = 128 (lists of 65 .. 128 keys): "winner r in lane r" of the rounds below does not hold 128 winners, so every slot count
+// takes the rank-by-counting form, which writes a winner straight to its place and knows no lane-per-winner; its loops stop
+// at each slot's last real pair, so the usual list (a slot or two) costs what it costs at NSL <= 2.
+template <int NSL, int LW = 64>
 __device__ __forceinline__ void wave_select(const float (&s)[NSL], const int (&id)[NSL], int k, int lane, int64_t base,
                                             float* out_s, int64_t* out_i, float* kth_out = nullptr) {
   // kth_out (optional, e.g. an LDS word): receives the k-th winner's score, -inf when fewer than k pairs exist
@@ -42,7 +45,7 @@ __device__ __forceinline__ void wave_select(const float (&s)[NSL], const int (&i
     khi[u] = empty ? 0u : select_ord(s[u]);
     klo[u] = empty ? 0u : ~(unsigned)id[u];
   }
-  if constexpr (NSL <= 2) {
+  if constexpr (NSL <= 2 || LW > 64) {
     // Up to 128 pairs: RANK BY COUNTING instead of k rounds.  Every key is broadcast once (v_readlane, a wave-uniform
     // value) and each lane counts the keys greater than its own: 64 NSL x NSL 64-bit compares, ~1 us at NSL = 2 whatever
     // k is, where the rounds take ~0.35 us each.  A pair with rank r < k is winner r.  Distinct non-empty pairs have
@@ -76,7 +79,13 @@ __device__ __forceinline__ void wave_select(const float (&s)[NSL], const int (&i
         out_i[rank[u]] = (int64_t)(int)~klo[u] + base;
       }
     }
-    if (lane < k && lane >= n_real) {
+    if constexpr (LW > 64) {
+      for (int e = lane; e < k; e += 64)
+        if (e >= n_real) {
+          out_s[e] = RG_NEG_INF;
+          out_i[e] = INT64_MAX;
+        }
+    } else if (lane < k && lane >= n_real) {
       out_s[lane] = RG_NEG_INF;
       out_i[lane] = INT64_MAX;
     }
@@ -238,21 +247,26 @@ __device__ __forceinline__ float coop_scores_few(const float4* __restrict__ qrow
 // lane per candidate, the k = 0..D-1 fmaf chain from +0), merge with the previous level's winners, canonical top-k.
 // COOP: rows staged through the LDS tile `sm` (coop_scores); else every lane reads its own row.
 // CS: ints per list entry (2: the scored lists' {key, I} pairs, of which only the key is read here).
-template <int D, int NS, bool COOP = false, bool FEW = false, int CS = 1>
+// LW = 128: the previous winners take TWO slots (entry p in lane p & 63 of slot p >> 6).
+template <int D, int NS, bool COOP = false, bool FEW = false, int CS = 1, int LW = 64>
 __device__ __forceinline__ void rescore_query(const float4* __restrict__ qrow, const float* __restrict__ Kn,
                                               const int* __restrict__ cand, int n, int lane, int k, int64_t base,
                                               const float* prev_s, const int64_t* prev_i, float* out_s, int64_t* out_i,
                                               float* sm = nullptr) {
   const int first_keys = cand[lane * CS];  // (no dependence on n: the list has >= 64 slots; issued next to the count's load)
-  float s[NS + 1];
-  int id[NS + 1];
+  constexpr int NP = LW > 64 ? 2 : 1;
+  float s[NS + NP];
+  int id[NS + NP];
   // the previous level's winners ride along as already-scored candidates (lane l holds entry l; k <= 64)
-  s[NS] = RG_NEG_INF;
-  id[NS] = INT_MAX;
-  if (prev_s && lane < k) {
-    s[NS] = prev_s[lane];
-    const int64_t pv = prev_i[lane];
-    id[NS] = pv >= INT_MAX ? INT_MAX : (int)pv;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    s[NS + p] = RG_NEG_INF;
+    id[NS + p] = INT_MAX;
+    if (prev_s && lane + 64 * p < k) {
+      s[NS + p] = prev_s[lane + 64 * p];
+      const int64_t pv = prev_i[lane + 64 * p];
+      id[NS + p] = pv >= INT_MAX ? INT_MAX : (int)pv;
+    }
   }
 #pragma unroll
   for (int u = 0; u < NS; ++u) {
@@ -285,7 +299,7 @@ __device__ __forceinline__ void rescore_query(const float4* __restrict__ qrow, c
       id[u] = key;
     }
   }
-  wave_select<NS + 1>(s, id, k, lane, base, out_s, out_i);
+  wave_select<NS + NP, LW>(s, id, k, lane, base, out_s, out_i);
 }
 
 // The exact fallback for one query by ONE wave (a candidate list overflowed: near-duplicate banks, zero queries): every
@@ -293,7 +307,7 @@ __device__ __forceinline__ void rescore_query(const float4* __restrict__ qrow, c
 // full scan of the bank by 64 lanes -- and rare; the four-wave, LDS-staged form is exact_scan_query (topk_filter.hip).
 // A ZERO query (the usual reason for an overflow on an ordinary bank: every score is +0, so every key passes any bound)
 // needs no scan: all chains end at +0 and the canonical order is the index order.  Wave-uniform result.
-template <int D>
+template <int D, int LW = 64>
 __device__ __forceinline__ bool zero_query_answer(const float4* qrow, int k, int64_t idx_base, int lane,
                                                   float* __restrict__ out_s, int64_t* __restrict__ out_i) {
   bool nz = false;
@@ -305,6 +319,12 @@ __device__ __forceinline__ bool zero_query_answer(const float4* qrow, int k, int
   if (lane < k) {
     out_s[lane] = 0.f;
     out_i[lane] = idx_base + lane;
+  }
+  if constexpr (LW > 64) {
+    if (lane + 64 < k) {
+      out_s[lane + 64] = 0.f;
+      out_i[lane + 64] = idx_base + lane + 64;
+    }
   }
   return true;
 }

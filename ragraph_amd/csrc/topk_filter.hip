@@ -26,6 +26,8 @@
 // candidate lists can carry the integer score that admitted each key (SCORED: topk_rescore_scored_kernel).
 // Lists of 33 .. 64 keys (ragraph_topk_cosine_filtered_wide_f32): the same launches of the MFMA kernels, which know no k, and
 // the LW = 64 instantiations of the kernels that carry a list (filter_rescore.h, filter_verify_fixup.h).
+// Lists of 65 .. 128 keys (ragraph_topk_cosine_filtered_wide128_f32): their LW = 128 instantiations, in which a wave holds two
+// entries of a list per lane; plain lists only (filter_scored_lists refuses k > 64).
 //
 // Two filter kernels share one bank layout (filter_common.h: MFMA fragment order of v_mfma_f32_16x16x32_bf16):
 // topk_filter_direct_kernel (topk_filter_direct.hip) for up to 256 queries, and this file's RING kernel above that:
@@ -318,7 +320,7 @@ struct FilterWs {
   float* theta;         // [B] the first bound
   int* overflow_list;   // [B] queries the final level sends to the exact fallback
   int* fix_done;        // [FILTER_FIX_MAX_Q] tickets, [.. x FILTER_FIX_SLICES x 32] partial winners of the sliced fallback scans
-                        // (the wide entry: half the slices x 64 winners, the same bytes)
+                        // (the wide entry: half the slices x 64 winners, the same bytes; wide128: a quarter x 128)
   float* fix_s;
   int64_t* fix_i;
   float* part_s;        // (B <= 64) sliced rescoring: [B][8][k] partial winners
@@ -363,15 +365,15 @@ static size_t filter_ws_carve(char* w, const FilterShape& in, const FilterCall& 
 // ---- the host queries: readers of the call plan ---------------------------------------------------------------------
 // The one argument check of the plan's readers and of the call: 0, or the error code of a shape no filtered call takes.
 // One path per k: the entries built for lists of 32 take 1 <= k <= 32, the WIDE entries (lists of 64: the LW = 64 instantiations
-// of the list-carrying kernels) take 33 <= k <= 64.
-static int filter_shape_code(int64_t B, int64_t N, int D, int k, bool wide = false) {
+// of the list-carrying kernels) take 33 <= k <= 64, the WIDE128 entries (LW = 128) 65 <= k <= 128.  lw: the entry's list width.
+static int filter_shape_code(int64_t B, int64_t N, int D, int k, int lw = 32) {
   if (!filter_dim_ok(D)) return RAGRAPH_EUNSUPPORTED;
-  const bool k_ok = wide ? (k >= 33 && k <= 64) : (k >= 1 && k <= 32);
+  const bool k_ok = lw == 128 ? (k >= 65 && k <= 128) : (lw == 64 ? (k >= 33 && k <= 64) : (k >= 1 && k <= 32));
   return B >= 1 && N >= 1 && k_ok && k <= N ? RAGRAPH_OK : RAGRAPH_EINVAL;
 }
-#define RG_REQUIRE_FILTER_SHAPE(who, B, N, D, k, wide)                                                                \
+#define RG_REQUIRE_FILTER_SHAPE(who, B, N, D, k, lw)                                                                  \
   do {                                                                                                                \
-    const int code__ = filter_shape_code(B, N, D, k, wide);                                                           \
+    const int code__ = filter_shape_code(B, N, D, k, lw);                                                             \
     RG_REQUIRE(code__ != RAGRAPH_EUNSUPPORTED, RAGRAPH_EUNSUPPORTED, who ": D=%d not in {64,128,256}", D);           \
     RG_REQUIRE(code__ == RAGRAPH_OK, RAGRAPH_EINVAL, who ": bad B/N/k");                                              \
   } while (0)
@@ -425,9 +427,9 @@ extern "C" int ragraph_topk_cosine_filtered_i8_levels(int64_t B, int64_t N, int 
   return filter_call_plan(in, filter_schedule(in)).i8_levels;
 }
 
-static int filter_plan_query(int64_t B, int64_t N, int D, int k, int64_t plan[7], bool wide) {
+static int filter_plan_query(int64_t B, int64_t N, int D, int k, int64_t plan[7], int lw) {
   RG_REQUIRE(plan, RAGRAPH_EINVAL, "topk_cosine_filtered_plan: null pointer");
-  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered_plan", B, N, D, k, wide);
+  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered_plan", B, N, D, k, lw);
   FilterShape in = filter_query_shape(B, N, D, k, 1, false);
   filter_query_follow_tight(in);
   // (the plan of one whole bank IS its schedule: filter_schedule leaves such a bank bound_keys <= N / 4 or <= ends[0] < N / 2
@@ -441,19 +443,38 @@ static int filter_plan_query(int64_t B, int64_t N, int D, int k, int64_t plan[7]
   return c.nlev;
 }
 extern "C" int ragraph_topk_cosine_filtered_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]) {
-  return filter_plan_query(B, N, D, k, plan, false);
+  return filter_plan_query(B, N, D, k, plan, 32);
 }
 // The wide entry's queries (33 <= k <= 64): the same plan words, the same workspace layout -- the lists of the fixup scan
 // keep their size (half the slices of twice the winners), every other buffer is sized by k as ever.
 extern "C" int ragraph_topk_cosine_filtered_wide_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]) {
-  return filter_plan_query(B, N, D, k, plan, true);
+  return filter_plan_query(B, N, D, k, plan, 64);
 }
 extern "C" size_t ragraph_topk_cosine_filtered_wide_workspace_bytes(int64_t B, int64_t N, int D, int k) {
-  if (filter_shape_code(B, N, D, k, true) != RAGRAPH_OK) return 0;
+  if (filter_shape_code(B, N, D, k, 64) != RAGRAPH_OK) return 0;
   // never less than the same shape needs at k = 32 (a handful of queries keep 8 sub-lists per query while 8 k <= 256 and 4
   // beyond: the lists alone would make k = 33 the smaller call): a buffer sized for a wide call serves every shorter list
   const size_t own = filter_workspace_bytes(B, N, D, k, 1), narrow = N >= 32 ? filter_workspace_bytes(B, N, D, 32, 1) : 0;
   return own > narrow ? own : narrow;
+}
+// The wide128 entry's queries (65 <= k <= 128): the same again -- the fixup scan keeps a quarter of the slices of four times
+// the winners; never less than the wide entry needs for the same shape at k = 64.
+extern "C" int ragraph_topk_cosine_filtered_wide128_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]) {
+  return filter_plan_query(B, N, D, k, plan, 128);
+}
+// How many trailing levels of that plan run on the int8 copy (under the calling thread's cap, like
+// ragraph_topk_cosine_filtered_i8_levels for k <= 32; 0 for a shape the entry refuses).
+extern "C" int ragraph_topk_cosine_filtered_wide128_i8_levels(int64_t B, int64_t N, int D, int k) {
+  if (filter_shape_code(B, N, D, k, 128) != RAGRAPH_OK) return 0;
+  FilterShape in = filter_query_shape(B, N, D, k, 1, false);
+  in.i8_cap = t_max_i8_levels;
+  filter_query_follow_tight(in);
+  return filter_call_plan(in, filter_schedule(in)).i8_levels;
+}
+extern "C" size_t ragraph_topk_cosine_filtered_wide128_workspace_bytes(int64_t B, int64_t N, int D, int k) {
+  if (filter_shape_code(B, N, D, k, 128) != RAGRAPH_OK) return 0;
+  const size_t own = filter_workspace_bytes(B, N, D, k, 1), wide = ragraph_topk_cosine_filtered_wide_workspace_bytes(B, N, D, 64);
+  return own > wide ? own : wide;
 }
 
 // Would a sharded call of this shape speculate under a prior?  (Any valid one: the answer is the plan's, not the value's.)
@@ -691,19 +712,35 @@ static int run_rescore(const FilterWs& f, const float* Kn, int64_t N, int64_t B,
                      cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx, overflow, f.overflow_list, f.flag, PART_S_, \
                      PART_I_, cstat)
 #define RG_COOP(FEW_)                                                                                                            \
-  hipLaunchKernelGGL((topk_rescore_coop_kernel<D, 32, FEW_>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,    \
+  hipLaunchKernelGGL((topk_rescore_coop_kernel<D, 32, FEW_, (LW > 64 ? 128 : 64)>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,    \
                      f.cand, B, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx, overflow, f.overflow_list,       \
                      f.flag, scan_n, cstat)
   switch (kind) {
-    case RESCORE_SCORED_SMALL: RG_SCORED(true); break;
-    case RESCORE_SCORED: RG_SCORED(false); break;
+    case RESCORE_SCORED_SMALL:
+    case RESCORE_SCORED:
+      if constexpr (LW <= 64) {
+        if (kind == RESCORE_SCORED_SMALL) RG_SCORED(true);
+        else RG_SCORED(false);
+      } else {  // (filter_scored_lists refuses k > 64: no plan asks for this)
+        set_error("topk_cosine_filtered: no scored rescoring for lists of more than 64 keys");
+        return RAGRAPH_EUNSUPPORTED;
+      }
+      break;
     case RESCORE_WIDE_SLICED:
       RG_WIDE(true, true, dim3((unsigned)B, (unsigned)rescore_slices(B, k)), f.part_s, f.part_i);
       wide_timing_report();
       break;
     case RESCORE_WIDE_COOP: RG_WIDE(false, true, dim3((unsigned)B), (float*)nullptr, (int*)nullptr); break;
     case RESCORE_WIDE: RG_WIDE(false, false, dim3((unsigned)B), (float*)nullptr, (int*)nullptr); break;
-    case RESCORE_COOP_FEW: RG_COOP(true); break;
+    case RESCORE_COOP_FEW:   // (the later levels of a sharded bank: no wide128 call is sharded, and at this kernel's 128
+                             // registers the two-entries-per-lane form would spill)
+      if constexpr (LW <= 64) {
+        RG_COOP(true);
+      } else {
+        set_error("topk_cosine_filtered: no 16-row rescoring for lists of more than 64 keys");
+        return RAGRAPH_EUNSUPPORTED;
+      }
+      break;
     case RESCORE_COOP: RG_COOP(false); break;
   }
 #undef RG_SCORED
@@ -845,7 +882,7 @@ static int run_tight_repair(const FilteredArgs& a, const FilterCall& c, const Fi
   rc = run_rescore<D, LW>(r.f, a.Kn, N, FILTER_REPAIR_Q, FILTER_LIST_CAP, k, 0, 0, 0, r.out_s, r.out_i, r.dummy,
                       rescore_kind(FILTER_REPAIR_Q, k, c.repair_scored, false), thr2, nullptr, st);
   if (rc != RAGRAPH_OK) return rc;
-  hipLaunchKernelGGL(filter_repair_scatter_kernel, dim3(FILTER_REPAIR_Q), dim3(64), 0, st, r.list, r.out_s, r.out_i, r.f.flag, k,
+  hipLaunchKernelGGL((filter_repair_scatter_kernel<(LW > 64 ? 128 : 64)>), dim3(FILTER_REPAIR_Q), dim3(64), 0, st, r.list, r.out_s, r.out_i, r.f.flag, k,
                      a.out_scores, a.out_idx, f.flag, stats);
   RG_CHECK_LAUNCH("topk_cosine_filtered(repair scatter)");
   // more than 256: one more level for everybody (proven queries carry theta = +inf)
@@ -958,7 +995,7 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
     thr.gmax = bound ? f.gmax : nullptr;
     thr.prev_scores = out_scores;
     if (bound) {  // k lower bounds of distinct keys' exact scores, descending, where a level leaves its exact top-k
-      hipLaunchKernelGGL(filter_bound_scores_kernel, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, thr, B, out_scores, a.theta);
+      hipLaunchKernelGGL(filter_bound_scores_kernel<2>, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, thr, B, out_scores, a.theta);
       RG_CHECK_LAUNCH("topk_cosine_filtered(theta)");
     } else if ((rc = launch_theta(thr, B, 1, a.theta, st)) != RAGRAPH_OK) {
       return rc;
@@ -967,7 +1004,10 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
     thr.theta = a.theta;
   } else if (bound && c.parts > k) {  // theta = the k-th largest of the part maxima, minus eps
     thr.gmax = f.gmax;
-    hipLaunchKernelGGL(filter_bound_scores_kernel, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, thr, B, (float*)nullptr, f.theta);
+    if constexpr (LW > 64)   // (up to 256 parts: four per lane)
+      hipLaunchKernelGGL(filter_bound_scores_kernel<4>, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, thr, B, (float*)nullptr, f.theta);
+    else
+      hipLaunchKernelGGL(filter_bound_scores_kernel<2>, dim3((unsigned)cdiv(B, 4)), dim3(256), 0, st, thr, B, (float*)nullptr, f.theta);
     RG_CHECK_LAUNCH("topk_cosine_filtered(theta)");
   }
 
@@ -1018,12 +1058,12 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
 // per-call switches are read here and nowhere else.  The schedule (its pow() search) is computed once for a single bank; a
 // shard among several that pool their first sample computes two -- the single bank's, which sizes the minimum workspace,
 // and its own.  filter_call_plan (cheap arithmetic) runs three times: twice for that size, once for the call.
-static int filtered_entry(const FilteredArgs& a, bool wide = false) {
+static int filtered_entry(const FilteredArgs& a, int lw = 32) {
   const int64_t B = a.B, N = a.N, plan_N = a.plan_N;
   const int D = a.D, k = a.k;
   RG_REQUIRE(a.Q && a.Kn && a.Kb && a.out_scores && a.out_idx && a.overflow && a.ws, RAGRAPH_EINVAL, "topk_cosine_filtered: null pointer");
   RG_REQUIRE(a.n_shards >= 1, RAGRAPH_EINVAL, "topk_cosine_filtered: n_shards=%d", a.n_shards);
-  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered", B, N, D, k, wide);
+  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered", B, N, D, k, lw);
   RG_REQUIRE(N < (int64_t)INT_MAX - 1024, RAGRAPH_EUNSUPPORTED, "topk_cosine_filtered: shard rows must fit int32");
   RG_REQUIRE(plan_N >= N && (a.exchange || plan_N - N <= 1024), RAGRAPH_EINVAL, "topk_cosine_filtered: plan_N must be the largest shard's size");
   RG_REQUIRE(!a.exchange || a.theta, RAGRAPH_EINVAL, "topk_cosine_filtered: an exchange needs the theta buffer");
@@ -1038,7 +1078,12 @@ static int filtered_entry(const FilteredArgs& a, bool wide = false) {
   const FilterShape in{B, N, plan_N, D, k, a.n_shards, a.exchange != nullptr, t_prior, t_max_i8_levels, false, one.env, one.cus, t_tight};
   const FilterCall c = filter_call_plan(in, a.exchange && a.n_shards > 1 ? filter_schedule(in) : sc_one);
   if (c.exact_participant) return run_exact_participant(a, c);
-  if (wide) {  // (single bank only: the wide entry has no exchange, so no exact participant either)
+  if (lw == 128) {  // (single bank only, like the wide entry)
+    if (D == 256) return run_filtered<256, 128>(a, c, in);
+    if (D == 128) return run_filtered<128, 128>(a, c, in);
+    return run_filtered<64, 128>(a, c, in);
+  }
+  if (lw == 64) {  // (single bank only: the wide entry has no exchange, so no exact participant either)
     if (D == 256) return run_filtered<256, 64>(a, c, in);
     if (D == 128) return run_filtered<128, 64>(a, c, in);
     return run_filtered<64, 64>(a, c, in);
@@ -1064,7 +1109,17 @@ extern "C" int ragraph_topk_cosine_filtered_wide_f32(const float* Q, int64_t B, 
                                                      float* out_scores, int64_t* out_idx, int* overflow,
                                                      int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream) {
   return filtered_entry({Q, B, Kn, Kp, Kb, N, D, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
-                         N, nullptr, nullptr, nullptr, 1}, true);
+                         N, nullptr, nullptr, nullptr, 1}, 64);
+}
+
+// Lists of 65 .. 128 keys: the same call once more, through the LW = 128 instantiations -- a wave's list holds two entries per
+// lane (rescore_common.h, filter_rescore.h).  Plain lists only.
+extern "C" int ragraph_topk_cosine_filtered_wide128_f32(const float* Q, int64_t B, const float* Kn, const float* Kp,
+                                                        const uint16_t* Kb, int64_t N, int D, int k, int64_t idx_base,
+                                                        float* out_scores, int64_t* out_idx, int* overflow,
+                                                        int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream) {
+  return filtered_entry({Q, B, Kn, Kp, Kb, N, D, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
+                         N, nullptr, nullptr, nullptr, 1}, 128);
 }
 
 extern "C" int ragraph_topk_cosine_filtered_sharded_f32(const float* Q, int64_t B, const float* Kn, const float* Kp,

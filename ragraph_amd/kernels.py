@@ -356,6 +356,35 @@ def filter_wide_helps(B: int, n_keys: int, D: int, k: int) -> bool:
     return B >= (512 if D >= 128 else 2048)
 
 
+def filter_wide128_helps(B: int, n_keys: int, D: int, k: int) -> bool:
+    """filter_helps for lists of 65 .. 128 keys (the wide128 entry behind topk_cosine_filtered): True where the filtered call is
+    the faster way to the bits of topk_cosine, whose fp32 score slabs are all such a k had before.  Host arithmetic only."""
+    if os.environ.get("RAGRAPH_EXACT_FP32") == "1":
+        return False
+    if D not in (64, 128, 256) or not 64 < k <= 128:
+        return False
+    # Kept where tools/filter_wide128_probe.py measured the wide128 call faster than the slabs by more than the spread of the pair
+    # (MI355X, ms per call, slab vs wide128 at k = 65 / 96 / 128; profiles/filter_wide128.txt); what was not measured stays out:
+    #   N >= 1M, D >= 128, every batch size: 100 000 x 1M x 256: 1131 vs 50.0 / 1146 vs 62.4 / 1163 vs 67.4;
+    #     4096 x 1M x 256: 46.9 vs 2.3 / 47.5 vs 2.5 / 48.2 vs 3.0;  256 x 1M: 6.7 - 8.7 times faster;  1 / 16 / 64 x 1M at
+    #     k = 128: 1.30 / 1.46 / 2.00 times faster (k = 65: 2.24 / 2.33 / 2.84);
+    #   65536 <= N < 1M, D >= 128, from 256 queries: 4096 x 200 000 x 128: 9.6 / 7.8 / 6.8 times faster; 600 x 70 000 x 256:
+    #     2.37 / 1.96 / 1.71;  256 x 70 000 x 256: 1.37 / 1.20 / 1.11 (fewer queries on such a bank were not measured);
+    #   D = 64: 4096 x 4M x 64: 72 / 65 / 55 times faster -- but 16 x 70 000 x 64: 0.59 / 0.58 / 0.33, and nothing between
+    #     was measured: only banks of >= 4M keys from 4096 queries;
+    #   32768 <= N < 65536: 2100 x 40 000 x 256: 1.16 / 1.37 / 1.11 times faster, 128 and 64 x 40 000 x 256: 0.84 - 0.51:
+    #     D = 256 from 2048 queries;
+    #   N < 32768: every shape lost (700 x 20 000 x 128: 0.91 / 0.57 / 0.53; 1024 x 10 000 x 256: 0.76 / 0.62 / 0.57;
+    #     8192 x 10 000 x 64: 0.99 / 0.78 / 0.66; 2048 x 20 000 x 64 won by 1.05 at k = 65 alone).
+    if n_keys >= 65536:
+        if D == 64:
+            return B >= 4096 and n_keys >= 4_000_000
+        return B >= (1 if n_keys >= 1_000_000 else 256)
+    if n_keys >= 32768:
+        return D == 256 and B >= 2048
+    return False
+
+
 _EXCHANGE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)
 
 # Candidate statistics of a filtered call: the 16 ints its launches leave at the end of its workspace (include/ragraph_hip.h:
@@ -411,7 +440,10 @@ def topk_cosine_filtered(q: torch.Tensor, keys_normalized: torch.Tensor, keys_bf
     idx = torch.empty((B, k), dtype=torch.int64, device=q.device)
     overflow = torch.empty(1, dtype=torch.int32, device=q.device)
     wide = exchange is None and 32 < k <= 64   # (lists of 33 .. 64 keys: the wide entry -- one path per k)
-    if wide:
+    wide128 = exchange is None and 64 < k <= N.TOPK_FILTER_MAX   # (65 .. 128: the wide128 entry)
+    if wide128:
+        nbytes = L.ragraph_topk_cosine_filtered_wide128_workspace_bytes(B, max(plan_n, Nk), D, k)
+    elif wide:
         nbytes = L.ragraph_topk_cosine_filtered_wide_workspace_bytes(B, max(plan_n, Nk), D, k)
     elif exchange is None:
         nbytes = L.ragraph_topk_cosine_filtered_workspace_bytes(B, max(plan_n, Nk), D, k)
@@ -424,7 +456,8 @@ def topk_cosine_filtered(q: torch.Tensor, keys_normalized: torch.Tensor, keys_bf
     off = L.ragraph_topk_cosine_filtered_stats_offset(ws.numel())
     stats = ws[off:off + 128].view(torch.int32)   # (32 words; valid until the next filtered call on this stream)
     if exchange is None:
-        entry = L.ragraph_topk_cosine_filtered_wide_f32 if wide else L.ragraph_topk_cosine_filtered_f32
+        entry = L.ragraph_topk_cosine_filtered_wide128_f32 if wide128 else (
+            L.ragraph_topk_cosine_filtered_wide_f32 if wide else L.ragraph_topk_cosine_filtered_f32)
         N.check(entry(q.data_ptr(), B, kn.data_ptr(), kp, keys_bf16.data_ptr(), Nk, D, k, idx_base, scores.data_ptr(),
                       idx.data_ptr(), overflow.data_ptr(), None, ws.data_ptr(), ws.numel(), _stream()),
                 "topk_cosine_filtered")

@@ -5,7 +5,7 @@ import os
 
 import torch
 
-from ._native import TOPK_MAX
+from ._native import TOPK_FILTER_MAX, TOPK_MAX
 
 
 class KeyIndex:
@@ -499,12 +499,27 @@ class KeyIndex:
     def _search(self, kn: torch.Tensor, q: torch.Tensor, k: int, idx_base: int = 0, exchange=None, plan_n: int = 0, prior=None):
         """topk over the rows kn: the sealed part (q already at the padded width then), or all rows of a bank without a tail."""
         ops = self.ops
+        wide128 = False
         if k > TOPK_MAX and exchange is None:
-            # ordered large k (exact fp32 score slabs) over the full bank: duplicate rows score alike and the lower row wins,
-            # so no collapse is needed; the prior, counters and pending overflow word are left as they are
+            # Lists of 65 .. 128 keys on one bank of a fused width: the wide128 filtered entry behind ops.topk_cosine_filtered where
+            # the ops' own rule says it pays -- not for a bank searched through its unique rows (topk_expand_groups stops at 64),
+            # a bank with a tail (the bf16 / int8 copy covers the sealed rows only) or one that defeated the filter.
+            rule = None
+            if k <= TOPK_FILTER_MAX and self._width is not None and not self._filter_off and not self._tail_rows:
+                rule = getattr(ops, "filter_wide128_helps", None)
+            if rule is not None:
+                if self._collapsed is None:
+                    self._judge_duplicates()
+                if self._collapsed:
+                    rule = None
+            qp = q
             if self._width is not None and self._width != self.dim:
-                q = ops.pad_cols(q, self._width)
-            return ops.topk_cosine(q, kn, k, idx_base=idx_base)
+                qp = ops.pad_cols(q, self._width)
+            if rule is None or not rule(qp.shape[0], kn.shape[0], qp.shape[1], k):
+                # ordered large k (exact fp32 score slabs) over the full bank: duplicate rows score alike and the lower row wins,
+                # so no collapse is needed; the prior, counters and pending overflow word are left as they are
+                return ops.topk_cosine(qp, kn, k, idx_base=idx_base)
+            wide128 = True   # (the rule has answered: the filtered call below, with its overflow poll, re-probe and learnt bounds)
         if self._width is None:   # wider than every fused kernel: exact score slabs, this shard's own top-k (no exchange needed)
             return ops.topk_cosine(q, kn, k, idx_base=idx_base)
         if self._width != self.dim:
@@ -554,6 +569,8 @@ class KeyIndex:
             # says it pays (an ops object without the rule keeps the fp32 score slabs); everything below -- the overflow poll,
             # the re-probe, the learned bounds per (bank, k) -- applies to it as to k <= 32
             fhelps = getattr(ops, "filter_wide_helps", None)
+        if wide128:
+            fhelps = lambda *_: True   # noqa: E731  (asked above, once per call)
         self._poll_overflow()
         self._maybe_reprobe(B)
         self._queries += B
