@@ -18,7 +18,9 @@
  *   - every dot product (cosine scores, GEMM, SpMM) is ONE fp32 fmaf chain in natural index order starting from
  *     +0 -- exactly what v_mfma_f32_32x32x2_f32 / _16x16x4_f32 compute -- so scores are bit-identical to the oracle
  *     regardless of batch size, tiling, split count or GPU count (one exception: SpMM rows and softmax segments of more
- *     than 4096 entries are summed in blocks of 4096, see "Hub rows" at ragraph_spmm_csr_ws_f32);
+ *     than 4096 entries are summed in blocks of 4096, see "Hub rows" at ragraph_spmm_csr_ws_f32); subnormal sums included.
+ *     "Identical" is as numbers: a chain whose last step underflows to zero from below is -0 in fmaf and has been seen as +0
+ *     out of the MFMA (one output in 33 million of tests/test_gpu_linear_variants.py, the same under every MFMA kernel);
  *   - top-k order is canonical: score descending, then index ascending (torch.topk leaves ties unspecified);
  *   - row L2 norms use the fixed reduction tree documented at ragraph_normalize_rows_f32.
  */
@@ -473,6 +475,20 @@ int ragraph_gather_reduce_mix_f32(const float* V, int D, const float* L, int C, 
  */
 int ragraph_linear_f32(const float* X, int64_t M, int K, const float* W, int64_t N, const float* bias, int act,
                        float alpha, float* Y, void* stream);
+
+/* Which kernel ragraph_linear_f32 runs for a shape, and its launch geometry: host arithmetic only (no HIP call, no device
+ *     query), and the function the dispatcher itself takes its decision and its grid from.  x_aligned16 / w_aligned16: whether
+ *     X / W start on a 16-byte boundary.  plan[0] one of RAGRAPH_LINEAR_PLAN_*; plan[1], plan[2] grid.x, grid.y; plan[3] the
+ *     stages per workgroup of the streaming kernel, the number of 32-wide K chunks for the others.  The variants give the same
+ *     bits; the environment switches RAGRAPH_LINEAR_TILE, _NARROW, _WGS and _MIN_STAGES (A/B diagnostics, read once per
+ *     process) are honoured, so the plan is what this process runs.  RAGRAPH_EINVAL for M, N, K < 1 or a null plan,
+ *     RAGRAPH_EUNSUPPORTED for N beyond one launch (as ragraph_linear_f32). */
+#define RAGRAPH_LINEAR_PLAN_GENERIC 0 /* 64 x 64 block tiles, any shape                                   */
+#define RAGRAPH_LINEAR_PLAN_SMALL 1   /* 32 x 32 block tiles: few blocks, K >= 256                        */
+#define RAGRAPH_LINEAR_PLAN_TILE 2    /* 128 x 128 block tiles: thousands of tiles, K % 4 == 0            */
+#define RAGRAPH_LINEAR_PLAN_STREAM 3  /* M >= 4096 rows streamed past 256-column blocks, K in {64,128,256} */
+#define RAGRAPH_LINEAR_PLAN_NARROW 4  /* M >= 4096, N <= 8, K % 32 == 0, K <= 2048: one row per lane      */
+int ragraph_linear_plan(int64_t M, int K, int64_t N, int x_aligned16, int w_aligned16, int64_t plan[4]);
 
 /* f4 (fine-tuning backward)  C = A^T B for tall row-major operands  -- the weight gradient of a dense layer, gW = gY^T X
  *     (torch autograd of nn.Linear in RAGraph_node/finetune-rag.py:81-84, TaskDecoder.py:15-16; the edge flavour's gating

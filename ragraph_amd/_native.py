@@ -25,6 +25,8 @@ TOPK_MAX = 64                # the fused kernels' list limit (RAGRAPH_TOPK_MAX)
 TOPK_FILTER_MAX = 128        # the filtered calls' (RAGRAPH_TOPK_FILTER_MAX: the wide128 entry)
 TOPK_ORDERED_MAX = 4096      # ordered top-k over exact fp32 score slabs (RAGRAPH_TOPK_ORDERED_MAX)
 TOPK_TAIL_MAX = 65536        # rows one seeded tail pass takes (RAGRAPH_TOPK_TAIL_MAX)
+# plan[0] of ragraph_linear_plan (RAGRAPH_LINEAR_PLAN_*): the kernel ragraph_linear_f32 runs
+LINEAR_GENERIC, LINEAR_SMALL, LINEAR_TILE, LINEAR_STREAM, LINEAR_NARROW = 0, 1, 2, 3, 4
 POSITION_CODES_LDS_MAX = 40000     # nodes one anchor's distance vector may have in LDS (ragraph_position_codes_csr_f32)
 POSITION_CODES_LONG_ROW = 512      # RAGRAPH_POSITION_CODES_LONG_ROW: rows with more edges go to a whole workgroup
 
@@ -93,6 +95,7 @@ SIGNATURES = {
     "ragraph_gather_reduce_f32": (_i32, [_vp, _i32, _vp, _i32, _i64, _vp, _i64, _i32, _i64, _f32, _vp, _vp, _vp]),
     "ragraph_gather_reduce_mix_f32": (_i32, [_vp, _i32, _vp, _i32, _i64, _vp, _i64, _i32, _i64, _f32, _vp, _f32, _f32, _vp, _vp, _vp]),
     "ragraph_linear_f32": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i32, _f32, _vp, _vp]),
+    "ragraph_linear_plan": (_i32, [_i64, _i32, _i64, _i32, _i32, _vp]),
     "ragraph_linear_tn_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "ragraph_linear_tn_f32": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
     "ragraph_spmm_csr_f32": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _f32, _f32, _vp, _vp, _vp]),

@@ -247,7 +247,8 @@ __global__ void __launch_bounds__(256) linear_small_kernel(const float* __restri
 }
 
 // ---- large shapes: 128 x 128 block tile, 4 waves x (64 x 64), K chunks of 32 double-buffered through LDS -----------
-// Used when M >= 128, N >= 128, K % 4 == 0 and the rows are 16-B aligned (the GCN encode of c2: 100k x 128 -> 256).
+// Used from 2048 tiles when M >= 128, N >= 128, K % 4 == 0 and the rows are 16-B aligned (linear_plan below; the large score
+// matrices of the slab paths).
 // Same numerics as linear_kernel (every output is the k = 0..K-1 fmaf chain the MFMA computes, bias added after), so
 // the two kernels are interchangeable bit for bit.  Per wave and K chunk: 4 A-row + 4 B-row ds_read_b128 feed 64 MFMAs
 // (each fragment is used by two tiles); the LDS image is de-interleaved like the top-k kernel's (row = [even k | odd k]
@@ -764,40 +765,18 @@ static int launch_spmm_linear(const int64_t* rowptr, const int32_t* col, const f
   return RAGRAPH_OK;
 }
 
+// (grid and stages per workgroup come from linear_plan below)
 template <int KD>
 static int launch_linear_stream(const float* X, int64_t M, const float* W, int64_t N, const float* bias, int act,
-                                float alpha, float* Y, hipStream_t st) {
+                                float alpha, float* Y, hipStream_t st, dim3 grid, int64_t stages_per_wg) {
   using C = LinStreamCfg<KD>;
   static DeviceOnce lds_once;  // per device (common.h)
   if (hipError_t e = raise_dynamic_lds(lds_once, &linear_stream_kernel<KD>, (int)C::LDS_BYTES); e != hipSuccess) {
     set_error("linear: cannot raise dynamic LDS limit: %s", hipGetErrorString(e));
     return RAGRAPH_EDEVICE;
   }
-  const int64_t total_stages = cdiv(M, C::STAGE_ROWS);
-  const int64_t col_blocks = cdiv(N, 256);
-  // ~2 workgroups per CU in flight (LDS 66 KB, <= 128 VGPRs); at least 4 stages each so the pipeline fills
-  static const int64_t wgs_env = [] {  // RAGRAPH_LINEAR_WGS: A/B of the workgroup count
-    const char* e = getenv("RAGRAPH_LINEAR_WGS");
-    return e ? (int64_t)atoll(e) : (int64_t)0;
-  }();
-  // two workgroups per CU hide each other's latencies on long streams (1M x 128 -> 256: 639 vs 693 us); with a few
-  // stages per CU one workgroup each keeps the CUs evenly loaded (100k x 256 -> 256: 148 vs 168 us; 391 workgroups on
-  // 256 CUs left half of them with twice the work)
-  const int64_t wgs_target = wgs_env > 0 ? wgs_env : (total_stages >= 16 * 256 ? 512 : 256);
-  int64_t wgs = wgs_target / col_blocks;
-  if (wgs < 1) wgs = 1;
-  int64_t per = cdiv(total_stages, wgs);
-  // (a short stream -- a rank's slice of the rows: 12 500 x 128 -> 256 is 196 stages -- used to keep "at least 4 stages per
-  // workgroup so the pipeline fills": 49 workgroups on 256 CUs, 54 us where the whole 100 000-row stream takes 96.  Fewer
-  // stages per workgroup and all CUs busy; RAGRAPH_LINEAR_MIN_STAGES: A/B)
-  static const int64_t min_stages = [] {
-    const char* e = getenv("RAGRAPH_LINEAR_MIN_STAGES");
-    return e ? (int64_t)atoll(e) : (int64_t)1;
-  }();
-  if (per < min_stages) per = min_stages;
-  wgs = cdiv(total_stages, per);
-  hipLaunchKernelGGL(linear_stream_kernel<KD>, dim3((unsigned)wgs, (unsigned)col_blocks), dim3(C::THREADS), C::LDS_BYTES,
-                     st, X, M, W, N, bias, act, alpha, Y, per);
+  hipLaunchKernelGGL(linear_stream_kernel<KD>, grid, dim3(C::THREADS), C::LDS_BYTES, st, X, M, W, N, bias, act, alpha, Y,
+                     stages_per_wg);
   RG_CHECK_LAUNCH("linear(stream)");
   return RAGRAPH_OK;
 }
@@ -909,22 +888,95 @@ extern "C" int ragraph_linear_tn_f32(const float* A, const float* B, int64_t n, 
   return RAGRAPH_OK;
 }
 
+// ---- which kernel, which grid: ONE place (host arithmetic only, no HIP call) -------------------------------------------
+// ragraph_linear_f32 launches what this returns and ragraph_linear_plan reports it, so a test can state which kernel a shape
+// reaches.  The four switches are read once per process and shared by both: the plan is what the process really runs.
+struct LinearEnv {
+  bool tile_ok;        // RAGRAPH_LINEAR_TILE=0: diagnostic switch back to the small-tile kernels (no tile, no stream kernel)
+  bool narrow_ok;      // RAGRAPH_LINEAR_NARROW=0: the MFMA tiles instead of the row-streaming kernel, A/B
+  int64_t wgs;         // RAGRAPH_LINEAR_WGS: A/B of the streaming kernel's workgroup count (0: the rule below)
+  int64_t min_stages;  // RAGRAPH_LINEAR_MIN_STAGES: A/B of its stages per workgroup
+};
+static const LinearEnv& linear_env() {
+  static const LinearEnv env = [] {
+    LinearEnv v;
+    const char* e = getenv("RAGRAPH_LINEAR_TILE");
+    v.tile_ok = !(e && atoi(e) == 0);
+    e = getenv("RAGRAPH_LINEAR_NARROW");
+    v.narrow_ok = !(e && atoi(e) == 0);
+    e = getenv("RAGRAPH_LINEAR_WGS");
+    v.wgs = e ? (int64_t)atoll(e) : (int64_t)0;
+    e = getenv("RAGRAPH_LINEAR_MIN_STAGES");
+    v.min_stages = e ? (int64_t)atoll(e) : (int64_t)1;
+    return v;
+  }();
+  return env;
+}
+
+// plan[0] variant, plan[1] x plan[2] the grid, plan[3] stages per workgroup (stream) or 32-wide K chunks (the others).
+// M, N, K >= 1 and cdiv(N, LBN) <= 65535 are the caller's to check.
+static void linear_plan(int64_t M, int K, int64_t N, bool x_aligned, bool w_aligned, int64_t plan[4]) {
+  const LinearEnv& env = linear_env();
+  // tall X, a handful of output columns: the row-streaming kernel
+  if (env.narrow_ok && N <= NARROW_MAX_N && M >= 4096 && K % NARROW_KC == 0 && K <= 2048 && x_aligned) {
+    plan[0] = RAGRAPH_LINEAR_PLAN_NARROW, plan[1] = cdiv(M, 256), plan[2] = 1, plan[3] = K / NARROW_KC;
+    return;
+  }
+  // tall X against blocks of 256 columns; the last block's idle waves must stay under 25 % of all of them
+  if (env.tile_ok && M >= 4096 && (K == 64 || K == 128 || K == 256) && x_aligned && w_aligned &&
+      4 * N >= 3 * 256 * cdiv(N, 256) && cdiv(N, 256) <= 65535) {
+    const int64_t total_stages = cdiv(M, 32 * (256 / K));   // LinStreamCfg<K>::STAGE_ROWS
+    const int64_t col_blocks = cdiv(N, 256);
+    // two workgroups per CU hide each other's latencies on long streams (1M x 128 -> 256: 639 vs 693 us); with a few
+    // stages per CU one workgroup each keeps the CUs evenly loaded (100k x 256 -> 256: 148 vs 168 us; 391 workgroups on
+    // 256 CUs left half of them with twice the work)
+    const int64_t wgs_target = env.wgs > 0 ? env.wgs : (total_stages >= 16 * 256 ? 512 : 256);
+    int64_t wgs = wgs_target / col_blocks;
+    if (wgs < 1) wgs = 1;
+    int64_t per = cdiv(total_stages, wgs);
+    // (a short stream -- a rank's slice of the rows: 12 500 x 128 -> 256 is 196 stages -- used to keep "at least 4 stages per
+    // workgroup so the pipeline fills": 49 workgroups on 256 CUs, 54 us where the whole 100 000-row stream takes 96.  Fewer
+    // stages per workgroup and all CUs busy)
+    if (per < env.min_stages) per = env.min_stages;
+    plan[0] = RAGRAPH_LINEAR_PLAN_STREAM, plan[1] = cdiv(total_stages, per), plan[2] = col_blocks, plan[3] = per;
+    return;
+  }
+  // (up to a few waves of 128 x 128 tiles the 64 x 64 kernel -- four times the workgroups, next chunk in flight under
+  // the MFMAs -- is as fast or faster: 2708 x 128 -> 128: 30 -> 10 us; 600 x 256 -> 20000: 124 -> 103; 300 x 256 ->
+  // 5000: 39 -> 20; equal from ~1000 tiles, and the tile kernel wins on large problems: 4096 x 256 -> 125000: 112 TF)
+  if (env.tile_ok && M >= TBM && N >= TBN && K % 4 == 0 && x_aligned && w_aligned && cdiv(M, TBM) * cdiv(N, TBN) >= 2048) {
+    plan[0] = RAGRAPH_LINEAR_PLAN_TILE, plan[1] = cdiv(M, TBM), plan[2] = cdiv(N, TBN), plan[3] = cdiv(K, TKC);
+    return;
+  }
+  // few 64 x 64 blocks and a long K: the chain of dependent MFMAs per wave is what the launch costs -- quarter-size tiles
+  if (cdiv(M, LBM) * cdiv(N, LBN) <= 192 && K >= 256 && cdiv(N, SBN) <= 65535) {
+    plan[0] = RAGRAPH_LINEAR_PLAN_SMALL, plan[1] = cdiv(M, SBM), plan[2] = cdiv(N, SBN), plan[3] = cdiv(K, LKC);
+    return;
+  }
+  plan[0] = RAGRAPH_LINEAR_PLAN_GENERIC, plan[1] = cdiv(M, LBM), plan[2] = cdiv(N, LBN), plan[3] = cdiv(K, LKC);
+}
+
+extern "C" int ragraph_linear_plan(int64_t M, int K, int64_t N, int x_aligned16, int w_aligned16, int64_t plan[4]) {
+  RG_REQUIRE(plan, RAGRAPH_EINVAL, "linear_plan: null pointer");
+  RG_REQUIRE(M >= 1 && N >= 1 && K >= 1, RAGRAPH_EINVAL, "linear_plan: M,N,K must be >= 1");
+  RG_REQUIRE(cdiv(N, LBN) <= 65535, RAGRAPH_EUNSUPPORTED, "linear_plan: N=%lld too large for one launch", (long long)N);
+  linear_plan(M, K, N, x_aligned16 != 0, w_aligned16 != 0, plan);
+  return RAGRAPH_OK;
+}
+
 extern "C" int ragraph_linear_f32(const float* X, int64_t M, int K, const float* W, int64_t N, const float* bias,
                                   int act, float alpha, float* Y, void* stream) {
   RG_REQUIRE(X && W && Y, RAGRAPH_EINVAL, "linear: null pointer");
   RG_REQUIRE(M >= 1 && N >= 1 && K >= 1, RAGRAPH_EINVAL, "linear: M,N,K must be >= 1");
   RG_REQUIRE(act >= RAGRAPH_ACT_NONE && act <= RAGRAPH_ACT_ELU, RAGRAPH_EINVAL, "linear: bad act %d", act);
   RG_REQUIRE(cdiv(N, LBN) <= 65535, RAGRAPH_EUNSUPPORTED, "linear: N=%lld too large for one launch", (long long)N);
-  static const bool tile_ok = [] {  // RAGRAPH_LINEAR_TILE=0: diagnostic switch back to the small-tile kernel (read once)
-    const char* e = getenv("RAGRAPH_LINEAR_TILE");
-    return !(e && atoi(e) == 0);
-  }();
-  // tall X, a handful of output columns: the row-streaming kernel (RAGRAPH_LINEAR_NARROW=0: the MFMA tiles, A/B)
-  static const bool narrow_ok = [] { const char* e = getenv("RAGRAPH_LINEAR_NARROW"); return !(e && atoi(e) == 0); }();
-  if (narrow_ok && N <= NARROW_MAX_N && M >= 4096 && K % NARROW_KC == 0 && K <= 2048 && aligned16(X)) {
-    const size_t lds = sizeof(float) * ((size_t)N * K + 4 * 64 * NARROW_LD);
-    dim3 grid((unsigned)cdiv(M, 256));
-    hipStream_t st = as_stream(stream);
+  int64_t plan[4];
+  linear_plan(M, K, N, aligned16(X), aligned16(W), plan);
+  const dim3 grid((unsigned)plan[1], (unsigned)plan[2]);
+  hipStream_t st = as_stream(stream);
+  switch ((int)plan[0]) {
+    case RAGRAPH_LINEAR_PLAN_NARROW: {
+      const size_t lds = sizeof(float) * ((size_t)N * K + 4 * 64 * NARROW_LD);
 #define RG_NARROW(NN_)                                                                                                    \
   case NN_: {                                                                                                               \
     static DeviceOnce once;                                                                                                 \
@@ -936,48 +988,37 @@ extern "C" int ragraph_linear_f32(const float* X, int64_t M, int K, const float*
     hipLaunchKernelGGL(linear_narrow_kernel<NN_>, grid, dim3(256), lds, st, X, M, K, W, bias, act, alpha, Y);               \
     break;                                                                                                                  \
   }
-    switch ((int)N) {
-      RG_NARROW(1) RG_NARROW(2) RG_NARROW(3) RG_NARROW(4) RG_NARROW(5) RG_NARROW(6) RG_NARROW(7) RG_NARROW(8)
-    }
+      switch ((int)N) {
+        RG_NARROW(1) RG_NARROW(2) RG_NARROW(3) RG_NARROW(4) RG_NARROW(5) RG_NARROW(6) RG_NARROW(7) RG_NARROW(8)
+      }
 #undef RG_NARROW
-    RG_CHECK_LAUNCH("linear(narrow)");
-    return RAGRAPH_OK;
-  }
-  // tall X against blocks of 256 columns; the last block's idle waves must stay under 25 % of all of them
-  if (tile_ok && M >= 4096 && (K == 64 || K == 128 || K == 256) && aligned16(X) && aligned16(W) &&
-      4 * N >= 3 * 256 * cdiv(N, 256) && cdiv(N, 256) <= 65535) {
-    hipStream_t st = as_stream(stream);
-    return K == 256 ? launch_linear_stream<256>(X, M, W, N, bias, act, alpha, Y, st)
-           : K == 128 ? launch_linear_stream<128>(X, M, W, N, bias, act, alpha, Y, st)
-                      : launch_linear_stream<64>(X, M, W, N, bias, act, alpha, Y, st);
-  }
-  // (up to a few waves of 128 x 128 tiles the 64 x 64 kernel -- four times the workgroups, next chunk in flight under
-  // the MFMAs -- is as fast or faster: 2708 x 128 -> 128: 30 -> 10 us; 600 x 256 -> 20000: 124 -> 103; 300 x 256 ->
-  // 5000: 39 -> 20; equal from ~1000 tiles, and the tile kernel wins on large problems: 4096 x 256 -> 125000: 112 TF)
-  if (tile_ok && M >= TBM && N >= TBN && K % 4 == 0 && aligned16(X) && aligned16(W) &&
-      cdiv(M, TBM) * cdiv(N, TBN) >= 2048) {
-    const size_t lds = sizeof(float) * 4 * TBM * TLD;
-    static DeviceOnce lds_once;  // per device (common.h)
-    if (hipError_t e = raise_dynamic_lds(lds_once, &linear_tile_kernel, (int)lds); e != hipSuccess) {
-      set_error("linear: cannot raise dynamic LDS limit: %s", hipGetErrorString(e));
-      return RAGRAPH_EDEVICE;
+      RG_CHECK_LAUNCH("linear(narrow)");
+      return RAGRAPH_OK;
     }
-    dim3 grid((unsigned)cdiv(M, TBM), (unsigned)cdiv(N, TBN));
-    hipLaunchKernelGGL(linear_tile_kernel, grid, dim3(256), lds, as_stream(stream), X, M, K, W, N, bias, act, alpha, Y);
-    RG_CHECK_LAUNCH("linear(tile)");
-    return RAGRAPH_OK;
+    case RAGRAPH_LINEAR_PLAN_STREAM:
+      return K == 256 ? launch_linear_stream<256>(X, M, W, N, bias, act, alpha, Y, st, grid, plan[3])
+             : K == 128 ? launch_linear_stream<128>(X, M, W, N, bias, act, alpha, Y, st, grid, plan[3])
+                        : launch_linear_stream<64>(X, M, W, N, bias, act, alpha, Y, st, grid, plan[3]);
+    case RAGRAPH_LINEAR_PLAN_TILE: {
+      const size_t lds = sizeof(float) * 4 * TBM * TLD;
+      static DeviceOnce lds_once;  // per device (common.h)
+      if (hipError_t e = raise_dynamic_lds(lds_once, &linear_tile_kernel, (int)lds); e != hipSuccess) {
+        set_error("linear: cannot raise dynamic LDS limit: %s", hipGetErrorString(e));
+        return RAGRAPH_EDEVICE;
+      }
+      hipLaunchKernelGGL(linear_tile_kernel, grid, dim3(256), lds, st, X, M, K, W, N, bias, act, alpha, Y);
+      RG_CHECK_LAUNCH("linear(tile)");
+      return RAGRAPH_OK;
+    }
+    case RAGRAPH_LINEAR_PLAN_SMALL:
+      hipLaunchKernelGGL(linear_small_kernel, grid, dim3(256), 0, st, X, M, K, W, N, bias, act, alpha, Y);
+      RG_CHECK_LAUNCH("linear(small)");
+      return RAGRAPH_OK;
+    default:
+      hipLaunchKernelGGL(linear_kernel, grid, dim3(256), 0, st, X, M, K, W, N, bias, act, alpha, Y);
+      RG_CHECK_LAUNCH("linear");
+      return RAGRAPH_OK;
   }
-  // few 64 x 64 blocks and a long K: the chain of dependent MFMAs per wave is what the launch costs -- quarter-size tiles
-  if (cdiv(M, LBM) * cdiv(N, LBN) <= 192 && K >= 256 && cdiv(N, SBN) <= 65535) {
-    dim3 grid((unsigned)cdiv(M, SBM), (unsigned)cdiv(N, SBN));
-    hipLaunchKernelGGL(linear_small_kernel, grid, dim3(256), 0, as_stream(stream), X, M, K, W, N, bias, act, alpha, Y);
-    RG_CHECK_LAUNCH("linear(small)");
-    return RAGRAPH_OK;
-  }
-  dim3 grid((unsigned)cdiv(M, LBM), (unsigned)cdiv(N, LBN));
-  hipLaunchKernelGGL(linear_kernel, grid, dim3(256), 0, as_stream(stream), X, M, K, W, N, bias, act, alpha, Y);
-  RG_CHECK_LAUNCH("linear");
-  return RAGRAPH_OK;
 }
 
 // a4, inference association (A_hat X) W^T in one launch  -- layers/gcn.py:36-40 (a layer at most half as

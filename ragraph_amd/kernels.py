@@ -5,6 +5,7 @@ All functions require CUDA(=ROCm) tensors and raise `RagraphNativeError` otherwi
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 
@@ -12,6 +13,7 @@ import torch
 
 from . import _native as N
 from ._native import ACT_ELU, ACT_LEAKY, ACT_NONE, ACT_PRELU, ACT_RELU, RagraphNativeError  # noqa: F401
+from ._native import LINEAR_GENERIC, LINEAR_NARROW, LINEAR_SMALL, LINEAR_STREAM, LINEAR_TILE  # noqa: F401
 
 _device_ok = False
 
@@ -797,6 +799,21 @@ def linear(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor | None = No
         N.check(L.ragraph_linear_f32(x2.data_ptr(), x2.shape[0], x2.shape[1], w.data_ptr(), w.shape[0], _ptr(b), act,
                                      float(alpha), y.data_ptr(), _stream()), "linear")
     return y.reshape(tuple(lead) + (w.shape[0],))
+
+
+LINEAR_VARIANTS = {LINEAR_GENERIC: "generic", LINEAR_SMALL: "small", LINEAR_TILE: "tile", LINEAR_STREAM: "stream",
+                   LINEAR_NARROW: "narrow"}
+LinearPlan = collections.namedtuple("LinearPlan", "variant grid_x grid_y steps")
+
+
+def linear_plan(M: int, K: int, N_: int, x_aligned: bool = True, w_aligned: bool = True) -> LinearPlan:
+    """The kernel `linear` runs for x [M, K] against weight [N_, K], and its launch (ragraph_linear_plan: host arithmetic, no
+    device needed; the dispatcher takes its decision from the same function).  variant: one of LINEAR_* (names in
+    LINEAR_VARIANTS); grid_x, grid_y; steps: the stages per workgroup of the streaming kernel, else the 32-wide K chunks.
+    x_aligned / w_aligned: whether the operand starts on a 16-byte boundary (data_ptr() % 16 == 0)."""
+    plan = (ctypes.c_int64 * 4)()
+    N.check(N.lib().ragraph_linear_plan(M, K, N_, int(bool(x_aligned)), int(bool(w_aligned)), plan), "linear_plan")
+    return LinearPlan(*(int(v) for v in plan))
 
 
 def linear_tn(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

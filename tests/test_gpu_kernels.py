@@ -226,16 +226,20 @@ def test_gather_reduce_mix_is_reduce_then_axpby(dev, D, k):
 
 @pytest.mark.parametrize("M,K_,N_,act", [(1, 1, 1, 0), (33, 18, 256, 2), (200, 1433, 256, 0), (130, 256, 3, 3),
                                          (65, 256, 256, 3), (64, 64, 64, 1),
-                                         # the 128 x 128 tile kernel (M, N >= 128, K % 4 == 0): ragged tiles, K not a
-                                         # multiple of the 32-wide chunk, one chunk, many chunks
+                                         # the 64 x 64 and 32 x 32 kernels (the 128 x 128 tile kernel starts at 2048 tiles:
+                                         # tests/test_gpu_linear_variants.py): ragged tiles, K not a multiple of the 32-wide
+                                         # chunk, one chunk, many chunks
                                          (300, 128, 256, 2), (129, 36, 130, 1), (128, 4, 128, 0), (1000, 260, 384, 3),
                                          (257, 1000, 129, 0), (2708, 1433, 128, 2), (31, 257, 17, 3),
-                                         # the streaming kernel (M >= 4096, K in {64,128,256}, N in (192,256] per block)
+                                         # the streaming kernel (M >= 4096, K in {64,128,256}, N in [192,256] per block), one
+                                         # stage per workgroup (longer pipelines: tests/test_gpu_linear_variants.py)
                                          (4096, 128, 256, 2), (4133, 256, 250, 3), (5000, 64, 512, 0), (4100, 128, 700, 1),
                                          (9000, 128, 193, 2)])
 def test_linear_bit_exact(dev, M, K_, N_, act):
     from ragraph_amd import kernels as K
 
+    if M >= 4096:
+        assert K.linear_plan(M, K_, N_).variant == K.LINEAR_STREAM
     rng = _rng(M + K_ + N_)
     X = rng.standard_normal((M, K_), dtype=np.float32)
     W = (rng.standard_normal((N_, K_), dtype=np.float32) / np.sqrt(K_)).astype(np.float32)
