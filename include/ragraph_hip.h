@@ -129,9 +129,9 @@ int ragraph_topk_cosine_bank_f32(const float* Q, int64_t B, const float* Kn, con
  *   Everything else (other widths, 32 < k, small score matrices, banks beyond one dense launch) takes
  *       materialised slabs inside ~1 GiB of the workspace in key chunks: dense kernel x 2, mix, ordered selection,
  *       canonical merge -- the same bits.  (Banks beyond one dense launch with 64 < k: a merged score of -0 reads +0.)
- *   RAGRAPH_EINVAL before anything touches the device: null pointer, A outside 1..16, k outside its range, a weight that is not finite,
- *   ws_bytes < ragraph_topk_cosine_mix_workspace_bytes().  RAGRAPH_EUNSUPPORTED: shards of >= 2^31 rows.  The call never
- *   synchronises or reads back and can be captured into a HIP graph.
+ *   RAGRAPH_EINVAL before anything touches the device: null pointer, A outside 1..16, k outside its range, a weight that is not
+ *   finite.  RAGRAPH_EWORKSPACE, also before anything touches the device: ws_bytes < ragraph_topk_cosine_mix_workspace_bytes().
+ *   RAGRAPH_EUNSUPPORTED: shards of >= 2^31 rows.  The call never synchronises or reads back and can be captured into a HIP graph.
  */
 size_t ragraph_topk_cosine_mix_workspace_bytes(int64_t B, int64_t N, int D, int A, int k);
 int ragraph_topk_cosine_mix_f32(const float* Q, int64_t B, const float* Kn, int64_t N, int D, const float* Pq,

@@ -657,7 +657,7 @@ extern "C" int ragraph_proto_cosine_grad_proto_f32(const float* emb, int64_t G, 
   RG_REQUIRE(D >= 1 && mode >= 0 && mode <= 2, RAGRAPH_EINVAL, "proto_cosine_grad_proto: bad D/mode");
   RG_REQUIRE((int64_t)C * D <= 8192, RAGRAPH_EUNSUPPORTED, "proto_cosine_grad_proto: C * D = %lld > 8192 (LDS accumulators)",
              (long long)C * D);
-  RG_REQUIRE(workspace_bytes >= ragraph_proto_cosine_grad_proto_workspace_bytes(G, C, D), RAGRAPH_EINVAL,
+  RG_REQUIRE(workspace_bytes >= ragraph_proto_cosine_grad_proto_workspace_bytes(G, C, D), RAGRAPH_EWORKSPACE,
              "proto_cosine_grad_proto: workspace of %zu bytes is too small", workspace_bytes);
   hipStream_t st = as_stream(stream);
   const int64_t blocks = G > 0 ? cdiv(G, 256) : 0;

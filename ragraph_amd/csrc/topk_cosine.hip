@@ -1537,7 +1537,7 @@ extern "C" int ragraph_topk_cosine_mix_f32(const float* Q, int64_t B, const floa
   if (takes_slabs(B, N, D, k)) {
     // materialised slabs: dense kernel x 2, mix, selection, canonical merge over key chunks
     const SlabLayout m = slab_layout(B, N, D, k, Flavour::Mix, A);
-    RG_REQUIRE(ws_bytes >= m.total, RAGRAPH_EINVAL, "topk_cosine_mix: workspace %zu < %zu", ws_bytes, m.total);
+    RG_REQUIRE(ws_bytes >= m.total, RAGRAPH_EWORKSPACE, "topk_cosine_mix: workspace %zu < %zu", ws_bytes, m.total);
     int rc = slab_merge_check("topk_cosine_mix", m, k);
     if (rc != RAGRAPH_OK) return rc;
     float* Qn = reinterpret_cast<float*>(w + m.qn);
@@ -1562,7 +1562,7 @@ extern "C" int ragraph_topk_cosine_mix_f32(const float* Q, int64_t B, const floa
 
   const TopkPlan pl = plan_topk(B, N, D, k);
   const FusedLayout m = fused_layout(pl, Flavour::Mix, B, A);
-  RG_REQUIRE(ws_bytes >= m.total, RAGRAPH_EINVAL, "topk_cosine_mix: workspace %zu < %zu", ws_bytes, m.total);
+  RG_REQUIRE(ws_bytes >= m.total, RAGRAPH_EWORKSPACE, "topk_cosine_mix: workspace %zu < %zu", ws_bytes, m.total);
   float* Qn = reinterpret_cast<float*>(w + m.qn);
   float* Pqn = reinterpret_cast<float*>(w + m.pqn);
   const bool streaming = use_streaming(B, k, D);

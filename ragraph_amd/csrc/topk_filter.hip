@@ -1055,9 +1055,10 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
 }
 
 // Steps 1 and 2 of a call: validate, plan, and hand the plan to whoever executes it.  The thread's prior and int8 cap and the
-// per-call switches are read here and nowhere else.  The schedule (its pow() search) is computed once for a single bank; a
-// shard among several that pool their first sample computes two -- the single bank's, which sizes the minimum workspace,
-// and its own.  filter_call_plan (cheap arithmetic) runs three times: twice for that size, once for the call.
+// per-call switches are read here and nowhere else.  The schedule (its pow() search) is computed once for a single bank of
+// up to 32 keys a list; a shard among several that pool their first sample computes the pooled one as well -- for the size its
+// query reports, and again as the call's own; the wide entry one more (k = 32) and the wide128 entry two more (k = 32, 64) for
+// the sizes their queries cover.  filter_call_plan (cheap arithmetic) runs twice per size, once for the call.
 static int filtered_entry(const FilteredArgs& a, int lw = 32) {
   const int64_t B = a.B, N = a.N, plan_N = a.plan_N;
   const int D = a.D, k = a.k;
@@ -1073,7 +1074,20 @@ static int filtered_entry(const FilteredArgs& a, int lw = 32) {
   // unless the call is one of several shards that pool their first sample
   const FilterShape one = filter_query_shape(B, plan_N, D, k, 1, false);
   const FilterSchedule sc_one = filter_schedule(one);
-  const size_t need = filter_workspace_bytes(one, sc_one);
+  size_t need = filter_workspace_bytes(one, sc_one);
+  // an entry refuses whatever is shorter than ITS OWN size query reports, whichever schedule this call runs.  `need` is the
+  // "own" term of each of those queries; only their other terms are computed here: the wide entries' shorter lists of the same
+  // shape (one more schedule at k = 32, wide128 another at k = 64), the sharded entry's pooled schedule (n_shards > 1: one more)
+  // and a short shard's exact top-k (arithmetic).  The entry for k <= 32 without an exchange computes nothing more.
+  auto at_least = [&](size_t bytes) {
+    if (bytes > need) need = bytes;
+  };
+  if (lw >= 64 && plan_N >= 32) at_least(filter_workspace_bytes(B, plan_N, D, 32, 1));
+  if (lw == 128) at_least(filter_workspace_bytes(B, plan_N, D, 64, 1));
+  if (a.exchange) {
+    if (a.n_shards > 1) at_least(filter_workspace_bytes(B, plan_N, D, k, a.n_shards));
+    at_least(ragraph_topk_cosine_workspace_bytes(B, plan_N, D, k));
+  }
   RG_REQUIRE(a.ws_bytes >= need, RAGRAPH_EWORKSPACE, "topk_cosine_filtered: workspace %zu < %zu", a.ws_bytes, need);
   const FilterShape in{B, N, plan_N, D, k, a.n_shards, a.exchange != nullptr, t_prior, t_max_i8_levels, false, one.env, one.cus, t_tight};
   const FilterCall c = filter_call_plan(in, a.exchange && a.n_shards > 1 ? filter_schedule(in) : sc_one);

@@ -65,8 +65,8 @@ def test_argument_validation_returns_einval_without_a_device():
     assert call(w_struct=float("nan")) == native.EINVAL
     need = lib.ragraph_topk_cosine_mix_workspace_bytes(4, 100, 64, 10, 5)
     assert need > 16
-    assert call(ws_bytes=need - 1) == native.EINVAL and "workspace" in native.last_error()
-    assert call(ws_bytes=16) == native.EINVAL
+    assert call(ws_bytes=need - 1) == native.EWORKSPACE and "workspace" in native.last_error()
+    assert call(ws_bytes=16) == native.EWORKSPACE   # (the code every entry refuses a short workspace with)
 
 
 def _bank(flavour="node", n=12, D=8, C=3, with_positions=True):

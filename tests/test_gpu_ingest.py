@@ -72,16 +72,22 @@ def test_ingestion_kernels_match_host_restatement_at_scale(dev):
     assert np.array_equal(nm.cpu().numpy(), n_ref)
 
 
-@pytest.mark.parametrize("n,bits,val_bytes", [(1, 64, 4), (255, 8, 0), (2049, 17, 8), (100_000, 40, 4), (1_000_003, 64, 8), (4097, 64, 0)])
+# (n at 2048 m +- 1 and the scan's 1024 / 1024^2 level boundaries -- 1024^2 + 1 reaches the third level of sums; bits 1, 8, 9, 64)
+@pytest.mark.parametrize("n,bits,val_bytes", [(1, 64, 4), (255, 8, 0), (2049, 17, 8), (100_000, 40, 4), (1_000_003, 64, 8), (4097, 64, 0),
+                                              (2047, 1, 0), (2049, 9, 4), (4095, 8, 8), (6145, 64, 4), (1024, 9, 0), (1025, 1, 8),
+                                              (1024 * 1024, 8, 4), (1024 * 1024 + 1, 9, 0), (1024 * 1024 - 1, 64, 8)])
 def test_radix_sort_and_scan_match_numpy(dev, n, bits, val_bytes):
     """The library's own stable radix sort (64-bit keys, low `bits` bits, optional 4- / 8-byte values) and prefix sums
     (csrc/sortscan.hip: what ingestion and the duplicate grouping of a bank are built on) against numpy's stable argsort and
-    cumsum; inputs untouched; keys drawn from few values so that stability is what is tested."""
+    cumsum; inputs untouched; keys drawn from few values so that stability is what is tested.  Both run on a temp buffer of
+    exactly the bytes their size queries ask for, between guard bands and pre-filled with 0x00 / 0xFF / 0xA5
+    (tests/guarded_workspace.py): no guard byte changes; one byte short, both refuse with RAGRAPH_EWORKSPACE and write nothing."""
     import ctypes
 
     import numpy as np
     import torch
 
+    import guarded_workspace as GW
     from ragraph_amd import kernels as K
 
     L = K._ready()
@@ -91,27 +97,44 @@ def test_radix_sort_and_scan_match_numpy(dev, n, bits, val_bytes):
     mask = np.uint64((1 << bits) - 1) if bits < 64 else np.uint64(0xFFFFFFFFFFFFFFFF)
     order = np.argsort(keys & mask, kind="stable")
     kd = torch.from_numpy(keys.view(np.int64)).to(dev)
-    ko = torch.empty_like(kd)
     vals = np.arange(n, dtype=np.int64 if val_bytes == 8 else np.int32)
     vd = torch.from_numpy(vals).to(dev) if val_bytes else None
-    vo = torch.empty_like(vd) if val_bytes else None
-    ws = torch.empty(L.ragraph_radix_sort_workspace_bytes(n, val_bytes), dtype=torch.uint8, device=dev)
-    K.N.check(L.ragraph_radix_sort_u64(kd.data_ptr(), ko.data_ptr(), vd.data_ptr() if val_bytes else None,
-                                       vo.data_ptr() if val_bytes else None, val_bytes, n, bits, ws.data_ptr(), ws.numel(), None), "radix_sort")
-    torch.cuda.synchronize()
-    assert np.array_equal(ko.cpu().numpy().view(np.uint64), keys[order])
-    assert np.array_equal(kd.cpu().numpy().view(np.uint64), keys)          # input untouched
-    if val_bytes:
-        assert np.array_equal(vo.cpu().numpy(), vals[order])
     x = rng.integers(0, 7, n).astype(np.int32)
     xd = torch.from_numpy(x).to(dev)
-    out = torch.empty_like(xd)
-    ws2 = torch.empty(L.ragraph_scan_workspace_bytes(n), dtype=torch.uint8, device=dev)
-    for inclusive in (0, 1):
-        K.N.check(L.ragraph_scan_sum_i32(xd.data_ptr(), out.data_ptr(), n, inclusive, ws2.data_ptr(), ws2.numel(), None), "scan")
-        ref = np.cumsum(x, dtype=np.int64)
-        ref = ref if inclusive else ref - x
-        assert np.array_equal(out.cpu().numpy(), ref.astype(np.int32))
+    sort_bytes, scan_bytes = L.ragraph_radix_sort_workspace_bytes(n, val_bytes), L.ragraph_scan_workspace_bytes(n)
+
+    def sort(ws, ko, vo):
+        return L.ragraph_radix_sort_u64(kd.data_ptr(), ko.data_ptr(), vd.data_ptr() if val_bytes else None,
+                                        vo.data_ptr() if val_bytes else None, val_bytes, n, bits, ws.data_ptr(), ws.numel(), None)
+
+    for fill in GW.FILLS:
+        gw = GW.GuardedWorkspace(fill=fill)
+        ko = torch.empty_like(kd)
+        vo = torch.empty_like(vd) if val_bytes else None
+        K.N.check(sort(gw(sort_bytes, dev), ko, vo), "radix_sort")
+        torch.cuda.synchronize()
+        assert np.array_equal(ko.cpu().numpy().view(np.uint64), keys[order])
+        assert np.array_equal(kd.cpu().numpy().view(np.uint64), keys)          # input untouched
+        if val_bytes:
+            assert np.array_equal(vo.cpu().numpy(), vals[order])
+        out = torch.empty_like(xd)
+        ws2 = gw(scan_bytes, dev)
+        for inclusive in (0, 1):
+            K.N.check(L.ragraph_scan_sum_i32(xd.data_ptr(), out.data_ptr(), n, inclusive, ws2.data_ptr(), ws2.numel(), None), "scan")
+            ref = np.cumsum(x, dtype=np.int64)
+            ref = ref if inclusive else ref - x
+            assert np.array_equal(out.cpu().numpy(), ref.astype(np.int32))
+        assert gw.check() == 2, f"fill 0x{fill:02X}"
+    gw = GW.GuardedWorkspace(fill=0xA5, short=True)
+    ko = torch.full_like(kd, -7)
+    out = torch.full_like(xd, -7)
+    if sort_bytes:
+        assert sort(gw(sort_bytes, dev), ko, torch.empty_like(vd) if val_bytes else None) == K.N.EWORKSPACE
+    if scan_bytes:
+        ws2 = gw(scan_bytes, dev)
+        assert L.ragraph_scan_sum_i32(xd.data_ptr(), out.data_ptr(), n, 1, ws2.data_ptr(), ws2.numel(), None) == K.N.EWORKSPACE
+    gw.check()
+    assert gw.interior_untouched() and bool((ko == -7).all()) and bool((out == -7).all())
 
 
 @pytest.mark.parametrize("E,n,sort_cols", [(0, 5, False), (1, 1, True), (1000, 37, False), (1000, 37, True), (300_000, 70_000, False),
