@@ -634,6 +634,28 @@ int ragraph_segment_softmax_ws_f32(const int64_t* rowptr, const float* x, int64_
  *     NOT contracted to an fma, matching the eager reference).  a,b,out [n] elementwise; in-place allowed. */
 int ragraph_axpby_f32(const float* a, float wa, const float* b, float wb, int64_t n, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * a14  the interpolative update of staged fine-tuning  -- RAGraph_edge/finetune_rag.py:63-86
+ *        F.normalize(torch.sum(torch.stack(tables) * w[:, None, None], dim=0), dim=1)
+ *      in ONE pass: the S tables [n,D] are read once, out [n,D] is written, nothing else is allocated or moved:
+ *      (S + 1) * n * D * 4 bytes.
+ *   tables, weights  HOST arrays of S device pointers and S floats.  They are copied into the kernel's arguments, so the
+ *      call makes no device-side pointer table, allocates nothing, does not synchronise and can be captured.
+ *   1 <= S <= RAGRAPH_INTERP_MAX_TABLES (the pre-trained tables + updt_inter saved stages; the largest split has 8 stages).
+ *      Any D >= 1, n >= 0 (n == 0: nothing to do).  out must not be one of the tables.
+ *   Numerics (never contracted to an fma, whatever the build's -ffp-contract):
+ *        acc = T_0[r,d] * w_0;   acc = acc + T_s[r,d] * w_s   for s = 1 .. S-1, in this order;
+ *      then out[r,:] = acc[r,:] / max(||acc[r,:]||_2, 1e-12) with the norm tree documented at ragraph_normalize_rows_f32 and
+ *      correctly rounded sqrtf and division.  The bits of ragraph_axpby_f32(T_0, w_0, T_1, w_1), then
+ *      ragraph_axpby_f32(acc, 1, T_s, w_s) for every further table, then ragraph_normalize_rows_f32.  A mixed row of zeros
+ *      stays zero.  (torch's stacked sum adds in the same order: the unnormalised mix has the reference's bits; the norm's
+ *      summation order is this library's.)
+ *   RAGRAPH_EINVAL, before the device is touched: a null pointer (tables, weights, out, or one of the S tables), S out of
+ *      range, D < 1, n < 0, out equal to a table. */
+#define RAGRAPH_INTERP_MAX_TABLES 8
+int ragraph_interp_normalize_f32(const float* const* tables, const float* weights, int S, int64_t n, int D, float* out,
+                                 void* stream);
+
 /* a8  K5 + K6 of an inference forward in ONE launch  -- RAGraph_node/RAGraph.py:53-57 + ragraph_utils/TaskDecoder.py:14-17:
  *       hidden = query * wq + rag * wr;  logits = fc2(LeakyReLU_slope(fc1(hidden)));
  *       out = softmax(logits) * (1 - lambda) + rag_label * lambda        (rag_label NULL: plain softmax)

@@ -27,6 +27,7 @@ TOPK_ORDERED_MAX = 4096      # ordered top-k over exact fp32 score slabs (RAGRAP
 TOPK_TAIL_MAX = 65536        # rows one seeded tail pass takes (RAGRAPH_TOPK_TAIL_MAX)
 # plan[0] of ragraph_linear_plan (RAGRAPH_LINEAR_PLAN_*): the kernel ragraph_linear_f32 runs
 LINEAR_GENERIC, LINEAR_SMALL, LINEAR_TILE, LINEAR_STREAM, LINEAR_NARROW = 0, 1, 2, 3, 4
+INTERP_MAX_TABLES = 8        # tables one interpolative update mixes (RAGRAPH_INTERP_MAX_TABLES)
 POSITION_CODES_LDS_MAX = 40000     # nodes one anchor's distance vector may have in LDS (ragraph_position_codes_csr_f32)
 POSITION_CODES_LONG_ROW = 512      # RAGRAPH_POSITION_CODES_LONG_ROW: rows with more edges go to a whole workgroup
 
@@ -123,6 +124,7 @@ SIGNATURES = {
     "ragraph_csr_rows_offsets_i64": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
     "ragraph_csr_rows_edges_f32": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "ragraph_axpby_f32": (_i32, [_vp, _f32, _vp, _f32, _i64, _vp, _vp]),
+    "ragraph_interp_normalize_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp]),
     "ragraph_softmax_mix_f32": (_i32, [_vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp]),
     "ragraph_fuse_decode_f32": (_i32, [_vp, _vp, _i64, _i32, _f32, _f32, _vp, _vp, _i32, _f32, _vp, _vp, _i32, _vp, _f32,
                                        _vp, _vp]),

@@ -15,21 +15,69 @@ import numpy as np
 import torch
 
 
-def _read(path, has_time=True):
-    users, items, times = [], [], []
-    per_user = {}
+def _read_lines(path):
+    """The lines of a file in order as [(user, items int64 array, times int64 array)]; a line without a time column gets
+    zero times, a line without items is skipped."""
+    lines = []
     with open(path, "r") as f:
         for line in f:
             parts = line.rstrip("\n").split("\t")
             if len(parts) < 2 or not parts[1]:
                 continue
-            u = int(parts[0])
             it = np.array(parts[1].split(" "), dtype=np.int64)
-            tm = np.array(parts[2].split(" "), dtype=np.int64) if (has_time and len(parts) > 2) else np.zeros_like(it)
-            users.append(np.full(it.shape, u, dtype=np.int64))
-            items.append(it)
-            times.append(tm)
-            per_user[u] = it.tolist()
+            tm = np.array(parts[2].split(" "), dtype=np.int64) if (len(parts) > 2 and parts[2]) else np.zeros_like(it)
+            lines.append((int(parts[0]), it, tm))
+    return lines
+
+
+def _check_unique_users(frame, what):
+    seen = set()
+    for line in frame:
+        if line[0] in seen:
+            raise ValueError(f"{what} names user {line[0]} twice: the reference's pd.merge would multiply its rows "
+                             "(utility.py:23), which is not reproduced")
+        seen.add(line[0])
+
+
+def read_frame(path):
+    """pd.read_csv(path, sep="\t", names=["user", "item", "time"]) (finetune_rag.py:106-114) without pandas: the file's lines
+    in order as a list of (user, items int64 array, times int64 array).  A frame is a table keyed by user: a file that names
+    a user twice raises ValueError."""
+    frame = _read_lines(path)
+    _check_unique_users(frame, str(path))
+    return frame
+
+
+def merge_frames(frames):
+    """utility.py:16-35 merge_pd: a left join on the FIRST frame's users, in its order; per user the items and times of the
+    later frames are appended in frame order; users absent from the first frame are dropped.  A single frame (not a list)
+    is returned as it is (:17-18)."""
+    if not isinstance(frames, list) or (frames and isinstance(frames[0], tuple)):
+        return frames
+    for j, fr in enumerate(frames):
+        _check_unique_users(fr, f"frame {j}")
+    later = [{u: (it, tm) for u, it, tm in fr} for fr in frames[1:]]
+    merged = []
+    for u, it, tm in frames[0]:
+        more = [d[u] for d in later if u in d]
+        merged.append((u, np.concatenate([it] + [m[0] for m in more]), np.concatenate([tm] + [m[1] for m in more])))
+    return merged
+
+
+def _is_frame(x):
+    return isinstance(x, (list, tuple))
+
+
+def _read(source, has_time=True):
+    """A file (path) or a frame (dataloader.py:47-93 _read_file / _read_pd) -> flat (users, items, times) in line order and
+    the per-user dict, in which a user's LAST line stands (:61,85)."""
+    users, items, times = [], [], []
+    per_user = {}
+    for u, it, tm in (source if _is_frame(source) else _read_lines(source)):
+        users.append(np.full(it.shape, u, dtype=np.int64))
+        items.append(it)
+        times.append(tm if has_time else np.zeros_like(it))
+        per_user[u] = it.tolist()
     cat = (lambda xs: np.concatenate(xs) if xs else np.zeros(0, np.int64))
     return cat(users), cat(items), cat(times), per_user
 
@@ -41,10 +89,17 @@ class EdgeListData:
     train_user_dict (the negative sampler's exclusion sets), all on `device`; shuffle() and get_train_batch()."""
 
     def __init__(self, train_file, test_file=None, hour_interval=1, has_time=True, num_users=None, num_items=None,
-                 device="cuda"):
+                 device="cuda", phase="pretrain", pre_dataset=None, user_hist_files=()):
+        """train_file / test_file: a path or a frame (read_frame, merge_frames), as dataloader.py:95-99.
+        pre_dataset: the dataset whose num_users / num_items this one takes (:106-108).
+        phase="finetune" (:36-45,126-135): user_hist_dict -- what an evaluation masks out of the ranking -- is a copy of
+        train_user_dict extended, in file order, by the items of every line of every file of user_hist_files (duplicates
+        kept); train_user_dict itself, the sampler's exclusion sets, is not extended."""
+        if phase not in ("pretrain", "finetune"):
+            raise ValueError(f"phase: 'pretrain' or 'finetune', not {phase!r}")
         u, i, t, train_user_dict = _read(train_file, has_time)
         self._setup(u, i, t, train_user_dict, _read(test_file, False)[3] if test_file else {}, hour_interval, num_users,
-                    num_items, device)
+                    num_items, device, phase, pre_dataset, user_hist_files)
 
     @classmethod
     def from_interactions(cls, users, items, times, test_user_dict=None, hour_interval=1, num_users=None, num_items=None,
@@ -60,16 +115,28 @@ class EdgeListData:
         obj._setup(u, i, t, train_user_dict, dict(test_user_dict or {}), hour_interval, num_users, num_items, device)
         return obj
 
-    def _setup(self, u, i, t, train_user_dict, test_user_dict, hour_interval, num_users, num_items, device):
+    def _setup(self, u, i, t, train_user_dict, test_user_dict, hour_interval, num_users, num_items, device,
+               phase="pretrain", pre_dataset=None, user_hist_files=()):
+        self.phase, self.pre_dataset = phase, pre_dataset
         self.train_user_dict = train_user_dict
         self.test_user_dict = test_user_dict
+        if pre_dataset is not None:                                      # dataloader.py:106-108
+            num_users, num_items = pre_dataset.num_users, pre_dataset.num_items
         tu = max(self.test_user_dict) + 1 if self.test_user_dict else 0
         ti = max(max(v) for v in self.test_user_dict.values()) + 1 if self.test_user_dict else 0
         self.num_users = int(num_users or max(u.max() + 1, tu))          # dataloader.py:100-101
         self.num_items = int(num_items or max(i.max() + 1, ti))
         self.num_edges = int(u.shape[0])
         step = 1 + (t - t.min()) // int(hour_interval * 3600)            # :94,186-196 (0 is the self-loop padding)
-        self.user_hist_dict = {uu: self.train_user_dict.get(uu, []) for uu in range(self.num_users)}
+        if phase == "finetune":                                          # :36-45,126-135
+            self.user_hist_dict = {uu: list(v) for uu, v in self.train_user_dict.items()}
+            for source in user_hist_files:
+                for uu, it, _ in (source if _is_frame(source) else _read_lines(source)):
+                    self.user_hist_dict.setdefault(uu, []).extend(it.tolist())
+            for uu in range(self.num_users):
+                self.user_hist_dict.setdefault(uu, [])
+        else:
+            self.user_hist_dict = {uu: self.train_user_dict.get(uu, []) for uu in range(self.num_users)}
         if torch.device(device).type == "cuda":   # the product path: sorts, degrees and norms on the device (csrc/ingest.hip)
             from . import kernels as K
             self.edges, self.edge_norm, self.edge_times = K.binorm_edges(

@@ -1076,6 +1076,40 @@ def axpby(a: torch.Tensor, wa: float, b: torch.Tensor, wb: float) -> torch.Tenso
     return out
 
 
+def interp_normalize(tables, weights, out: torch.Tensor | None = None) -> torch.Tensor:
+    """F.normalize(sum_s tables[s] * weights[s], dim=1) in one pass -- RAGraph_edge/finetune_rag.py:63-86 (the interpolative
+    update).  tables: 1 to INTERP_MAX_TABLES fp32 [n, D] device tensors of one shape on one device; weights: as many floats (a
+    sequence or a host tensor).  The bits of the axpby chain followed by normalize_rows; `out` must not be one of the tables."""
+    L = _ready()
+    tables = list(tables)
+    if not 1 <= len(tables) <= N.INTERP_MAX_TABLES:
+        raise RagraphNativeError(f"interp_normalize: {len(tables)} tables, not 1 to {N.INTERP_MAX_TABLES}")
+    for s, t in enumerate(tables):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+            raise RagraphNativeError(f"interp_normalize: table {s} must be an fp32 [n, D] ROCm device tensor")
+        if t.shape != tables[0].shape or t.device != tables[0].device:
+            raise RagraphNativeError(f"interp_normalize: table {s} is {tuple(t.shape)} on {t.device}, table 0 "
+                                     f"{tuple(tables[0].shape)} on {tables[0].device}")
+    tables = [t.contiguous() for t in tables]
+    w = [float(x) for x in (weights.tolist() if isinstance(weights, torch.Tensor) else weights)]
+    if len(w) != len(tables):
+        raise RagraphNativeError(f"interp_normalize: {len(w)} weights for {len(tables)} tables")
+    n, D = tables[0].shape
+    if D < 1:
+        raise RagraphNativeError("interp_normalize: tables have no columns")
+    if out is None:
+        out = torch.empty_like(tables[0])
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != tables[0].shape
+          or out.device != tables[0].device or not out.is_contiguous()):
+        raise RagraphNativeError("interp_normalize: out must be a contiguous fp32 tensor of the tables' shape and device")
+    if n == 0:
+        return out
+    ptrs = (ctypes.c_void_p * len(tables))(*[t.data_ptr() for t in tables])
+    ws = (ctypes.c_float * len(w))(*w)
+    N.check(L.ragraph_interp_normalize_f32(ptrs, ws, len(tables), n, D, out.data_ptr(), _stream()), "interp_normalize")
+    return out
+
+
 def softmax_mix(logits: torch.Tensor, rag_label: torch.Tensor | None, lam: float = 0.0,
                 log_mode: bool = False) -> torch.Tensor:
     """softmax(logits)*(1-lam) + rag_label*lam -- RAGraph.py:55-57."""
