@@ -16,7 +16,7 @@
 // exact scan), [18] / [19] the smallest / largest final exact k-th best score of the call's queries as order-preserving
 // ints (f2ord; what the owner of the bank builds the next call's prior from), [20] the call's final *overflow (so that ONE
 // copy of these words tells the owner everything), [21] a tight bound was in force, [22] soft misses, [23] the repair that ran
-// (filter_verify_fixup.h), [24..32) reserved.
+// (filter_verify_fixup.h), [24..32) reserved.  Host-side mirror, by name: ragraph_amd/filter_stats.py (keep the two alike).
 constexpr int FILTER_STATS_INTS = 32;
 constexpr int FILTER_STATS_MAGIC = 0x52414753;
 __device__ __forceinline__ void note_candidates(int* cstat, int64_t b, int n) {

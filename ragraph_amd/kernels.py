@@ -14,6 +14,7 @@ import torch
 from . import _native as N
 from ._native import ACT_ELU, ACT_LEAKY, ACT_NONE, ACT_PRELU, ACT_RELU, RagraphNativeError  # noqa: F401
 from ._native import LINEAR_GENERIC, LINEAR_NARROW, LINEAR_SMALL, LINEAR_STREAM, LINEAR_TILE  # noqa: F401
+from .filter_stats import MAGIC_VALUE as FILTER_STATS_MAGIC, levels as filter_stats_levels, ord2f  # noqa: F401  (the names tools import)
 
 _device_ok = False
 
@@ -273,17 +274,6 @@ def set_filter_tight_prior(theta_tight) -> float:
     return N.lib().ragraph_topk_cosine_filtered_set_tight_prior(float("nan") if theta_tight is None else float(theta_tight))
 
 
-def ord2f(v: int) -> float:
-    """The float behind an order-preserving int of the statistics words (csrc/filter_common.h f2ord: non-negative floats
-    keep their bits, negative ones have the 31 low bits flipped)."""
-    import struct
-
-    v = int(v)
-    if v < 0:
-        v ^= 0x7FFFFFFF
-    return struct.unpack("<f", struct.pack("<i", v))[0]
-
-
 def set_max_i8_levels(n: int) -> int:
     """Cap the int8 levels of this thread's following filtered calls (-1: the library's rule); returns the old cap."""
     return N.lib().ragraph_topk_cosine_filtered_max_i8_levels(int(n))
@@ -389,21 +379,10 @@ def filter_wide128_helps(B: int, n_keys: int, D: int, k: int) -> bool:
 
 _EXCHANGE_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)
 
-# Candidate statistics of a filtered call: the 16 ints its launches leave at the end of its workspace (include/ragraph_hip.h:
-# ragraph_topk_cosine_filtered_stats_offset).  topk_cosine_filtered(..., return_stats=True) hands the caller a view of
-# THAT call's words (valid until the next filtered call on the same stream reuses the workspace); there is no module-level
-# "last call" state -- another thread, stream or index would overwrite it.
+# Candidate statistics of a filtered call (filter_stats.py): topk_cosine_filtered(..., return_stats=True) hands the caller a
+# view of THAT call's words (valid until the next filtered call on the same stream reuses the workspace); there is no
+# module-level "last call" state -- another thread, stream or index would overwrite it.
 FILTER_STATS = True   # (KeyIndex: this ops object supports return_stats)
-FILTER_STATS_MAGIC = 0x52414753
-
-
-def filter_stats_levels(stats) -> list:
-    """[(dtype, keys, candidates per query or None)] per level from a HOST copy of a call's statistics words."""
-    st = [int(x) for x in stats]
-    if len(st) < 16 or st[0] != FILTER_STATS_MAGIC:
-        return []
-    return [("int8" if st[8 + l] else "bf16", st[11 + l], (st[2 + l] / st[5 + l]) if st[5 + l] else None)
-            for l in range(min(st[1], 3))]
 
 
 def topk_cosine_filtered(q: torch.Tensor, keys_normalized: torch.Tensor, keys_bf16: torch.Tensor, k: int,
@@ -596,7 +575,7 @@ def topk_cosine_small(q: torch.Tensor, keys_normalized: torch.Tensor, keys_bf16:
     (scores, idx, overflow): overflow = 1-element int32 device tensor, the queries answered by an exact scan.  Under this
     thread's speculative first bound (set_filter_prior) the launch has no bound phase and a second, normally empty launch
     scans for the queries the prior was too high for.  return_stats=True: + a [32] int32 view of the call's statistics words
-    ([16] speculative, [17] misses, [18] / [19] smallest / largest k-th best score: filter_stats / ord2f)."""
+    (filter_stats.py: SPECULATIVE, SPEC_FAILED, KTH_LO / KTH_HI -- smallest / largest k-th best score, through ord2f)."""
     L = _ready()
     q = _f32c(q, "topk_cosine_small.q")
     kn = _f32c(keys_normalized, "topk_cosine_small.keys")

@@ -5,7 +5,14 @@ import os
 
 import torch
 
+from . import filter_stats as FS
 from ._native import TOPK_FILTER_MAX, TOPK_MAX
+
+# The kernel paths KeyIndex._route names (SLAB: plain ops.topk_cosine), and the filtered entries of one bank
+# by list length: (longest list, route, the ops' rule that says where it pays -- None: asked before the bank's clock moves).
+ROUTES = (SLAB, PACKED, FUSED, SMALL, FILTERED, WIDE, WIDE128, SHARDED, COLLAPSED, SLABS_OF_FILTERED) = (
+    "SLAB", "PACKED", "FUSED", "SMALL", "FILTERED", "WIDE", "WIDE128", "SHARDED", "COLLAPSED", "SLABS_OF_FILTERED")
+FILTERED_BY_K = ((32, FILTERED, "filter_helps"), (TOPK_MAX, WIDE, "filter_wide_helps"), (TOPK_FILTER_MAX, WIDE128, None))
 
 
 class KeyIndex:
@@ -154,7 +161,8 @@ class KeyIndex:
 
     @staticmethod
     def _capturing() -> bool:
-        return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+        # (is_initialized, not is_available: nothing captures before the runtime is up, and is_available costs ~2 us of every call)
+        return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
 
     def _sealed_keys(self) -> torch.Tensor:
         return self.keys_normalized[:self._sealed_rows] if self._tail_rows else self.keys_normalized
@@ -228,7 +236,7 @@ class KeyIndex:
         if dedup is None or kn.shape[0] < self.DEDUP_MIN_ROWS:
             self._collapsed = False
             return
-        if kn.is_cuda and torch.cuda.is_current_stream_capturing():
+        if kn.is_cuda and self._capturing():
             return   # (stays undecided: searched as it is for now)
         U, largest, uniq_row, group_ptr, members = dedup(kn)
         self.duplicate_stats = (kn.shape[0], U, largest)
@@ -246,26 +254,23 @@ class KeyIndex:
         kernels spend ~3.5 us more per query than the filter: beyond OVERFLOW_FRACTION of a batch the levels first leave
         int8 (the bf16 bound is ~5x tighter), then the bank leaves the filter."""
         pend = self._pending
-        if pend is None or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
-            return  # (an event query is not a capturable call)
-        if not pend[1].query():
+        if pend is None or self._capturing() or not pend[1].query():   # (an event query is not a capturable call)
             return
-        n_over, B = int(pend[0][0]), pend[2]   # (no kernel counts all-zero queries: they are answered without a scan)
-        if n_over < 0:                          # (the statistics words came in one copy: their word 20 is the count)
-            n_over = int(pend[0][21]) if int(pend[0][1]) == 0x52414753 else 0
         self._pending = None
-        words = pend[0][1:].tolist()
+        (n_over, *words), B = pend[0].tolist(), pend[2]   # the pinned word: the count, then the call's statistics words (filter_stats)
+        labelled = len(words) > FS.MAGIC and words[FS.MAGIC] == FS.MAGIC_VALUE
+        if n_over < 0:                          # (the statistics words came in one copy: they hold the count themselves)
+            n_over = words[FS.OVERFLOW] if labelled else 0   # (no kernel counts all-zero queries: answered without a scan)
         speculative = False
-        if len(pend) > 4 and pend[4] and len(words) >= 20 and words[0] == 0x52414753:
-            speculative = bool(words[16])
+        if len(pend) > 4 and pend[4] and len(words) > FS.KTH_HI and labelled:
+            speculative = bool(words[FS.SPECULATIVE])
             n_over = self._judge_prior(pend[4], B, words, n_over)   # (what is left is the lists' fault)
         self._overflowed += n_over
         i8_was_off = self._i8_off               # (the call ran under this setting: the overflow rule below judges IT)
         # the call's sampled candidate counts (int8 levels only are judged -- and only of a call with a bound pass: what a
         # prior far below the queries' k-th best lets through says nothing about the int8 copy, _judge_prior withdraws the prior)
-        if pend[3] and pend[0].numel() > 16 and not speculative:
-            from .kernels import filter_stats_levels
-            i8 = [(keys, c) for dt, keys, c in filter_stats_levels(pend[0][1:17].tolist()) if dt == "int8" and c is not None]
+        if pend[3] and len(words) >= FS.LEVEL_WORDS and not speculative:
+            i8 = [(keys, c) for dt, keys, c in FS.levels(words) if dt == "int8" and c is not None]
             if i8:
                 self.last_i8_candidates = sum(c for _, c in i8)
                 if self.last_i8_candidates > self.I8_MAX_CANDIDATES_BASE + self.I8_MAX_CANDIDATES_PER_KEY * sum(kk for kk, _ in i8):
@@ -290,16 +295,13 @@ class KeyIndex:
         their fault, and neither are lists that overflowed under a prior (far below most queries' k-th best it floods them:
         the prior goes, the bank is judged by its calls with a bound pass)."""
         st = self._spec_state(k)
-        spec, failed, lo, hi = words[16], words[17], words[18], words[19]
+        spec, failed, lo, hi = words[FS.SPECULATIVE], words[FS.SPEC_FAILED], words[FS.KTH_LO], words[FS.KTH_HI]
         lists_over = max(n_over - failed, 0)
-        cand = None
-        if any(words[5 + l] for l in range(3)):
-            cand = sum(words[2 + l] / words[5 + l] for l in range(min(words[1], 3)) if words[5 + l])
+        cand = FS.candidates_per_query(words)
         if lists_over:
             st["hist"], st["queries"] = [], 0      # (a bank whose lists overflow is no ground for a prior)
         elif lo != 0x7FFFFFFF and hi != -0x80000000 and B - failed > 0:
-            from .kernels import ord2f
-            st["hist"].append((ord2f(lo), ord2f(hi)))
+            st["hist"].append((FS.ord2f(lo), FS.ord2f(hi)))
             del st["hist"][:-self.SPEC_HISTORY]
             st["queries"] += B
         if not spec:
@@ -321,15 +323,15 @@ class KeyIndex:
         return 0   # (a speculative call says nothing about the lists)
 
     def _judge_tight(self, st: dict, words):
-        """A polled speculative call's words [21] (a tight bound was in force), [22] (soft misses), [23] (1: the 256-query
+        """A polled speculative call's words TIGHT (a tight bound was in force), SOFT_MISSES and REPAIR (1: the 256-query
         repair ran, 2: the all-queries level): widen the margin after a flood of soft misses, withdraw t after the level."""
-        if len(words) < 24 or not words[21]:
+        if len(words) <= FS.REPAIR or not words[FS.TIGHT]:
             return
-        st["soft"] = st.get("soft", 0) + words[22]
+        st["soft"] = st.get("soft", 0) + words[FS.SOFT_MISSES]
         st["tight_used"] = st.get("tight_used", 0) + 1
-        if words[23] == 2:
+        if words[FS.REPAIR] == 2:
             st["tight_off_at"] = self._queries
-        if words[23] == 2 or words[22] > self.TIGHT_MAX_SOFT:
+        if words[FS.REPAIR] == 2 or words[FS.SOFT_MISSES] > self.TIGHT_MAX_SOFT:
             st["tight_margin"] = min(2.0 * st.get("tight_margin", self.TIGHT_MARGIN), self.TIGHT_MARGIN_MAX)
 
     def _tight_for(self, B: int, k: int, prior):
@@ -394,7 +396,7 @@ class KeyIndex:
         small: the single-launch kernel's call (any batch size it takes)."""
         if not self.spec_enabled or (B < self.SPEC_MIN_BATCH and not small) or getattr(self.ops, "set_filter_prior", None) is None:
             return None
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        if self._capturing():
             # a captured launch would carry TODAY's prior by value into every replay, and the statistics that could withdraw it
             # are not read under capture: captured calls keep their bound pass (a proof, whatever queries the replays bring)
             return None
@@ -415,19 +417,19 @@ class KeyIndex:
         judged by _poll_overflow at a later call."""
         if not over.is_cuda:  # (the CPU tests' oracle shim)
             self._overflowed += int(over)
-        elif self._pending is None and not torch.cuda.is_current_stream_capturing():
+        elif self._pending is None and not self._capturing():
             # a call of a few queries takes ~60 us and the copy + event below ~2 us of its stream: once the bank's dispatch
             # has settled (a prior in use, nothing withdrawn or demoted) such calls report every fourth time only
             self._notes += 1
             if B <= 64 and (self._notes & 3) and self.last_prior is not None:
                 return
             if self._host_word is None:
-                self._host_word = torch.zeros(33, dtype=torch.int32).pin_memory()   # [0] overflow, [1:33] the call's statistics
+                self._host_word = torch.zeros(1 + FS.N_WORDS, dtype=torch.int32).pin_memory()   # [0] overflow, [1:] the call's statistics
                 self._event = torch.cuda.Event()
-            if stats is not None and stats.numel() >= 32:
-                # ONE copy: the statistics words carry the call's final overflow count themselves ([20])
-                self._host_word[1:33].copy_(stats[:32], non_blocking=True)
-                self._host_word[0] = -1            # (host store: "read it from word 20")
+            if stats is not None and stats.numel() >= FS.N_WORDS:
+                # ONE copy: the statistics words carry the call's final overflow count themselves (FS.OVERFLOW)
+                self._host_word[1:].copy_(stats[:FS.N_WORDS], non_blocking=True)
+                self._host_word[0] = -1            # (host store: "read it from the words")
             else:
                 self._host_word[:1].copy_(over, non_blocking=True)
                 self._host_word[1:].zero_()
@@ -443,7 +445,7 @@ class KeyIndex:
         cap = getattr(self.ops, "set_max_i8_levels", None)
         if cap is None:
             return None, False
-        if self._i8_ok is None and not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
+        if self._i8_ok is None and not self._capturing():
             # (the copy has two scales, csrc/filter_common.h: the NORMAL granules' error decides, unless more than a quarter
             # of the granules are HEAVY ones with a useless bound -- a bank of heavy-tailed rows throughout)
             c = self.ops.int8_copy_classes(self._bf16, self._sealed_rows)
@@ -471,22 +473,21 @@ class KeyIndex:
         decision that changes which collectives run is taken from plan_n -- the largest shard's size -- so that all
         ranks take it alike.  prior (with exchange only): the speculative first bound the owner of the sharded bank chose for
         THIS call on every rank alike (it removes the bound pass and exchange 0; the owner proves the merged rows).
-        With a tail: the sealed rows are searched as a bank of their own (every rule below unchanged), then one
+        With a tail: the sealed rows are searched as a bank of their own (every rule of _route unchanged), then one
         ops.topk_cosine_tail call continues the lists over the tail; idx_base applies to both parts.  Calls without a seeded
         pass -- k > TOPK_MAX, banks wider than every fused kernel -- run over all rows as ever; a shard of a sharded bank
         (exchange) seals first."""
         ops = self.ops
         if q.shape[1] != self.dim:
             raise ValueError(f"KeyIndex.topk: queries of {q.shape[1]} columns against a bank of {self.dim}")
-        if self._tail_rows:
-            if exchange is not None:
-                self.seal()
-            else:
-                self._maybe_seal(k)
+        if self._width is not None and self._width != self.dim:
+            q = ops.pad_cols(q, self._width)   # (the only place: _search and the tail pass take q at the bank's width)
+        if self._tail_rows and exchange is not None:
+            self.seal()
+        else:
+            self._maybe_seal(k)   # (nothing without a tail)
         if not self._tail_rows or k > TOPK_MAX or self._width is None:
             return self._search(self.keys_normalized, q, k, idx_base, exchange, plan_n, prior)
-        if self._width != self.dim:
-            q = ops.pad_cols(q, self._width)
         if k > self._sealed_rows:   # (only while capturing: the rule above seals otherwise) exact over all rows, no seed
             return ops.topk_cosine(q, self.keys_normalized, k, idx_base=idx_base)
         s, i = self._search(self._sealed_keys(), q, k, idx_base)
@@ -496,155 +497,129 @@ class KeyIndex:
             s, i = ops.topk_cosine_tail(q, self.keys_normalized[t0:t1], s, i, idx_base + t0)
         return s, i
 
-    def _search(self, kn: torch.Tensor, q: torch.Tensor, k: int, idx_base: int = 0, exchange=None, plan_n: int = 0, prior=None):
-        """topk over the rows kn: the sealed part (q already at the padded width then), or all rows of a bank without a tail."""
-        ops = self.ops
-        wide128 = False
-        if k > TOPK_MAX and exchange is None:
-            # Lists of 65 .. 128 keys on one bank of a fused width: the wide128 filtered entry behind ops.topk_cosine_filtered where
-            # the ops' own rule says it pays -- not for a bank searched through its unique rows (topk_expand_groups stops at 64),
-            # a bank with a tail (the bf16 / int8 copy covers the sealed rows only) or one that defeated the filter.
-            rule = None
-            if k <= TOPK_FILTER_MAX and self._width is not None and not self._filter_off and not self._tail_rows:
-                rule = getattr(ops, "filter_wide128_helps", None)
-            if rule is not None:
-                if self._collapsed is None:
-                    self._judge_duplicates()
-                if self._collapsed:
-                    rule = None
-            qp = q
-            if self._width is not None and self._width != self.dim:
-                qp = ops.pad_cols(q, self._width)
-            if rule is None or not rule(qp.shape[0], kn.shape[0], qp.shape[1], k):
-                # ordered large k (exact fp32 score slabs) over the full bank: duplicate rows score alike and the lower row wins,
-                # so no collapse is needed; the prior, counters and pending overflow word are left as they are
-                return ops.topk_cosine(qp, kn, k, idx_base=idx_base)
-            wide128 = True   # (the rule has answered: the filtered call below, with its overflow poll, re-probe and learnt bounds)
+    def _says(self, rule: str, *shape) -> bool:
+        """The ops' own rule for a shape; an ops object without the rule never takes that route."""
+        rule = getattr(self.ops, rule, None)
+        return rule is not None and bool(rule(*shape))
+
+    def _wide128_open(self, k: int) -> bool:
+        """May lists of 65 .. 128 keys ask the wide128 rule?  (The bf16 / int8 copy covers the sealed rows only.)"""
+        return k <= TOPK_FILTER_MAX and self._width is not None and not self._filter_off and not self._tail_rows and \
+            hasattr(self.ops, "filter_wide128_helps")
+
+    def _route(self, B: int, n_rows: int, D: int, k: int, exchange=None, plan_n: int = 0, tick: bool = False) -> str:
+        """The kernel path (one of ROUTES) a call of B queries of width D against n_rows sealed rows takes as the index stands, and
+        the only place that orders the paths.  Without tick no side effect: it reads _filter_off, _collapsed (undecided: searched
+        as it is), _tail_rows and _width and asks each of the ops' rules at most once.  tick: _search's call (its docstring)."""
+        shape = (B, n_rows, D, k)
         if self._width is None:   # wider than every fused kernel: exact score slabs, this shard's own top-k (no exchange needed)
-            return ops.topk_cosine(q, kn, k, idx_base=idx_base)
-        if self._width != self.dim:
-            q = ops.pad_cols(q, self._width)
-        B, D = q.shape
-        if self._collapsed is None:
+            return SLAB
+        if k > TOPK_MAX and exchange is None:
+            # ordered large k over the full bank (duplicate rows score alike and the lower row wins: no collapse needed) unless the
+            # wide128 entry pays -- never through unique rows: topk_expand_groups stops at 64
+            if self._collapsed or not (self._wide128_open(k) and self._says("filter_wide128_helps", *shape)):
+                return SLAB
+        elif self._collapsed:
+            return COLLAPSED
+        elif exchange is not None and self._says("filter_helps", B, max(plan_n, n_rows), D, k) and B <= self.MAX_FILTERED_BATCH:
+            return SHARDED   # (the rule is asked about the largest shard: every rank takes the same collectives)
+        if tick:   # the bank's clock: judge the last polled call, lift a demotion that is due, count the queries
+            self._poll_overflow()
+            self._maybe_reprobe(B)
+            self._queries += B
+        if not self._filter_off:
+            if self._says("fused_helps", *shape):   # small bank: every phase in one launch
+                return FUSED
+            ready = getattr(self.ops, "small_state_ready", None)   # a handful of queries against a large bank: ONE launch
+            if self._says("small_helps", *shape) and (ready is None or ready(self.keys_normalized.device)):
+                return SMALL
+            for longest, route, rule in FILTERED_BY_K if exchange is None else ():   # (a shard the sharded rule refused: fp32)
+                if k <= longest:   # (no rule: it was asked above, once per call)
+                    if rule is None or self._says(rule, *shape):
+                        return route if B <= self.MAX_FILTERED_BATCH else SLABS_OF_FILTERED
+                    break
+        return PACKED if self._says("packed_keys_help", B, D, k) else SLAB
+
+    def _bf16_copy(self, kn: torch.Tensor) -> torch.Tensor:
+        if self._bf16 is None:
+            self._bf16 = self.ops.keys_to_bf16(kn)
+        return self._bf16
+
+    def _guarded(self, entry, q, kn, k: int, prior, tight, **kwargs):
+        """ONE call entry(q, kn, bf16 copy, k, **kwargs) under the library's thread-local knobs -- this bank's int8 cap, the prior,
+        the tight bound --, each knob it set reset whatever the call does; a call that returns leaves its prior in last_prior.
+        Returns (scores, idx, over, the call's statistics words or None from an ops object without FILTER_STATS, int8 allowed)."""
+        kb = self._bf16_copy(kn)
+        knobs = [(getattr(self.ops, name), v) for name, v in (("set_filter_prior", prior), ("set_filter_tight_prior", tight)) if v is not None]
+        cap, had_i8 = self._cap_i8()
+        for knob, v in knobs:
+            knob(v)
+        with_stats = getattr(self.ops, "FILTER_STATS", False)   # this call's own statistics words, handed on explicitly
+        try:
+            out = entry(q, kn, kb, k, **(dict(kwargs, return_stats=True) if with_stats else kwargs))
+        finally:
+            if cap is not None:
+                cap(-1)
+            for knob, _ in knobs:
+                knob(None)
+        self.last_prior = prior
+        s, i, over, stats = out if with_stats else (*out, None)
+        return s, i, over, stats, had_i8
+
+    def _search(self, kn: torch.Tensor, q: torch.Tensor, k: int, idx_base: int = 0, exchange=None, plan_n: int = 0, prior=None):
+        """topk over the rows kn (the sealed part, or all rows of a bank without a tail), q at the bank's width: prepare, route,
+        dispatch.  The order is behaviour:
+        * duplicates are judged first (a large k: only where the wide128 rule could be asked);
+        * a large k that stays on the slabs, a collapsed bank (the inner index counts, not this one) and a sharded filtered call are
+          settled on _filter_off AS IT STANDS: no poll, no re-probe, _queries and _pending as they are, never a _note_overflow;
+        * every other call: _poll_overflow(), _maybe_reprobe(B), _queries += B, and only then is _filter_off read for the fused,
+          small and filtered routes (so a demotion that is due is lifted by the call that then takes the filter)."""
+        ops = self.ops
+        (B, D), n_rows = q.shape, kn.shape[0]
+        if self._collapsed is None and self._width is not None and (k <= TOPK_MAX or exchange is not None or self._wide128_open(k)):
             self._judge_duplicates()
-        if self._collapsed:
-            inner, group_ptr, members = self._collapsed
-            U = inner.keys_normalized.shape[0]
-            if exchange is None:
-                su, iu = inner.topk(q, min(k, U))
-                return ops.topk_expand_groups(su, iu, group_ptr, members, k, idx_base=idx_base)
-            if U >= k:
-                # one shard of a row-sharded bank: the unique rows take part in the exchanges (plan_n = the largest number of
-                # searched rows over the shards -- ShardedToyGraphBase asks search_rows() of every rank); the shard's list
-                # (padded with -inf / INT64_MAX where nothing can reach the global top-k any more) is expanded to bank rows
-                su, iu = inner.topk(q, k, 0, exchange, plan_n, prior)
-                return ops.topk_expand_groups(su, iu, group_ptr, members, k, idx_base=idx_base)
-            raise RuntimeError("KeyIndex: a collapsed shard of fewer unique rows than k cannot take part in the exchanges; "
-                               "ShardedToyGraphBase keeps such a shard uncollapsed (search_rows(min_unique=k))")
-        fhelps = getattr(ops, "filter_helps", None)
-        if exchange is not None:
-            if fhelps is not None and fhelps(B, max(plan_n, kn.shape[0]), D, k) and B <= self.MAX_FILTERED_BATCH:
-                if self._bf16 is None:
-                    self._bf16 = ops.keys_to_bf16(kn)
-                cap, _ = self._cap_i8()   # (per shard: which kernel a level runs on does not change the exchanges)
-                if prior is not None:
-                    ops.set_filter_prior(prior)
-                try:
-                    if getattr(ops, "FILTER_STATS", False):
-                        s, i, self.last_over, self.last_stats = ops.topk_cosine_filtered(
-                            q, kn, self._bf16, k, idx_base=idx_base, exchange=exchange, plan_n=plan_n, return_stats=True)
-                    else:
-                        s, i, self.last_over = ops.topk_cosine_filtered(q, kn, self._bf16, k, idx_base=idx_base,
-                                                                        exchange=exchange, plan_n=plan_n)
-                finally:
-                    if cap is not None:
-                        cap(-1)
-                    if prior is not None:
-                        ops.set_filter_prior(None)
-                self.last_prior = prior
-                return s, i
-            fhelps = None  # (fp32 kernels: the shard's own exact top-k, no exchange needed)
-        if exchange is None and 32 < k <= TOPK_MAX:
-            # lists of 33 .. 64 keys on one bank: the wide filtered entry behind ops.topk_cosine_filtered, where the ops' own rule
-            # says it pays (an ops object without the rule keeps the fp32 score slabs); everything below -- the overflow poll,
-            # the re-probe, the learned bounds per (bank, k) -- applies to it as to k <= 32
-            fhelps = getattr(ops, "filter_wide_helps", None)
-        if wide128:
-            fhelps = lambda *_: True   # noqa: E731  (asked above, once per call)
-        self._poll_overflow()
-        self._maybe_reprobe(B)
-        self._queries += B
-        fused = getattr(ops, "fused_helps", None)
-        if fused is not None and not self._filter_off and fused(B, kn.shape[0], D, k):  # small bank: every phase in one launch
-            if self._bf16 is None:
-                self._bf16 = ops.keys_to_bf16(kn)
-            return ops.topk_cosine_fused(q, kn, self._bf16, k, idx_base=idx_base)
-        small = getattr(ops, "small_helps", None)
-        if (small is not None and not self._filter_off and small(B, kn.shape[0], D, k)
-                and getattr(ops, "small_state_ready", lambda _d: True)(q.device)):
-            # a handful of queries against a large bank: every phase of the filtered call in ONE launch (csrc/topk_small.hip)
-            if self._bf16 is None:
-                self._bf16 = ops.keys_to_bf16(kn)
-            cap, had_i8 = self._cap_i8()
-            stats = None
-            prior = self._prior_for(B, k, small=True)
-            if prior is not None:
-                ops.set_filter_prior(prior)
-            try:
-                if getattr(ops, "FILTER_STATS", False):
-                    s, i, over, stats = ops.topk_cosine_small(q, kn, self._bf16, k, idx_base=idx_base, return_stats=True)
-                else:
-                    s, i, over = ops.topk_cosine_small(q, kn, self._bf16, k, idx_base=idx_base)
-            finally:
-                if cap is not None:
-                    cap(-1)
-                if prior is not None:
-                    ops.set_filter_prior(None)
-            self.last_prior = prior
-            self._note_overflow(over, B, had_i8 and D in (128, 256), stats, k)
-            return s, i
-        if fhelps is not None and not self._filter_off and fhelps(B, kn.shape[0], D, k):
-            if self._bf16 is None:
-                self._bf16 = ops.keys_to_bf16(kn)
-            # (the packed fp32 copy is not made for this path: its first bound comes from the bf16 copy itself)
-            if B > self.MAX_FILTERED_BATCH:
-                # the candidate lists take 8 KiB per query: slabs of 256 k queries keep the workspace at 2 GiB (the edge
-                # flavour asks for all 4 M nodes at once) at the throughput of one big call
-                outs = [self._search(kn, q[b0:b0 + self.MAX_FILTERED_BATCH], k, idx_base)
-                        for b0 in range(0, B, self.MAX_FILTERED_BATCH)]
-                return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
-            cap, had_i8 = self._cap_i8()
-            # (did THIS call have int8 levels?  The plan queries answer for k <= 32; a wide call under an open cap is taken to
-            # have had them: an overflowing bank then leaves int8 first and the filter at the next verdict, the usual order)
-            had_i8 = had_i8 and (k > 32 or ops.filtered_i8_levels(B, kn.shape[0], D, k) > 0)
-            stats = None
-            prior = self._prior_for(B, k)
-            tight = self._tight_for(B, k, prior)
-            if prior is not None:
-                ops.set_filter_prior(prior)
-            if tight is not None:
-                ops.set_filter_tight_prior(tight)
-            try:
-                if getattr(ops, "FILTER_STATS", False):   # this call's own statistics words, handed on explicitly
-                    s, i, over, stats = ops.topk_cosine_filtered(q, kn, self._bf16, k, idx_base=idx_base,
-                                                                 keys_packed=self._packed, return_stats=True)
-                else:
-                    s, i, over = ops.topk_cosine_filtered(q, kn, self._bf16, k, idx_base=idx_base, keys_packed=self._packed)
-            finally:
-                if cap is not None:
-                    cap(-1)
-                if prior is not None:
-                    ops.set_filter_prior(None)
-                if tight is not None:
-                    ops.set_filter_tight_prior(None)
-            self.last_prior = prior
-            self.last_tight = tight
-            self._note_overflow(over, B, had_i8, stats, k)
-            self.last_stats = stats   # (diagnostic: bench.py / tools read the levels' candidate counts of the last call)
-            return s, i
-        helps = getattr(ops, "packed_keys_help", None)
-        if helps is not None and helps(B, D, k):
+        route = self._route(B, n_rows, D, k, exchange, plan_n, tick=True)
+        if route == SLAB:
+            return ops.topk_cosine(q, kn, k, idx_base=idx_base)
+        if route == PACKED:
             if self._packed is None:
                 self._packed = ops.pack_keys(kn)
             return ops.topk_cosine(q, kn, k, idx_base=idx_base, keys_packed=self._packed)
-        return ops.topk_cosine(q, kn, k, idx_base=idx_base)
+        if route == FUSED:
+            return ops.topk_cosine_fused(q, kn, self._bf16_copy(kn), k, idx_base=idx_base)
+        if route == COLLAPSED:
+            # (a shard: its unique rows take part in the exchanges, plan_n being the largest search_rows() of the ranks)
+            inner, group_ptr, members = self._collapsed
+            U = inner.keys_normalized.shape[0]
+            if exchange is not None and U < k:
+                raise RuntimeError("KeyIndex: a collapsed shard of fewer unique rows than k cannot take part in the exchanges; "
+                                   "ShardedToyGraphBase keeps such a shard uncollapsed (search_rows(min_unique=k))")
+            su, iu = inner.topk(q, min(k, U)) if exchange is None else inner.topk(q, k, 0, exchange, plan_n, prior)
+            return ops.topk_expand_groups(su, iu, group_ptr, members, k, idx_base=idx_base)
+        if route == SLABS_OF_FILTERED:
+            # the candidate lists take 8 KiB per query: slabs of 256 k queries keep the workspace at 2 GiB (the edge flavour
+            # asks for all 4 M nodes at once) at the throughput of one big call
+            self._bf16_copy(kn)
+            outs = [self._search(kn, q[b0:b0 + self.MAX_FILTERED_BATCH], k, idx_base) for b0 in range(0, B, self.MAX_FILTERED_BATCH)]
+            return torch.cat([o[0] for o in outs]), torch.cat([o[1] for o in outs])
+        if route == SHARDED:   # the caller's prior, no tight bound; the owner of the sharded bank reads last_over: no _note_overflow
+            s, i, self.last_over, stats, _ = self._guarded(ops.topk_cosine_filtered, q, kn, k, prior, None,
+                                                           idx_base=idx_base, exchange=exchange, plan_n=plan_n)
+            if stats is not None:   # (only an ops object with FILTER_STATS has any)
+                self.last_stats = stats
+        elif route == SMALL:   # records the prior only: last_stats and last_tight stay those of the last filtered call
+            s, i, over, stats, had_i8 = self._guarded(ops.topk_cosine_small, q, kn, k, self._prior_for(B, k, small=True), None,
+                                                      idx_base=idx_base)
+            self._note_overflow(over, B, had_i8 and D in (128, 256), stats, k)
+        else:                  # FILTERED, WIDE, WIDE128: one entry (the packed fp32 copy is passed on, never made here)
+            prior = self._prior_for(B, k)
+            tight = self._tight_for(B, k, prior)
+            s, i, over, stats, had_i8 = self._guarded(ops.topk_cosine_filtered, q, kn, k, prior, tight, idx_base=idx_base, keys_packed=self._packed)
+            # (did THIS call have int8 levels?  The plan answers for k <= 32, under the open cap the call ran with; a wide call under
+            # an open cap is taken to have had them: an overflowing bank then leaves int8 first and the filter at the next verdict)
+            had_i8 = had_i8 and (k > 32 or ops.filtered_i8_levels(B, n_rows, D, k) > 0)
+            self.last_tight = tight
+            self._note_overflow(over, B, had_i8, stats, k)
+            self.last_stats = stats   # (diagnostic: bench.py / tools read the levels' candidate counts of the last call)
+        return s, i
+
