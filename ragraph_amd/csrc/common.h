@@ -86,6 +86,11 @@ static inline int device_cus_multiple_of_8() {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+// CSR rows longer than this many edges are summed in blocks: every block of ROW_BLOCK consecutive edges is its own chain from
+// +0 and the block sums are added in block order (sparse.hip, the gather waves of dense.hip) -- the oracle's ORACLE_ROW_BLOCK;
+// the bits depend on it.  ragraph_amd/kernels.py keeps the same number as ROW_BLOCK.
+constexpr int ROW_BLOCK = 4096;
+
 #define RG_NEG_INF (-__builtin_huge_valf())
 #define RG_IDX_NONE INT_MAX
 

@@ -472,8 +472,7 @@ __global__ void __launch_bounds__(512, 2) linear_stream_kernel(const float* __re
 // bits of the two-launch form, the aggregated table never in HBM, gathers and MFMAs on the same CU at the same time.  The
 // gather waves keep two prefetches ahead of themselves (the row pointers of the stage after next, the first KD / 4 (col, val)
 // pairs of the next stage's rows: one load covers a row of up to KD / 4 edges), so a stage waits for ONE dependent latency,
-// the gathers themselves.  Rows longer than ROW_BLOCK edges are summed in blocks as everywhere (csrc/sparse.hip).
-constexpr int AGG_ROW_BLOCK = 4096;   // = sparse.hip's ROW_BLOCK (the oracle's ORACLE_ROW_BLOCK)
+// the gathers themselves.  Rows longer than ROW_BLOCK edges are summed in blocks as everywhere (ROW_BLOCK, common.h).
 template <int KD>
 struct AggLinCfg {
   static constexpr int THREADS = 1024, MFMA_THREADS = 512;
@@ -641,7 +640,7 @@ __global__ void __launch_bounds__(1024, 1) spmm_linear_stream_kernel(const int64
       if (stage < nstages && r < M) {
         e0[i] = rowptr[r];
         const int64_t d64 = rowptr[r + 1] - e0[i];
-        deg[i] = d64 > AGG_ROW_BLOCK ? AGG_ROW_BLOCK + 1 : (int)d64;
+        deg[i] = d64 > ROW_BLOCK ? ROW_BLOCK + 1 : (int)d64;
       }
     }
   };
@@ -664,17 +663,17 @@ __global__ void __launch_bounds__(1024, 1) spmm_linear_stream_kernel(const int64
     load_pairs(nxt_e0, nxt_deg, nc, nv);            // (in flight under the gathers below)
     load_rowptr(stage + 2, nn_e0, nn_deg);
     float4 a = zero4, b = zero4;
-    if (cur_deg[0] > AGG_ROW_BLOCK || cur_deg[1] > AGG_ROW_BLOCK) {
-      // a hub row in the pair: blocks of AGG_ROW_BLOCK edges, each its own chain, the block sums added in order
+    if (cur_deg[0] > ROW_BLOCK || cur_deg[1] > ROW_BLOCK) {
+      // a hub row in the pair: blocks of ROW_BLOCK edges, each its own chain, the block sums added in order
 #pragma unroll 1
       for (int i = 0; i < 2; ++i) {
         const int64_t r = (st0 + stage) * C::STAGE_ROWS + grp + C::GROUPS * i;
         const int64_t e0 = i ? cur_e0[1] : cur_e0[0];
-        const int64_t deg = (i ? cur_deg[1] : cur_deg[0]) > AGG_ROW_BLOCK ? rowptr[r + 1] - e0 : (int64_t)(i ? cur_deg[1] : cur_deg[0]);
+        const int64_t deg = (i ? cur_deg[1] : cur_deg[0]) > ROW_BLOCK ? rowptr[r + 1] - e0 : (int64_t)(i ? cur_deg[1] : cur_deg[0]);
         float4 tot = zero4;
 #pragma unroll 1
-        for (int64_t b0 = 0; b0 < deg; b0 += AGG_ROW_BLOCK) {
-          const float4 p = chain_one(e0 + b0, (int)(deg - b0 < AGG_ROW_BLOCK ? deg - b0 : AGG_ROW_BLOCK));
+        for (int64_t b0 = 0; b0 < deg; b0 += ROW_BLOCK) {
+          const float4 p = chain_one(e0 + b0, (int)(deg - b0 < ROW_BLOCK ? deg - b0 : ROW_BLOCK));
           if (b0) {
             tot.x = __fadd_rn(tot.x, p.x); tot.y = __fadd_rn(tot.y, p.y); tot.z = __fadd_rn(tot.z, p.z); tot.w = __fadd_rn(tot.w, p.w);
           } else {

@@ -12,18 +12,25 @@
 // every neighbour gather is a single coalesced 1 KiB wave-instruction), edges are consumed four at a time so four
 // row gathers are in flight per wave, and bias / activation / residual are fused into the store.  No atomics: the
 // sum is one fmaf chain in CSR order, deterministic and bit-identical to the oracle.
-#include "common.h"
-
-namespace ragraph {
-
-// Rows longer than ROW_BLOCK edges (the hubs of a power-law graph) are summed in blocks: each block of ROW_BLOCK
+//
+// Rows longer than ROW_BLOCK edges (common.h; the hubs of a power-law graph) are summed in blocks: each block of ROW_BLOCK
 // consecutive edges is its own sequential chain from +0 and the block sums are added in block order -- the order
 // oracle/ragraph_oracle.c uses (ORACLE_ROW_BLOCK).  One chain over the 3 M edges of c5's most popular item kept a
-// single lane group busy for 31 ms per layer while the chip idled; with a workspace the blocks of long rows are
-// separate tasks for the whole chip (long_rows_kernel lists them, spmm_long_blocks_kernel sums them,
-// spmm_long_finish_kernel adds a row's block sums in order and applies the epilogue).  Without a workspace the row's
-// lane group walks its blocks itself: same bits, no parallelism.
-constexpr int ROW_BLOCK = 4096;
+// single lane group busy for 31 ms per layer while the chip idled.  There is ONE long-row path, with three users -- the
+// full product (ragraph_spmm_csr_ws_f32 and its device-slope form), the segment softmax (ragraph_segment_softmax_ws_f32)
+// and the row-subset product (ragraph_spmm_csr_rows_f32):
+//   * without a workspace a row's own lanes walk its blocks (row_sum_in_blocks): same bits, no parallelism;
+//   * with one, prepare_long_rows checks it, lays it out (long_rows_layout, fed by full_capacity or subset_capacity),
+//     clears the two counters and launches the lister (long_rows_kernel over all rows, rows_long_kernel over the
+//     requests); the blocks of the listed rows are then tasks for the whole chip (spmm_long_blocks_kernel) and
+//     spmm_long_finish_kernel adds a row's block sums in block order (block_sums_in_order) and stores them, with the
+//     epilogue for the full product, at the request's position for the subset.  The softmax reads the same lists.
+// The SpMM launch sites pick the lane-group width through with_lane_group.
+#include "common.h"
+
+#include <type_traits>
+
+namespace ragraph {
 
 // A row's edges are consumed in chunks of CH = 16: the first lanes of the row's lane group load the chunk's (col, val)
 // pairs with ONE coalesced load each, the group broadcasts them, and all gathers of the chunk are issued back to back
@@ -63,6 +70,31 @@ __device__ __forceinline__ float4 row_chain(const int32_t* __restrict__ col, con
 
 __device__ __forceinline__ float4 add4(float4 a, float4 b) {
   return make_float4(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y), __fadd_rn(a.z, b.z), __fadd_rn(a.w, b.w));
+}
+
+// A whole row's sum for one c4 column piece, by the row's own lane group: the first ROW_BLOCK edges as one chain, then
+// every further block as its own chain from +0, added in block order.
+template <int LPR>
+__device__ __forceinline__ float4 row_sum_in_blocks(const int32_t* col, const float* val, int64_t e0, int64_t deg,
+                                                    const float4* X4, int D4, int c4, bool colok, int lr, int gbase) {
+  float4 acc;
+  if (deg <= ROW_BLOCK) {
+    acc = row_chain<LPR>(col, val, e0, (int)deg, X4, D4, c4, colok, lr, gbase);
+  } else {
+    acc = row_chain<LPR>(col, val, e0, ROW_BLOCK, X4, D4, c4, colok, lr, gbase);
+    for (int64_t b0 = ROW_BLOCK; b0 < deg; b0 += ROW_BLOCK) {
+      const int cnt = deg - b0 < ROW_BLOCK ? (int)(deg - b0) : ROW_BLOCK;
+      acc = add4(acc, row_chain<LPR>(col, val, e0 + b0, cnt, X4, D4, c4, colok, lr, gbase));
+    }
+  }
+  return acc;
+}
+
+// The same sum from block sums that are already there: partial rows p .. p + nb - 1, in block order.
+__device__ __forceinline__ float4 block_sums_in_order(const float4* __restrict__ P4, int64_t p, int nb, int D4, int c4) {
+  float4 acc = P4[p * D4 + c4];
+  for (int b = 1; b < nb; ++b) acc = add4(acc, P4[(p + b) * D4 + c4]);
+  return acc;
 }
 
 // panel_n > 0: Y is PANEL-major -- [D / 32][panel_n][32] floats (a row's eight-float4 pieces of one 128-byte line go to the
@@ -128,16 +160,8 @@ __global__ void __launch_bounds__(256) spmm_csr_kernel(const int64_t* __restrict
 
   for (int c4 = lr; c4 < ((D4 + LPR - 1) / LPR) * LPR; c4 += LPR) {  // uniform trip count: shuffles inside
     const bool colok = c4 < D4;
-    float4 acc;
-    if (deg <= ROW_BLOCK) {
-      acc = row_chain<LPR>(col, val, e0, (int)deg, X4, D4, c4, colok, lr, gbase);
-    } else {  // no workspace: this group walks the row's blocks itself
-      acc = row_chain<LPR>(col, val, e0, ROW_BLOCK, X4, D4, c4, colok, lr, gbase);
-      for (int64_t b0 = ROW_BLOCK; b0 < deg; b0 += ROW_BLOCK) {
-        const int cnt = deg - b0 < ROW_BLOCK ? (int)(deg - b0) : ROW_BLOCK;
-        acc = add4(acc, row_chain<LPR>(col, val, e0 + b0, cnt, X4, D4, c4, colok, lr, gbase));
-      }
-    }
+    // (more than one block only without a workspace: this group walks the row's blocks itself)
+    const float4 acc = row_sum_in_blocks<LPR>(col, val, e0, deg, X4, D4, c4, colok, lr, gbase);
     if (!live || !colok) continue;
     spmm_epilogue_store(acc, bias, act, alpha, beta, Yin, Y, row, D4, c4, panel_n, DEV ? Z : nullptr);
   }
@@ -311,14 +335,25 @@ __global__ void __launch_bounds__(1024) spmm_tiled_kernel(TilePlan t, int64_t n,
 
 // ---- long rows, with a workspace ------------------------------------------------------------------------------------
 struct LongRows {
-  int* ctr;           // [0] number of long rows, [1] number of block tasks
-  int64_t* rows;      // [max_rows]  row index of long row i
-  int* pos;           // [max_rows]  first task / partial slot of long row i (its blocks follow in order)
-  int64_t* task_row;  // [max_tasks]
+  int* ctr;           // [0] number of listed rows, [1] number of block tasks
+  int64_t* rows;      // [max_rows]  listed entry i: a matrix row (full product, softmax) or a REQUEST index (row subset)
+  int* pos;           // [max_rows]  first task / partial slot of listed entry i (its blocks follow in order)
+  int64_t* task_row;  // [max_tasks] matrix row of the task
   int* task_blk;      // [max_tasks]
   float* partial;     // [max_tasks, D] block sums (spmm) / [max_tasks] (softmax)
   int64_t max_rows, max_tasks;
 };
+
+// Lists `listed` (whose matrix row is `row`) with the nb tasks it reserved at p .. p + nb - 1.
+__device__ __forceinline__ void list_long_row(const LongRows& w, int64_t listed, int64_t row, int p, int nb) {
+  const int li = atomicAdd(w.ctr, 1);
+  w.rows[li] = listed;
+  w.pos[li] = p;
+  for (int b = 0; b < nb; ++b) {
+    w.task_row[p + b] = row;
+    w.task_blk[p + b] = b;
+  }
+}
 
 // One thread per row: a long row reserves its task slots (a contiguous range, so its blocks stay in order; which range
 // is decided by atomics and does not matter) and writes its tasks.
@@ -328,14 +363,7 @@ __global__ void __launch_bounds__(256) long_rows_kernel(const int64_t* __restric
   const int64_t deg = rowptr[row + 1] - rowptr[row];
   if (deg <= ROW_BLOCK) return;
   const int nb = (int)((deg + ROW_BLOCK - 1) / ROW_BLOCK);
-  const int li = atomicAdd(w.ctr, 1);
-  const int p = atomicAdd(w.ctr + 1, nb);
-  w.rows[li] = row;
-  w.pos[li] = p;
-  for (int b = 0; b < nb; ++b) {
-    w.task_row[p + b] = row;
-    w.task_blk[p + b] = b;
-  }
+  list_long_row(w, row, row, atomicAdd(w.ctr + 1, nb), nb);
 }
 
 // One lane group per (long row, block): the block's chain -> partial[task].
@@ -368,9 +396,13 @@ __global__ void __launch_bounds__(256) spmm_long_blocks_kernel(const int64_t* __
   }
 }
 
-// One lane group per long row: its block sums in block order, then the epilogue (DEV: as spmm_csr_kernel).
+// One lane group per listed entry: its block sums in block order, then the epilogue (DEV: as spmm_csr_kernel).
+// requests == nullptr, the full product: the entry is a matrix row, written at that row.  Otherwise the row subset: the
+// entry is a request index r, the matrix row is requests[r] and the sum goes to Y[r] (the caller passes no bias,
+// RAGRAPH_ACT_NONE, no Yin and no Z: apply_act(x, NONE, .) is x, so the block sums are stored as they are).
 template <int LPR, bool DEV = false>
-__global__ void __launch_bounds__(256) spmm_long_finish_kernel(const int64_t* __restrict__ rowptr, int D,
+__global__ void __launch_bounds__(256) spmm_long_finish_kernel(const int64_t* __restrict__ rowptr,
+                                                               const int64_t* __restrict__ requests, int D,
                                                                const float* __restrict__ bias, int act, float alpha,
                                                                float beta, const float* __restrict__ Yin,
                                                                float* __restrict__ Y, LongRows w,
@@ -381,16 +413,87 @@ __global__ void __launch_bounds__(256) spmm_long_finish_kernel(const int64_t* __
   const int lr = threadIdx.x % LPR;
   const int64_t li = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
   if (li >= w.ctr[0]) return;
-  const int64_t row = w.rows[li];
+  const int64_t out = w.rows[li];
+  const int64_t row = requests ? requests[out] : out;
   const int64_t deg = rowptr[row + 1] - rowptr[row];
   const int nb = (int)((deg + ROW_BLOCK - 1) / ROW_BLOCK);
   const int64_t p = w.pos[li];
   const int D4 = D >> 2;
   const float4* P4 = reinterpret_cast<const float4*>(w.partial);
-  for (int c4 = lr; c4 < D4; c4 += LPR) {
-    float4 acc = P4[p * D4 + c4];
-    for (int b = 1; b < nb; ++b) acc = add4(acc, P4[(p + b) * D4 + c4]);
-    spmm_epilogue_store(acc, bias, act, alpha, beta, Yin, Y, row, D4, c4, 0, DEV ? Z : nullptr);
+  for (int c4 = lr; c4 < D4; c4 += LPR)
+    spmm_epilogue_store(block_sums_in_order(P4, p, nb, D4, c4), bias, act, alpha, beta, Yin, Y, out, D4, c4, 0,
+                        DEV ? Z : nullptr);
+}
+
+// ---- row subset: Y[r, :] = (A X)[rows[r], :] -----------------------------------------------------------------------
+// The edge flavour's training step reads the last propagation layer at the batch's rows only (RAGraph_edge/modules/
+// RAGraph.py:232-240 summed at :327, read at :343-345): a few thousand rows of millions.  One lane group per REQUEST walks
+// the requested row with row_sum_in_blocks -- the sum of spmm_csr_kernel, so the bits are those of the full product at that
+// row.  Hub rows: with a workspace a request for a row of more than ROW_BLOCK edges reserves one task per block
+// (rows_long_kernel; the blocks kernel above sums them, spmm_long_finish_kernel adds a request's block sums in block order).
+// How many blocks the requests hold is only known on the device: the area takes R + nnz / ROW_BLOCK + 1 block sums, which is
+// enough for distinct rows; a request whose blocks do not fit (duplicated hubs) keeps slot -1 and is walked by its own lanes.
+
+// One thread per request.  slot[r] = the first task of request r, or -1 (short, outside [0, n), or no room).  The
+// reservation is a compare-and-swap on the task counter: it only ever moves by a reservation that fits, so the tasks
+// [0, ctr[1]) are all written and ctr[1] <= max_tasks.  (Which request gets which range does not reach the result.)
+__global__ void __launch_bounds__(256) rows_long_kernel(const int64_t* __restrict__ rowptr, int64_t n,
+                                                        const int64_t* __restrict__ rows, int64_t R, int* __restrict__ slot,
+                                                        LongRows w) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  int s = -1;
+  const int64_t row = rows[r];
+  if (row >= 0 && row < n) {
+    const int64_t deg = rowptr[row + 1] - rowptr[row];
+    if (deg > ROW_BLOCK) {
+      const int64_t nb = (deg + ROW_BLOCK - 1) / ROW_BLOCK;
+      int cur = __atomic_load_n(w.ctr + 1, __ATOMIC_RELAXED);
+      while ((int64_t)cur + nb <= w.max_tasks) {
+        const int prev = atomicCAS(w.ctr + 1, cur, cur + (int)nb);
+        if (prev == cur) {
+          s = cur;
+          break;
+        }
+        cur = prev;
+      }
+      // (every reservation holds >= 2 tasks: at most max_tasks / 2 < max_rows entries are listed)
+      if (s >= 0) list_long_row(w, r, row, s, (int)nb);
+    }
+  }
+  slot[r] = s;
+}
+
+// One lane group per request.  slot == nullptr: no workspace, a hub row's group walks its blocks itself.
+template <int LPR>
+__global__ void __launch_bounds__(256) spmm_rows_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                        const float* __restrict__ val, int64_t n,
+                                                        const float* __restrict__ X, int D,
+                                                        const int64_t* __restrict__ rows, int64_t R,
+                                                        const int* __restrict__ slot, float* __restrict__ Y) {
+  constexpr int RPB = 256 / LPR;
+  const int lr = threadIdx.x % LPR;
+  const int gbase = (threadIdx.x & 63) - lr;
+  const int64_t r = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
+  const bool live = r < R;   // dead groups run along with zero edges
+  const int64_t row = live ? rows[r] : -1;
+  int64_t e0 = 0, deg = 0;
+  if (row >= 0 && row < n) {   // a row outside the matrix is an empty row: zeros
+    e0 = rowptr[row];
+    deg = rowptr[row + 1] - e0;
+  }
+  bool mine = live;
+  if (slot && deg > ROW_BLOCK && slot[r] >= 0) {   // its blocks are tasks of the long-row kernels
+    mine = false;
+    deg = 0;
+  }
+  const int D4 = D >> 2;
+  const float4* X4 = reinterpret_cast<const float4*>(X);
+  for (int c4 = lr; c4 < ((D4 + LPR - 1) / LPR) * LPR; c4 += LPR) {
+    const bool colok = c4 < D4;
+    const float4 acc = row_sum_in_blocks<LPR>(col, val, e0, deg, X4, D4, c4, colok, lr, gbase);
+    if (!mine || !colok) continue;
+    reinterpret_cast<float4*>(Y)[r * D4 + c4] = acc;
   }
 }
 
@@ -531,46 +634,99 @@ __global__ void __launch_bounds__(256) segment_reduce_scalar_kernel(const float*
 
 using namespace ragraph;
 
-// Workspace of the long-row path: counters, long-row list, block tasks, block sums.
-static size_t long_rows_layout(int64_t nnz, int D, LongRows* w, char* base) {
-  const int64_t max_rows = nnz / ROW_BLOCK + 1, max_tasks = 2 * (nnz / ROW_BLOCK) + 2;
+// ---- the long-row workspace ---------------------------------------------------------------------------------------------
+// How many listed rows and block tasks an area holds.  Full product and softmax: every row of the matrix may be listed, a
+// row of deg > ROW_BLOCK edges has at most deg / ROW_BLOCK + 1 blocks.  Row subset: what the requests hold is only known
+// on the device, so the lister never reserves past max_tasks; a reservation is at least two tasks.
+struct LongRowsCapacity {
+  int64_t max_rows, max_tasks;
+};
+static LongRowsCapacity full_capacity(int64_t nnz) { return {nnz / ROW_BLOCK + 1, 2 * (nnz / ROW_BLOCK) + 2}; }
+static LongRowsCapacity subset_capacity(int64_t nnz, int64_t R) {
+  const int64_t max_tasks = R + nnz / ROW_BLOCK + 1;
+  return {max_tasks / 2 + 1, max_tasks};
+}
+
+// The one layout: counters, per-request slots (request_slots > 0: the row subset), listed rows, block tasks, block sums of
+// partial_floats floats per task.  Every piece starts on a multiple of 256 bytes.  base == nullptr: the size only.
+static size_t long_rows_layout(LongRowsCapacity cap, int partial_floats, int64_t request_slots, char* base, LongRows* w,
+                               int** slot) {
   size_t off = 0;
-  auto take = [&](size_t bytes) {
+  auto take = [&](size_t count, size_t size) {
     char* p = base ? base + off : nullptr;
-    off += align_up(bytes, 256);
+    off += align_up(count * size, 256);
     return p;
   };
-  char* c = take(2 * sizeof(int));
-  char* r = take((size_t)max_rows * sizeof(int64_t));
-  char* ps = take((size_t)max_rows * sizeof(int));
-  char* tr = take((size_t)max_tasks * sizeof(int64_t));
-  char* tb = take((size_t)max_tasks * sizeof(int));
-  char* pa = take((size_t)max_tasks * (size_t)(D > 0 ? D : 1) * sizeof(float));
-  if (w) {
-    w->ctr = reinterpret_cast<int*>(c);
-    w->rows = reinterpret_cast<int64_t*>(r);
-    w->pos = reinterpret_cast<int*>(ps);
-    w->task_row = reinterpret_cast<int64_t*>(tr);
-    w->task_blk = reinterpret_cast<int*>(tb);
-    w->partial = reinterpret_cast<float*>(pa);
-    w->max_rows = max_rows;
-    w->max_tasks = max_tasks;
-  }
+  LongRows l{};
+  l.ctr = reinterpret_cast<int*>(take(2, sizeof(int)));
+  int* sl = request_slots > 0 ? reinterpret_cast<int*>(take((size_t)request_slots, sizeof(int))) : nullptr;
+  l.rows = reinterpret_cast<int64_t*>(take((size_t)cap.max_rows, sizeof(int64_t)));
+  l.pos = reinterpret_cast<int*>(take((size_t)cap.max_rows, sizeof(int)));
+  l.task_row = reinterpret_cast<int64_t*>(take((size_t)cap.max_tasks, sizeof(int64_t)));
+  l.task_blk = reinterpret_cast<int*>(take((size_t)cap.max_tasks, sizeof(int)));
+  l.partial = reinterpret_cast<float*>(take((size_t)cap.max_tasks * (size_t)partial_floats, sizeof(float)));
+  l.max_rows = cap.max_rows;
+  l.max_tasks = cap.max_tasks;
+  if (w) *w = l;
+  if (slot) *slot = sl;
   return off;
 }
 
 extern "C" size_t ragraph_sparse_workspace_bytes(int64_t nnz, int D) {
   if (nnz < 0 || D < 0) return 0;
-  return long_rows_layout(nnz, D, nullptr, nullptr);
+  return long_rows_layout(full_capacity(nnz), D > 0 ? D : 1, 0, nullptr, nullptr, nullptr);
 }
 
-static int find_long_rows(const int64_t* rowptr, int64_t n, const LongRows& w, hipStream_t st) {
-  if (hipMemsetAsync(w.ctr, 0, 2 * sizeof(int), st) != hipSuccess) {
-    set_error("sparse: memset failed");
+extern "C" size_t ragraph_spmm_csr_rows_workspace_bytes(int64_t nnz, int64_t R, int D) {
+  if (nnz < 0 || R < 0 || D < 1 || R + nnz / ROW_BLOCK + 1 >= (int64_t)INT_MAX) return 0;
+  return long_rows_layout(subset_capacity(nnz, R), D, R > 0 ? R : 1, nullptr, nullptr, nullptr);
+}
+
+// What every entry with a workspace does before its own kernels: check the workspace, lay it out, clear the two counters
+// and launch the lister -- over all n rows (requests == nullptr), or over the R requests, whose slots it also fills.
+static int prepare_long_rows(const char* who, LongRowsCapacity cap, int partial_floats, void* ws, size_t ws_bytes,
+                             const int64_t* rowptr, int64_t n, const int64_t* requests, int64_t R, hipStream_t st,
+                             LongRows* w, int** slot) {
+  const int64_t request_slots = requests ? (R > 0 ? R : 1) : 0;
+  const size_t need = long_rows_layout(cap, partial_floats, request_slots, nullptr, nullptr, nullptr);
+  RG_REQUIRE(aligned16(ws) && ws_bytes >= need, RAGRAPH_EWORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, need);
+  long_rows_layout(cap, partial_floats, request_slots, static_cast<char*>(ws), w, slot);
+  if (hipMemsetAsync(w->ctr, 0, 2 * sizeof(int), st) != hipSuccess) {
+    set_error("%s: memset failed", who);
     return RAGRAPH_EDEVICE;
   }
-  hipLaunchKernelGGL(long_rows_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, rowptr, n, w);
-  RG_CHECK_LAUNCH("sparse(long rows)");
+  if (requests)
+    hipLaunchKernelGGL(rows_long_kernel, dim3((unsigned)cdiv(R, 256)), dim3(256), 0, st, rowptr, n, requests, R, *slot, *w);
+  else
+    hipLaunchKernelGGL(long_rows_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, rowptr, n, *w);
+  RG_CHECK_LAUNCH(who);
+  return RAGRAPH_OK;
+}
+
+// The lane group that holds one output row: the narrowest of 16, 32 and 64 lanes (a float4 each) that covers D4 = D / 4, 64
+// beyond.  f is called with std::integral_constant<int, lanes>.
+template <typename F>
+static void with_lane_group(int D4, F&& f) {
+  if (D4 <= 16) f(std::integral_constant<int, 16>{});
+  else if (D4 <= 32) f(std::integral_constant<int, 32>{});
+  else f(std::integral_constant<int, 64>{});
+}
+
+// Workgroups of one XCD's contiguous run (see spmm_csr_kernel).
+static unsigned xcd_run() {
+  static const unsigned run = [] {
+    const char* e = getenv("RAGRAPH_SPMM_XCD_RUN");
+    const int v = e ? atoi(e) : 32;
+    return (unsigned)(v < 1 ? 1 : v);
+  }();
+  return run;
+}
+
+// The argument checks the SpMM entries share.
+static int check_spmm_args(const char* who, int D, const float* X, const float* Y, int act) {
+  RG_REQUIRE(D >= 4 && (D & 3) == 0, RAGRAPH_EINVAL, "%s: D=%d must be a positive multiple of 4", who, D);
+  RG_REQUIRE(aligned16(X) && aligned16(Y) && X != Y, RAGRAPH_EINVAL, "%s: X, Y must be 16-B aligned and distinct", who);
+  RG_REQUIRE(act >= RAGRAPH_ACT_NONE && act <= RAGRAPH_ACT_ELU, RAGRAPH_EINVAL, "%s: bad act %d", who, act);
   return RAGRAPH_OK;
 }
 
@@ -581,11 +737,10 @@ static int spmm_csr_launch(const int64_t* rowptr, const int32_t* col, const floa
                            const float* bias, int act, float alpha, float beta, const float* Y_in, float* Y, int64_t nnz,
                            void* ws, size_t ws_bytes, const float* alpha_dev, float* Z, void* stream) {
   RG_REQUIRE(rowptr && X && Y, RAGRAPH_EINVAL, "spmm_csr: null pointer");
-  RG_REQUIRE(n >= 0 && D >= 4 && (D & 3) == 0, RAGRAPH_EINVAL, "spmm_csr: D=%d must be a positive multiple of 4", D);
-  RG_REQUIRE(aligned16(X) && aligned16(Y) && (!bias || aligned16(bias)) && (!Y_in || aligned16(Y_in)), RAGRAPH_EINVAL,
-             "spmm_csr: X, Y, bias, Y_in must be 16-B aligned");
-  RG_REQUIRE(X != Y, RAGRAPH_EINVAL, "spmm_csr: Y must not alias X");
-  RG_REQUIRE(act >= RAGRAPH_ACT_NONE && act <= RAGRAPH_ACT_ELU, RAGRAPH_EINVAL, "spmm_csr: bad act %d", act);
+  RG_REQUIRE(n >= 0, RAGRAPH_EINVAL, "spmm_csr: n=%lld", (long long)n);
+  if (const int rc = check_spmm_args("spmm_csr", D, X, Y, act)) return rc;
+  RG_REQUIRE((!bias || aligned16(bias)) && (!Y_in || aligned16(Y_in)), RAGRAPH_EINVAL,
+             "spmm_csr: bias, Y_in must be 16-B aligned");
   if (DEV) {
     RG_REQUIRE(alpha_dev, RAGRAPH_EINVAL, "spmm_csr_prelu_dev: null slope pointer");
     RG_REQUIRE(!Z || (aligned16(Z) && Z != X && Z != Y), RAGRAPH_EINVAL,
@@ -596,35 +751,21 @@ static int spmm_csr_launch(const int64_t* rowptr, const int32_t* col, const floa
   LongRows w{};
   const bool par = ws != nullptr && nnz > ROW_BLOCK;  // (no row can be long otherwise)
   if (par) {
-    RG_REQUIRE(aligned16(ws) && ws_bytes >= long_rows_layout(nnz, D, nullptr, nullptr), RAGRAPH_EWORKSPACE,
-               "spmm_csr: workspace %zu < %zu", ws_bytes, long_rows_layout(nnz, D, nullptr, nullptr));
-    long_rows_layout(nnz, D, &w, static_cast<char*>(ws));
-    const int rc = find_long_rows(rowptr, n, w, st);
-    if (rc != RAGRAPH_OK) return rc;
+    if (const int rc = prepare_long_rows("spmm_csr", full_capacity(nnz), D, ws, ws_bytes, rowptr, n, nullptr, 0, st, &w,
+                                         nullptr))
+      return rc;
   }
-  const int skip = par ? 1 : 0;
-  const int D4 = D >> 2;
-  static const unsigned xcd_run = [] {  // workgroups of one XCD's contiguous run (see spmm_csr_kernel)
-    const char* e = getenv("RAGRAPH_SPMM_XCD_RUN");
-    const int v = e ? atoi(e) : 32;
-    return (unsigned)(v < 1 ? 1 : v);
-  }();
-#define RG_SPMM(LPR_)                                                                                                  \
-  do {                                                                                                                 \
-    constexpr int RPB_ = 256 / (LPR_);                                                                                 \
-    hipLaunchKernelGGL((spmm_csr_kernel<LPR_, DEV>), dim3((unsigned)cdiv(n, RPB_)), dim3(256), 0, st, rowptr, col, val,\
-                       n, X, D, bias, act, alpha, beta, Y_in, Y, skip, xcd_run, (int64_t)0, alpha_dev, Z);             \
-    if (par) {                                                                                                         \
-      hipLaunchKernelGGL(spmm_long_blocks_kernel<LPR_>, dim3((unsigned)cdiv(w.max_tasks, RPB_)), dim3(256), 0, st,     \
-                         rowptr, col, val, X, D, w);                                                                   \
-      hipLaunchKernelGGL((spmm_long_finish_kernel<LPR_, DEV>), dim3((unsigned)cdiv(w.max_rows, RPB_)), dim3(256), 0,   \
-                         st, rowptr, D, bias, act, alpha, beta, Y_in, Y, w, alpha_dev, Z);                             \
-    }                                                                                                                  \
-  } while (0)
-  if (D4 <= 16) RG_SPMM(16);
-  else if (D4 <= 32) RG_SPMM(32);
-  else RG_SPMM(64);
-#undef RG_SPMM
+  with_lane_group(D >> 2, [&](auto lanes) {
+    constexpr int LPR = decltype(lanes)::value, RPB = 256 / LPR;
+    hipLaunchKernelGGL((spmm_csr_kernel<LPR, DEV>), dim3((unsigned)cdiv(n, RPB)), dim3(256), 0, st, rowptr, col, val, n, X,
+                       D, bias, act, alpha, beta, Y_in, Y, par ? 1 : 0, xcd_run(), (int64_t)0, alpha_dev, Z);
+    if (par) {
+      hipLaunchKernelGGL(spmm_long_blocks_kernel<LPR>, dim3((unsigned)cdiv(w.max_tasks, RPB)), dim3(256), 0, st, rowptr,
+                         col, val, X, D, w);
+      hipLaunchKernelGGL((spmm_long_finish_kernel<LPR, DEV>), dim3((unsigned)cdiv(w.max_rows, RPB)), dim3(256), 0, st,
+                         rowptr, (const int64_t*)nullptr, D, bias, act, alpha, beta, Y_in, Y, w, alpha_dev, Z);
+    }
+  });
   RG_CHECK_LAUNCH("spmm_csr");
   return RAGRAPH_OK;
 }
@@ -657,27 +798,18 @@ extern "C" int ragraph_spmm_csr_panels_f32(const int64_t* rowptr, const int32_t*
   RG_REQUIRE(x_rows >= 1, RAGRAPH_EINVAL, "spmm_csr_panels: x_rows=%lld", (long long)x_rows);
   RG_REQUIRE(n >= 1 && (D == 64 || D == 128 || D == 256 || (D % 256 == 0 && D <= 2048)), RAGRAPH_EUNSUPPORTED,
              "spmm_csr_panels: D=%d (panels of 32 columns: 2, 4 or a multiple of 8 of them)", D);
-  RG_REQUIRE(aligned16(X) && aligned16(Y) && X != Y, RAGRAPH_EINVAL, "spmm_csr_panels: X, Y must be 16-B aligned and distinct");
-  RG_REQUIRE(act >= RAGRAPH_ACT_NONE && act <= RAGRAPH_ACT_ELU, RAGRAPH_EINVAL, "spmm_csr_panels: bad act %d", act);
+  if (const int rc = check_spmm_args("spmm_csr_panels", D, X, Y, act)) return rc;
   hipStream_t st = as_stream(stream);
   const int P = D / 32;
   // row-major in: the XCD-sliced kernel reading its 128-byte slice of every row (RAGRAPH_SPMM_ROW_SLICES=0: the row kernel)
   static const bool row_slices = [] { const char* e = getenv("RAGRAPH_SPMM_ROW_SLICES"); return !e || atoi(e) != 0; }();
   if (!x_panels && !row_slices) {  // the row kernel, storing row-major or panel-major
-    static const unsigned xcd_run = [] {
-      const char* e = getenv("RAGRAPH_SPMM_XCD_RUN");
-      const int v = e ? atoi(e) : 32;
-      return (unsigned)(v < 1 ? 1 : v);
-    }();
-    const int D4 = D >> 2;
     const int64_t pn = y_panels ? n : 0;
-#define RG_SPMM_P(LPR_)                                                                                                     \
-  hipLaunchKernelGGL(spmm_csr_kernel<LPR_>, dim3((unsigned)cdiv(n, 256 / (LPR_))), dim3(256), 0, st, rowptr, col, val, n, X, D, \
-                     (const float*)nullptr, act, alpha, 0.f, (const float*)nullptr, Y, 0, xcd_run, pn)
-    if (D4 <= 16) RG_SPMM_P(16);
-    else if (D4 <= 32) RG_SPMM_P(32);
-    else RG_SPMM_P(64);
-#undef RG_SPMM_P
+    with_lane_group(D >> 2, [&](auto lanes) {
+      constexpr int LPR = decltype(lanes)::value;
+      hipLaunchKernelGGL(spmm_csr_kernel<LPR>, dim3((unsigned)cdiv(n, 256 / LPR)), dim3(256), 0, st, rowptr, col, val, n, X,
+                         D, (const float*)nullptr, act, alpha, 0.f, (const float*)nullptr, Y, 0, xcd_run(), pn);
+    });
     RG_CHECK_LAUNCH("spmm_csr_panels");
     return RAGRAPH_OK;
   }
@@ -708,12 +840,10 @@ extern "C" int ragraph_segment_softmax_ws_f32(const int64_t* rowptr, const float
   hipStream_t st = as_stream(stream);
   LongRows w{};
   const bool par = ws != nullptr && nnz > ROW_BLOCK;
-  if (par) {
-    RG_REQUIRE(aligned16(ws) && ws_bytes >= long_rows_layout(nnz, 0, nullptr, nullptr), RAGRAPH_EWORKSPACE,
-               "segment_softmax: workspace %zu < %zu", ws_bytes, long_rows_layout(nnz, 0, nullptr, nullptr));
-    long_rows_layout(nnz, 0, &w, static_cast<char*>(ws));
-    const int rc = find_long_rows(rowptr, n, w, st);
-    if (rc != RAGRAPH_OK) return rc;
+  if (par) {  // one block sum per task
+    if (const int rc = prepare_long_rows("segment_softmax", full_capacity(nnz), 1, ws, ws_bytes, rowptr, n, nullptr, 0, st,
+                                         &w, nullptr))
+      return rc;
   }
   hipLaunchKernelGGL(segment_softmax_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, st, rowptr, x, n, out,
                      par ? 1 : 0);
@@ -771,195 +901,38 @@ extern "C" int ragraph_spmm_csr_tiled_f32(const int* wp, const int* col3, const 
   return RAGRAPH_OK;
 }
 
-// ---- row subset: Y[r, :] = (A X)[rows[r], :] -----------------------------------------------------------------------
-// The edge flavour's training step reads the last propagation layer at the batch's rows only (RAGraph_edge/modules/
-// RAGraph.py:232-240 summed at :327, read at :343-345): a few thousand rows of millions.  One lane group per REQUEST walks
-// the requested row with row_chain -- the chain of spmm_csr_kernel, so the bits are those of the full product at that row.
-// Hub rows: with a workspace a request for a row of more than ROW_BLOCK edges reserves one task per block (rows_long_kernel;
-// the blocks kernel above sums them, spmm_rows_finish_kernel adds a request's block sums in block order).  How many blocks
-// the requests hold is only known on the device: the area takes R + nnz / ROW_BLOCK + 1 block sums, which is enough for
-// distinct rows; a request whose blocks do not fit (duplicated hubs) keeps slot -1 and is walked by its own lane group.
-namespace ragraph {
-
-// One thread per request.  slot[r] = the first task of request r, or -1 (short, outside [0, n), or no room).  The
-// reservation is a compare-and-swap on the task counter: it only ever moves by a reservation that fits, so the tasks
-// [0, ctr[1]) are all written and ctr[1] <= max_tasks.  (Which request gets which range does not reach the result.)
-__global__ void __launch_bounds__(256) rows_long_kernel(const int64_t* __restrict__ rowptr, int64_t n,
-                                                        const int64_t* __restrict__ rows, int64_t R, int* __restrict__ slot,
-                                                        LongRows w) {
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r >= R) return;
-  int s = -1;
-  const int64_t row = rows[r];
-  if (row >= 0 && row < n) {
-    const int64_t deg = rowptr[row + 1] - rowptr[row];
-    if (deg > ROW_BLOCK) {
-      const int64_t nb = (deg + ROW_BLOCK - 1) / ROW_BLOCK;
-      int cur = __atomic_load_n(w.ctr + 1, __ATOMIC_RELAXED);
-      while ((int64_t)cur + nb <= w.max_tasks) {
-        const int prev = atomicCAS(w.ctr + 1, cur, cur + (int)nb);
-        if (prev == cur) {
-          s = cur;
-          break;
-        }
-        cur = prev;
-      }
-      if (s >= 0) {
-        const int li = atomicAdd(w.ctr, 1);   // (every reservation holds >= 2 tasks: li < max_tasks / 2 + 1 = max_rows)
-        w.rows[li] = r;
-        w.pos[li] = s;
-        for (int b = 0; b < (int)nb; ++b) {
-          w.task_row[s + b] = row;
-          w.task_blk[s + b] = b;
-        }
-      }
-    }
-  }
-  slot[r] = s;
-}
-
-// One lane group per request.  slot == nullptr: no workspace, a hub row's group walks its blocks itself.
-template <int LPR>
-__global__ void __launch_bounds__(256) spmm_rows_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                                        const float* __restrict__ val, int64_t n,
-                                                        const float* __restrict__ X, int D,
-                                                        const int64_t* __restrict__ rows, int64_t R,
-                                                        const int* __restrict__ slot, float* __restrict__ Y) {
-  constexpr int RPB = 256 / LPR;
-  const int lr = threadIdx.x % LPR;
-  const int gbase = (threadIdx.x & 63) - lr;
-  const int64_t r = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-  const bool live = r < R;   // dead groups run along with zero edges
-  const int64_t row = live ? rows[r] : -1;
-  int64_t e0 = 0, deg = 0;
-  if (row >= 0 && row < n) {   // a row outside the matrix is an empty row: zeros
-    e0 = rowptr[row];
-    deg = rowptr[row + 1] - e0;
-  }
-  bool mine = live;
-  if (slot && deg > ROW_BLOCK && slot[r] >= 0) {   // its blocks are tasks of the long-row kernels
-    mine = false;
-    deg = 0;
-  }
-  const int D4 = D >> 2;
-  const float4* X4 = reinterpret_cast<const float4*>(X);
-  for (int c4 = lr; c4 < ((D4 + LPR - 1) / LPR) * LPR; c4 += LPR) {
-    const bool colok = c4 < D4;
-    float4 acc;
-    if (deg <= ROW_BLOCK) {
-      acc = row_chain<LPR>(col, val, e0, (int)deg, X4, D4, c4, colok, lr, gbase);
-    } else {
-      acc = row_chain<LPR>(col, val, e0, ROW_BLOCK, X4, D4, c4, colok, lr, gbase);
-      for (int64_t b0 = ROW_BLOCK; b0 < deg; b0 += ROW_BLOCK) {
-        const int cnt = deg - b0 < ROW_BLOCK ? (int)(deg - b0) : ROW_BLOCK;
-        acc = add4(acc, row_chain<LPR>(col, val, e0 + b0, cnt, X4, D4, c4, colok, lr, gbase));
-      }
-    }
-    if (!mine || !colok) continue;
-    reinterpret_cast<float4*>(Y)[r * D4 + c4] = acc;
-  }
-}
-
-// One lane group per listed request: its block sums in block order -> Y[request].
-template <int LPR>
-__global__ void __launch_bounds__(256) spmm_rows_finish_kernel(const int64_t* __restrict__ rowptr,
-                                                               const int64_t* __restrict__ rows, int D,
-                                                               float* __restrict__ Y, LongRows w) {
-  constexpr int RPB = 256 / LPR;
-  const int lr = threadIdx.x % LPR;
-  const int64_t li = (int64_t)blockIdx.x * RPB + threadIdx.x / LPR;
-  if (li >= w.ctr[0]) return;
-  const int64_t r = w.rows[li];
-  const int64_t row = rows[r];
-  const int64_t deg = rowptr[row + 1] - rowptr[row];
-  const int nb = (int)((deg + ROW_BLOCK - 1) / ROW_BLOCK);
-  const int64_t p = w.pos[li];
-  const int D4 = D >> 2;
-  const float4* P4 = reinterpret_cast<const float4*>(w.partial);
-  for (int c4 = lr; c4 < D4; c4 += LPR) {
-    float4 acc = P4[p * D4 + c4];
-    for (int b = 1; b < nb; ++b) acc = add4(acc, P4[(p + b) * D4 + c4]);
-    reinterpret_cast<float4*>(Y)[r * D4 + c4] = acc;
-  }
-}
-
-}  // namespace ragraph
-
-// Workspace of the row-subset product: per-request slots, then the long-row lists with rows[] = REQUEST indices.
-static size_t rows_layout(int64_t nnz, int64_t R, int D, int** slot, LongRows* w, char* base) {
-  const int64_t max_tasks = R + nnz / ROW_BLOCK + 1, max_rows = max_tasks / 2 + 1;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align_up(bytes, 256);
-    return p;
-  };
-  char* c = take(2 * sizeof(int));
-  char* sl = take((size_t)(R > 0 ? R : 1) * sizeof(int));
-  char* r = take((size_t)max_rows * sizeof(int64_t));
-  char* ps = take((size_t)max_rows * sizeof(int));
-  char* tr = take((size_t)max_tasks * sizeof(int64_t));
-  char* tb = take((size_t)max_tasks * sizeof(int));
-  char* pa = take((size_t)max_tasks * (size_t)D * sizeof(float));
-  if (slot) *slot = reinterpret_cast<int*>(sl);
-  if (w) {
-    w->ctr = reinterpret_cast<int*>(c);
-    w->rows = reinterpret_cast<int64_t*>(r);
-    w->pos = reinterpret_cast<int*>(ps);
-    w->task_row = reinterpret_cast<int64_t*>(tr);
-    w->task_blk = reinterpret_cast<int*>(tb);
-    w->partial = reinterpret_cast<float*>(pa);
-    w->max_rows = max_rows;
-    w->max_tasks = max_tasks;
-  }
-  return off;
-}
-
-extern "C" size_t ragraph_spmm_csr_rows_workspace_bytes(int64_t nnz, int64_t R, int D) {
-  if (nnz < 0 || R < 0 || D < 1 || R + nnz / ROW_BLOCK + 1 >= (int64_t)INT_MAX) return 0;
-  return rows_layout(nnz, R, D, nullptr, nullptr, nullptr);
-}
-
+// Y[r, :] = (A X)[rows[r], :].  A request whose hub row found no room in the area is walked by its own lane group
+// (spmm_rows_kernel), so the result never depends on the capacity.
 extern "C" int ragraph_spmm_csr_rows_f32(const int64_t* rowptr, const int32_t* col, const float* val, int64_t n,
                                          const float* X, int D, const int64_t* rows, int64_t R, float* Y, int64_t nnz,
                                          void* ws, size_t ws_bytes, void* stream) {
   RG_REQUIRE(rowptr && X && (R == 0 || (rows && Y)), RAGRAPH_EINVAL, "spmm_csr_rows: null pointer");
   RG_REQUIRE(n >= 0 && R >= 0 && nnz >= 0, RAGRAPH_EINVAL, "spmm_csr_rows: bad n/R/nnz");
-  RG_REQUIRE(D >= 4 && (D & 3) == 0, RAGRAPH_EINVAL, "spmm_csr_rows: D=%d must be a positive multiple of 4", D);
-  RG_REQUIRE(aligned16(X) && aligned16(Y) && X != Y, RAGRAPH_EINVAL, "spmm_csr_rows: X, Y must be 16-B aligned and distinct");
+  if (const int rc = check_spmm_args("spmm_csr_rows", D, X, Y, RAGRAPH_ACT_NONE)) return rc;
   if (R == 0) return RAGRAPH_OK;
   hipStream_t st = as_stream(stream);
   LongRows w{};
   int* slot = nullptr;
   const bool par = ws != nullptr && nnz > ROW_BLOCK;  // (no row can be long otherwise)
   if (par) {
-    const size_t need = ragraph_spmm_csr_rows_workspace_bytes(nnz, R, D);
-    RG_REQUIRE(need > 0, RAGRAPH_EUNSUPPORTED, "spmm_csr_rows: R + nnz / 4096 must fit int32");
-    RG_REQUIRE(aligned16(ws) && ws_bytes >= need, RAGRAPH_EWORKSPACE, "spmm_csr_rows: workspace %zu < %zu", ws_bytes, need);
-    rows_layout(nnz, R, D, &slot, &w, static_cast<char*>(ws));
-    if (hipMemsetAsync(w.ctr, 0, 2 * sizeof(int), st) != hipSuccess) {
-      set_error("spmm_csr_rows: memset failed");
-      return RAGRAPH_EDEVICE;
-    }
-    hipLaunchKernelGGL(rows_long_kernel, dim3((unsigned)cdiv(R, 256)), dim3(256), 0, st, rowptr, n, rows, R, slot, w);
+    RG_REQUIRE(ragraph_spmm_csr_rows_workspace_bytes(nnz, R, D) > 0, RAGRAPH_EUNSUPPORTED,
+               "spmm_csr_rows: R + nnz / 4096 must fit int32");
+    if (const int rc = prepare_long_rows("spmm_csr_rows", subset_capacity(nnz, R), D, ws, ws_bytes, rowptr, n, rows, R, st,
+                                         &w, &slot))
+      return rc;
   }
-#define RG_SPMM_ROWS(LPR_)                                                                                             \
-  do {                                                                                                                 \
-    constexpr int RPB_ = 256 / (LPR_);                                                                                 \
-    hipLaunchKernelGGL(spmm_rows_kernel<LPR_>, dim3((unsigned)cdiv(R, RPB_)), dim3(256), 0, st, rowptr, col, val, n,   \
-                       X, D, rows, R, (const int*)slot, Y);                                                           \
-    if (par) {                                                                                                         \
-      hipLaunchKernelGGL(spmm_long_blocks_kernel<LPR_>, dim3((unsigned)cdiv(w.max_tasks, RPB_)), dim3(256), 0, st,     \
-                         rowptr, col, val, X, D, w);                                                                   \
-      hipLaunchKernelGGL(spmm_rows_finish_kernel<LPR_>, dim3((unsigned)cdiv(w.max_rows, RPB_)), dim3(256), 0, st,      \
-                         rowptr, rows, D, Y, w);                                                                       \
-    }                                                                                                                  \
-  } while (0)
-  const int D4 = D >> 2;
-  if (D4 <= 16) RG_SPMM_ROWS(16);
-  else if (D4 <= 32) RG_SPMM_ROWS(32);
-  else RG_SPMM_ROWS(64);
-#undef RG_SPMM_ROWS
+  with_lane_group(D >> 2, [&](auto lanes) {
+    constexpr int LPR = decltype(lanes)::value, RPB = 256 / LPR;
+    hipLaunchKernelGGL(spmm_rows_kernel<LPR>, dim3((unsigned)cdiv(R, RPB)), dim3(256), 0, st, rowptr, col, val, n, X, D,
+                       rows, R, (const int*)slot, Y);
+    if (par) {
+      hipLaunchKernelGGL(spmm_long_blocks_kernel<LPR>, dim3((unsigned)cdiv(w.max_tasks, RPB)), dim3(256), 0, st, rowptr,
+                         col, val, X, D, w);
+      hipLaunchKernelGGL(spmm_long_finish_kernel<LPR>, dim3((unsigned)cdiv(w.max_rows, RPB)), dim3(256), 0, st, rowptr,
+                         rows, D, (const float*)nullptr, RAGRAPH_ACT_NONE, 0.f, 0.f, (const float*)nullptr, Y, w,
+                         (const float*)nullptr, (float*)nullptr);
+    }
+  });
   RG_CHECK_LAUNCH("spmm_csr_rows");
   return RAGRAPH_OK;
 }

@@ -847,6 +847,24 @@ LINEAR_TN_MIN_ROWS = 2048   # below: gY^T X through the dense kernel on transpos
 ROW_BLOCK = 4096  # rows / segments longer than this are summed in blocks (csrc/sparse.hip, oracle ORACLE_ROW_BLOCK)
 
 
+def _csr_args(who: str, rowptr, col, val, x):
+    """The CSR operands of an SpMM wrapper in the dtypes the library takes, with n, D and nnz."""
+    rowptr = _idxc(rowptr, f"{who}.rowptr")
+    col = _idxc(col, f"{who}.col", torch.int32)
+    val = _f32c(val, f"{who}.val")
+    x = _f32c(x, f"{who}.x")
+    return rowptr, col, val, x, rowptr.numel() - 1, x.shape[1], col.numel()
+
+
+def _hub_workspace(long_rows: bool, nnz: int, D: int, device):
+    """(pointer, bytes) of the hub-row workspace of the full product (D = 0: of the softmax); (None, 0) without long rows --
+    the `_ws` entries then leave a hub row to its own lanes, which is all the entries without a workspace do."""
+    if not long_rows:
+        return None, 0
+    ws = _workspace(_ready().ragraph_sparse_workspace_bytes(nnz, D), device)
+    return ws.data_ptr(), ws.numel()
+
+
 def spmm_csr(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, x: torch.Tensor,
              bias: torch.Tensor | None = None, act: int = ACT_NONE, alpha: float = 0.0, beta: float = 0.0,
              y_in: torch.Tensor | None = None, long_rows: bool = False) -> torch.Tensor:
@@ -854,24 +872,14 @@ def spmm_csr(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, x: torc
     `long_rows`: the graph has rows of more than ROW_BLOCK edges (CSRGraph.has_long_rows): their blocks are spread over
     the chip through a workspace -- same bits, three more launches."""
     L = _ready()
-    rowptr = _idxc(rowptr, "spmm_csr.rowptr")
-    col = _idxc(col, "spmm_csr.col", torch.int32)
-    val = _f32c(val, "spmm_csr.val")
-    x = _f32c(x, "spmm_csr.x")
-    n = rowptr.numel() - 1
-    D = x.shape[1]
+    rowptr, col, val, x, n, D, nnz = _csr_args("spmm_csr", rowptr, col, val, x)
     b = None if bias is None else _f32c(bias, "spmm_csr.bias")
     yi = None if y_in is None else _f32c(y_in, "spmm_csr.y_in")
     y = torch.empty((n, D), dtype=torch.float32, device=x.device)
-    if long_rows:
-        nnz = col.numel()
-        ws = _workspace(L.ragraph_sparse_workspace_bytes(nnz, D), x.device)
-        N.check(L.ragraph_spmm_csr_ws_f32(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), n, x.data_ptr(), D, _ptr(b),
-                                          act, float(alpha), float(beta), _ptr(yi), y.data_ptr(), nnz, ws.data_ptr(),
-                                          ws.numel(), _stream()), "spmm_csr")
-        return y
-    N.check(L.ragraph_spmm_csr_f32(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), n, x.data_ptr(), D, _ptr(b), act,
-                                   float(alpha), float(beta), _ptr(yi), y.data_ptr(), _stream()), "spmm_csr")
+    ws, ws_bytes = _hub_workspace(long_rows, nnz, D, x.device)
+    N.check(L.ragraph_spmm_csr_ws_f32(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), n, x.data_ptr(), D, _ptr(b), act,
+                                      float(alpha), float(beta), _ptr(yi), y.data_ptr(), nnz if long_rows else 0, ws,
+                                      ws_bytes, _stream()), "spmm_csr")
     return y
 
 
@@ -882,12 +890,9 @@ def spmm_csr_rows(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, x:
     returns [R, D], bit-identical to spmm_csr(...)[rows].  `long_rows`: as spmm_csr (the blocks of requested hub rows are
     spread over the chip through a workspace)."""
     L = _ready()
-    rowptr = _idxc(rowptr, "spmm_csr_rows.rowptr")
-    col = _idxc(col, "spmm_csr_rows.col", torch.int32)
-    val = _f32c(val, "spmm_csr_rows.val")
-    x = _f32c(x, "spmm_csr_rows.x")
+    rowptr, col, val, x, n, D, nnz = _csr_args("spmm_csr_rows", rowptr, col, val, x)
     rows = _idxc(rows, "spmm_csr_rows.rows").reshape(-1)
-    n, D, R, nnz = rowptr.numel() - 1, x.shape[1], rows.numel(), col.numel()
+    R = rows.numel()
     y = torch.empty((R, D), dtype=torch.float32, device=x.device)
     ws = None
     if long_rows:
@@ -933,11 +938,7 @@ def spmm_csr_panels(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, 
     the hops of a k-hop propagation between which the features never need to be row-major (ragraph_spmm_csr_panels_f32:
     an XCD gathers from one panel; same bits as spmm_csr in every layout)."""
     L = _ready()
-    rowptr = _idxc(rowptr, "spmm_csr_panels.rowptr")
-    col = _idxc(col, "spmm_csr_panels.col", torch.int32)
-    val = _f32c(val, "spmm_csr_panels.val")
-    x = _f32c(x, "spmm_csr_panels.x")
-    n, D = rowptr.numel() - 1, x.shape[1]
+    rowptr, col, val, x, n, D, _ = _csr_args("spmm_csr_panels", rowptr, col, val, x)
     y = torch.empty((n, D), dtype=torch.float32, device=x.device)
     N.check(L.ragraph_spmm_csr_panels_f32(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), n, x.data_ptr(), x.shape[0], int(x_panels),
                                           D, act, float(alpha), y.data_ptr(), int(y_panels), _stream()), "spmm_csr_panels")
@@ -949,13 +950,10 @@ def spmm_linear(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, x: t
     """act((A @ x) @ weight^T + bias) in ONE launch (ragraph_spmm_linear_f32: the aggregate-first GCN layer; x of 64 or 128
     columns): the bits of spmm_csr followed by linear, without the aggregated table in HBM."""
     L = _ready()
-    rowptr = _idxc(rowptr, "spmm_linear.rowptr")
-    col = _idxc(col, "spmm_linear.col", torch.int32)
-    val = _f32c(val, "spmm_linear.val")
-    x = _f32c(x, "spmm_linear.x")
+    rowptr, col, val, x, m, _, _ = _csr_args("spmm_linear", rowptr, col, val, x)
     w = _f32c(weight, "spmm_linear.weight")
     b = _f32c(bias, "spmm_linear.bias") if bias is not None else None
-    m, n_out = rowptr.numel() - 1, w.shape[0]
+    n_out = w.shape[0]
     if w.shape[1] != x.shape[1]:
         raise ValueError(f"spmm_linear: weight [{w.shape[0]}, {w.shape[1]}] does not take x of {x.shape[1]} columns")
     y = torch.empty((m, n_out), dtype=torch.float32, device=x.device)
@@ -1031,14 +1029,10 @@ def segment_softmax(rowptr: torch.Tensor, x: torch.Tensor, long_rows: bool = Fal
     rowptr = _idxc(rowptr, "segment_softmax.rowptr")
     x = _f32c(x, "segment_softmax.x")
     out = torch.zeros_like(x)
-    if long_rows:
-        nnz = x.numel()
-        ws = _workspace(L.ragraph_sparse_workspace_bytes(nnz, 0), x.device)
-        N.check(L.ragraph_segment_softmax_ws_f32(rowptr.data_ptr(), x.data_ptr(), rowptr.numel() - 1, nnz, out.data_ptr(),
-                                                 ws.data_ptr(), ws.numel(), _stream()), "segment_softmax")
-        return out
-    N.check(L.ragraph_segment_softmax_f32(rowptr.data_ptr(), x.data_ptr(), rowptr.numel() - 1, out.data_ptr(),
-                                          _stream()), "segment_softmax")
+    ws, ws_bytes = _hub_workspace(long_rows, x.numel(), 0, x.device)
+    N.check(L.ragraph_segment_softmax_ws_f32(rowptr.data_ptr(), x.data_ptr(), rowptr.numel() - 1,
+                                             x.numel() if long_rows else 0, out.data_ptr(), ws, ws_bytes, _stream()),
+            "segment_softmax")
     return out
 
 
@@ -1566,25 +1560,17 @@ def spmm_csr_prelu_dev(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tenso
     captured HIP graph follows the slope as the optimizer moves it).  want_z: also the pre-activation A @ x + bias ->
     (y, z).  Bit-identical to spmm_csr(..., act=ACT_PRELU, alpha=float(alpha[0])) (and z to act=ACT_NONE)."""
     L = _ready()
-    rowptr = _idxc(rowptr, "spmm_csr_prelu_dev.rowptr")
-    col = _idxc(col, "spmm_csr_prelu_dev.col", torch.int32)
-    val = _f32c(val, "spmm_csr_prelu_dev.val")
-    x = _f32c(x, "spmm_csr_prelu_dev.x")
+    rowptr, col, val, x, n, D, nnz = _csr_args("spmm_csr_prelu_dev", rowptr, col, val, x)
     a = _f32c(alpha, "spmm_csr_prelu_dev.alpha")
     if a.numel() != 1:
         raise ValueError(f"spmm_csr_prelu_dev: one slope expected (nn.PReLU(num_parameters=1)), got {a.numel()}")
     b = None if bias is None else _f32c(bias, "spmm_csr_prelu_dev.bias")
-    n, D = rowptr.numel() - 1, x.shape[1]
     y = torch.empty((n, D), dtype=torch.float32, device=x.device)
     z = torch.empty((n, D), dtype=torch.float32, device=x.device) if want_z else None
-    nnz, ws, wsn = 0, None, 0
-    if long_rows:
-        nnz = col.numel()
-        ws = _workspace(L.ragraph_sparse_workspace_bytes(nnz, D), x.device)
-        wsn = ws.numel()
+    ws, ws_bytes = _hub_workspace(long_rows, nnz, D, x.device)
     N.check(L.ragraph_spmm_csr_prelu_dev_f32(rowptr.data_ptr(), col.data_ptr(), val.data_ptr(), n, x.data_ptr(), D, _ptr(b),
-                                             a.data_ptr(), y.data_ptr(), _ptr(z), nnz, _ptr(ws), wsn, _stream()),
-            "spmm_csr_prelu_dev")
+                                             a.data_ptr(), y.data_ptr(), _ptr(z), nnz if long_rows else 0, ws, ws_bytes,
+                                             _stream()), "spmm_csr_prelu_dev")
     return (y, z) if want_z else y
 
 

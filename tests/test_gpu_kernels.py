@@ -334,11 +334,12 @@ def ref_rows(rowptr, col, val, X, W, b, act, lo, hi):
     return cref.linear(cref.spmm_csr(rowptr, col, val, X), W, bias=b, act=act, alpha=0.25)[lo:hi]
 
 
-@pytest.mark.parametrize("D", [64, 256, 20])
+@pytest.mark.parametrize("D", [64, 256, 20, 128, 512])
 def test_spmm_and_softmax_hub_rows_bit_exact(dev, D):
     """Power-law shape: a few rows hold thousands of edges (one of them most of the graph).  Rows longer than 4096 edges
     are summed in blocks of 4096 (block chains from +0, added in block order) -- by the row's own lanes without a
-    workspace, by the whole chip with one; both must give the oracle's bits, and short rows stay single chains."""
+    workspace, by the whole chip with one; both must give the oracle's bits, and short rows stay single chains.
+    D = 20 and 64: groups of 16 lanes, 128: of 32, 256: of 64, 512: of 64 in two column passes."""
     from ragraph_amd import kernels as K
     from ragraph_amd.graph import CSRGraph
 

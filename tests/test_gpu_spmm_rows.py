@@ -103,6 +103,45 @@ def test_more_hub_requests_than_the_area_holds(dev):
     assert torch.equal(K.spmm_csr_rows(rowptr, col, val, x, rows, long_rows=True), y)
 
 
+def test_one_finish_kernel_with_an_epilogue_and_without(dev):
+    """The full product and the row subset finish their hub rows in the same kernel (spmm_long_finish_kernel: a row's block
+    sums in block order), one with bias, activation, residual and pre-activation, the other with none of them and the sum
+    stored at the request's position.  One small graph, hub rows of two and three blocks, every user against the oracle."""
+    from ragraph_amd import kernels as K
+
+    rng = np.random.default_rng(77)
+    n, D, hub, hub2, short = 64, 32, 5, 40, 9
+    deg = rng.integers(0, 9, n)
+    deg[[hub, hub2, short]] = 4097, 2 * 4096 + 3, 7
+    rowptr = np.zeros(n + 1, dtype=np.int64)
+    rowptr[1:] = np.cumsum(deg)
+    col = rng.integers(0, n, int(rowptr[-1])).astype(np.int32)
+    val = rng.standard_normal(col.size).astype(np.float32)
+    X = rng.standard_normal((n, D)).astype(np.float32)
+    b = rng.standard_normal(D).astype(np.float32)
+    Yin = rng.standard_normal((n, D)).astype(np.float32)
+    t = tuple(torch.from_numpy(a).to(dev) for a in (rowptr, col, val, X))
+    bd, yd = torch.from_numpy(b).to(dev), torch.from_numpy(Yin).to(dev)
+
+    got = K.spmm_csr(*t, bias=bd, act=K.ACT_PRELU, alpha=0.25, beta=0.5, y_in=yd, long_rows=True)
+    ref = cref.spmm_csr(rowptr, col, val, X, bias=b, act=2, alpha=0.25, beta=0.5, Y_in=Yin)
+    assert np.array_equal(got.cpu().numpy(), ref)
+
+    y, z = K.spmm_csr_prelu_dev(*t, bd, torch.tensor([0.25], device=dev), want_z=True, long_rows=True)
+    assert np.array_equal(y.cpu().numpy(), cref.spmm_csr(rowptr, col, val, X, bias=b, act=2, alpha=0.25))
+    assert np.array_equal(z.cpu().numpy(), cref.spmm_csr(rowptr, col, val, X, bias=b, act=0))
+
+    rows = [hub, short, hub, n + 3, hub2]                      # n + 3: no such row, an empty one
+    want = np.zeros((len(rows), D), dtype=np.float32)
+    plain = cref.spmm_csr(rowptr, col, val, X)
+    for i, r in enumerate(rows):
+        if r < n:
+            want[i] = plain[r]
+    _poison(dev, col.size, len(rows), D)
+    sub = K.spmm_csr_rows(*t, torch.tensor(rows, device=dev), long_rows=True)
+    assert np.array_equal(sub.cpu().numpy(), want)
+
+
 def _grads(g, x0, rows, w):
     from ragraph_amd import autograd as A
 
