@@ -411,6 +411,28 @@ int ragraph_topk_cosine_tail_f32(const float* Q, int64_t B, const float* Kn_tail
                                  int64_t idx_base_tail, const float* seed_scores, const int64_t* seed_idx,
                                  float* out_scores, int64_t* out_idx, void* ws, size_t ws_bytes, void* stream);
 
+/* a1 + a2 with rows RETIRED from a bank  -- the other half of a bank edited while it is in use: a withdrawn row keeps its
+ * place among the physical rows (so every copy, grouping and learnt bound stays valid) and has its bit set in a bitmap over
+ * them, bit r & 31 of 32-bit word r >> 5.  The search asks for k_in = k_out + (retired rows) keys and this entry drops the
+ * retired entries from the finished lists (ragraph_amd/csrc/topk_retire.hip):
+ *   scores / idx [B,k_in]  canonical lists (score descending, index ascending); their end may be -inf / INT64_MAX padding.
+ *   bitmap   ceil(n_rows / 32) words over the n_rows physical rows; entry idx names row idx - idx_base.
+ *   out_scores / out_idx [B,k_out]  per list a STABLE compaction: the entries whose row has its bit clear, in order, the
+ *            first k_out of them.  Padding entries and entries whose row lies outside [0, n_rows) are dropped like retired
+ *            ones.  A list that ends with fewer than k_out live entries is padded with -inf / INT64_MAX and adds one to
+ *            *short_lists (an atomic add: the caller zeroes the word).  out must not alias the lists.
+ *   Scores are copied, never recomputed: the canonical top-k_in of all rows holds at most k_in - k_out retired rows, so what
+ *   comes out is the canonical top-k_out of the live rows -- the bits of a search over them alone.
+ *   1 <= k_out <= k_in <= RAGRAPH_TOPK_ORDERED_MAX, n_rows >= 1, B >= 1, idx_base >= 0; RAGRAPH_EINVAL before any launch.
+ *   ONE launch: a wave per list, a chunk of 64 entries per step (bit test, ballot, prefix count, store), left as soon as k_out
+ *   entries are out.  No workspace, no allocation, no synchronisation, no read-back: capturable.
+ * ragraph_rows_retire_u32 sets the bits of rows [m] (int64 physical row ids; one thread per id, atomic OR, so duplicates and
+ * bits already set are fine; an id outside [0, n_rows) sets nothing).  m = 0 launches nothing. */
+int ragraph_topk_drop_rows_f32(const float* scores, const int64_t* idx, int64_t B, int k_in, int64_t idx_base,
+                               const uint32_t* bitmap, int64_t n_rows, int k_out, float* out_scores, int64_t* out_idx,
+                               int* short_lists, void* stream);
+int ragraph_rows_retire_u32(const int64_t* rows, int64_t m, int64_t n_rows, uint32_t* bitmap, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * a3  banks of duplicates  -- the reference's own bank recipe makes most rows bit-identical:
  *     RAGraph_node/ragraph_utils/ToyGraphBase.py:91-119 appends 1 + num_augment_scale passes per resource graph, :98 draws

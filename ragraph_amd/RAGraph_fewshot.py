@@ -85,6 +85,8 @@ class ToyGraphBaseFewShot(ToyGraphBase):
     def retrieve(self, search_keys, search_adj, add_noise: bool, anchors=None, row_ids=None, row_base: int = 0):
         """`row_ids` / `row_base`: the keys of the noise rows with noise_rng = "device" (ToyGraphBase.retrieve_indices)."""
         retrieve_num = 2 * self.retrieve_num if add_noise else self.retrieve_num
+        if add_noise or self.structure_weight == 0:   # (uniform draws, or scores over every physical row: live rows only)
+            self._compact_before_uniform_draws()
         if self.structure_weight != 0:   # :49-64 in one call, no [B, N] matrix in this module
             pos = self.search_positions(search_adj, None, anchors)
             _, idx = self.topk(search_keys, retrieve_num, pos)

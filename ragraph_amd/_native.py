@@ -89,6 +89,8 @@ SIGNATURES = {
     "ragraph_topk_merge_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "ragraph_topk_cosine_tail_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "ragraph_topk_cosine_tail_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ragraph_topk_drop_rows_f32": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "ragraph_rows_retire_u32": (_i32, [_vp, _i64, _i64, _vp, _vp]),
     "ragraph_dedup_rows_workspace_bytes": (_sz, [_i64]),
     "ragraph_dedup_rows_f32": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ragraph_topk_expand_groups_f32": (_i32, [_vp, _vp, _i32, _i64, _vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp]),

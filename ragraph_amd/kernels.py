@@ -668,6 +668,52 @@ def topk_cosine_tail(q: torch.Tensor, keys_tail: torch.Tensor, seed_scores: torc
     return scores, idx
 
 
+TOPK_ORDERED_MAX = N.TOPK_ORDERED_MAX   # the longest ordered list (RAGRAPH_TOPK_ORDERED_MAX)
+
+
+def retired_bitmap(n_rows: int, device) -> torch.Tensor:
+    """A zeroed bitmap over n_rows physical rows (int32 storage of 32-bit words: bit r & 31 of word r >> 5)."""
+    return torch.zeros(max(-(-n_rows // 32), 1), dtype=torch.int32, device=device)
+
+
+def retire_rows(bitmap: torch.Tensor, rows: torch.Tensor, n_rows: int) -> torch.Tensor:
+    """Set the bits of the physical rows `rows` (int64 ids; duplicates and bits already set are fine, an id outside
+    [0, n_rows) sets nothing) in `bitmap`, in place (ragraph_rows_retire_u32).  No synchronisation."""
+    L = _ready()
+    rows = _idxc(rows, "retire_rows.rows").reshape(-1)
+    if not isinstance(bitmap, torch.Tensor) or not bitmap.is_cuda or bitmap.dtype != torch.int32 or not bitmap.is_contiguous() \
+            or bitmap.numel() * 32 < n_rows:
+        raise RagraphNativeError(f"retire_rows: the bitmap must be a contiguous int32 ROCm device tensor of at least {-(-n_rows // 32)} words")
+    N.check(L.ragraph_rows_retire_u32(rows.data_ptr() if rows.numel() else None, rows.numel(), n_rows, bitmap.data_ptr(), _stream()),
+            "retire_rows")
+    return bitmap
+
+
+def topk_drop_rows(scores: torch.Tensor, idx: torch.Tensor, bitmap: torch.Tensor, n_rows: int, k_out: int, idx_base: int = 0):
+    """Canonical lists [B, k_in] without their retired rows: per list the entries whose row idx - idx_base has its bit clear in
+    `bitmap` (retired_bitmap / retire_rows), in order, the first k_out of them -- the canonical top-k_out of the live rows when
+    the lists are the canonical top-k_in of all n_rows rows and at most k_in - k_out rows are retired.  Returns (scores, idx)
+    [B, k_out] and `short_lists`, a device int32 word: the lists that held fewer than k_out live entries (padded with -inf /
+    INT64_MAX).  One launch behind the word's memset (ragraph_topk_drop_rows_f32); no synchronisation, capturable."""
+    L = _ready()
+    s = _f32c(scores, "topk_drop_rows.scores")
+    i = _idxc(idx, "topk_drop_rows.idx")
+    if s.dim() != 2 or s.shape != i.shape:
+        raise RagraphNativeError(f"topk_drop_rows: lists {tuple(s.shape)} / {tuple(i.shape)}")
+    if not isinstance(bitmap, torch.Tensor) or not bitmap.is_cuda or bitmap.dtype != torch.int32 or not bitmap.is_contiguous() \
+            or bitmap.numel() * 32 < n_rows:
+        raise RagraphNativeError(f"topk_drop_rows: the bitmap must be a contiguous int32 ROCm device tensor of at least {-(-n_rows // 32)} words")
+    B, k_in = s.shape
+    out_s = torch.empty((B, k_out), dtype=torch.float32, device=s.device)
+    out_i = torch.empty((B, k_out), dtype=torch.int64, device=s.device)
+    short = torch.zeros(1, dtype=torch.int32, device=s.device)
+    if B == 0:
+        return out_s, out_i, short
+    N.check(L.ragraph_topk_drop_rows_f32(s.data_ptr(), i.data_ptr(), B, k_in, idx_base, bitmap.data_ptr(), n_rows, k_out,
+                                         out_s.data_ptr(), out_i.data_ptr(), short.data_ptr(), _stream()), "topk_drop_rows")
+    return out_s, out_i, short
+
+
 def dedup_rows(keys_normalized: torch.Tensor):
     """Groups of bit-identical bank rows (ragraph_dedup_rows_f32; the reference's bank recipe stores most rows several
     hundred thousand times over, ToyGraphBase.py:91-119 + Augmentation.py:9-20).  Returns (U, largest group, uniq_row [U]

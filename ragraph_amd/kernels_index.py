@@ -6,7 +6,7 @@ import os
 import torch
 
 from . import filter_stats as FS
-from ._native import TOPK_FILTER_MAX, TOPK_MAX
+from ._native import TOPK_FILTER_MAX, TOPK_MAX, TOPK_ORDERED_MAX, RagraphNativeError
 
 # The kernel paths KeyIndex._route names (SLAB: plain ops.topk_cosine), and the filtered entries of one bank
 # by list length: (longest list, route, the ops' rule that says where it pays -- None: asked before the bank's clock moves).
@@ -25,7 +25,12 @@ class KeyIndex:
     from -- and a short TAIL of rows appended since: topk searches the sealed rows exactly as it would a bank of only those
     rows, then continues the finished lists over the tail (ops.topk_cosine_tail: the same fmaf chains, the same canonical
     order, so the bits of one search over all rows).  seal() folds the tail in: it drops what was derived from the ROWS and
-    keeps what was learnt from the QUERIES (priors, demotions, re-probe clocks).  DESIGN.md section 4.19."""
+    keeps what was learnt from the QUERIES (priors, demotions, re-probe clocks).  DESIGN.md section 4.19.
+
+    A bank that shrinks (retire) keeps its physical rows and marks the rows taken out in a bitmap: topk searches for k +
+    retired_rows keys exactly as above and drops the retired entries from the finished lists (ops.topk_drop_rows) -- the bits
+    of a fresh index over the live rows.  rebase() is the owner's word that the rows themselves changed (a compaction).
+    DESIGN.md section 4.21."""
 
     MAX_FILTERED_BATCH = 262144
     # int8 levels only for banks whose int8 copy is accurate enough: max |dk| of the dequantised rows.  Gaussian-like unit
@@ -148,6 +153,9 @@ class KeyIndex:
         # group_ptr, members)
         self._collapsed = None if dedup else False
         self.duplicate_stats = None   # (rows, unique rows, largest group) once judged
+        # retired rows (retire): the sorted host ids (int64 CPU tensor; the authority) and the device bitmap over the physical
+        # rows (int32 words, bit r & 31 of word r >> 5); both None until a row is retired
+        self._retired = self._bitmap = None
 
     @property
     def sealed_rows(self) -> int:
@@ -158,6 +166,88 @@ class KeyIndex:
     def tail_rows(self) -> int:
         """Rows appended since (searched by the seeded tail pass)."""
         return self._tail_rows
+
+    @property
+    def retired_rows(self) -> int:
+        """Physical rows taken out of the bank (retire) and still stored."""
+        return 0 if self._retired is None else int(self._retired.numel())
+
+    @property
+    def live_rows(self) -> int:
+        """sealed_rows + tail_rows - retired_rows: the rows topk answers over."""
+        return self._sealed_rows + self._tail_rows - self.retired_rows
+
+    @property
+    def retired_ids(self) -> torch.Tensor:
+        """The retired physical row ids, sorted (an int64 host tensor)."""
+        return torch.empty(0, dtype=torch.int64) if self._retired is None else self._retired
+
+    @property
+    def retired_bitmap(self):
+        """The device bitmap over the physical rows (None while nothing is retired): the one topk_drop_rows reads."""
+        return self._bitmap
+
+    def retire(self, rows) -> None:
+        """Take the physical rows `rows` (a tensor, array or list of ids over sealed_rows + tail_rows: what topk returns minus
+        idx_base) out of the answers.  Nothing stored is touched -- the copies' scales and error rows are functions of the whole
+        bank (csrc/filter_common.h) and every bound is a proof over them --: the ids join one sorted host array (the authority
+        for retired_rows) and have their bits set in a device bitmap, made on the first call.  Validated and de-duplicated on the
+        host (not a hot path: one copy); an id out of range raises IndexError before anything changes; retiring a row twice is a
+        no-op.  A learnt prior stays: the physical rows it was learnt over are unchanged, and the state is per k_in."""
+        if getattr(self.ops, "topk_drop_rows", None) is None or getattr(self.ops, "retire_rows", None) is None:
+            raise RagraphNativeError("KeyIndex.retire: the kernels (ops) have no topk_drop_rows / retire_rows entry")
+        ids = torch.as_tensor(rows).detach().to("cpu", torch.int64).reshape(-1)
+        n = self._sealed_rows + self._tail_rows
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n):
+            raise IndexError(f"KeyIndex.retire: row ids outside [0, {n}) (lowest {int(ids.min())}, highest {int(ids.max())})")
+        old = self._retired if self._retired is not None else ids.new_empty(0)
+        merged = torch.unique(torch.cat([old, ids]))   # (sorted)
+        if merged.numel() == old.numel():
+            return
+        new = merged[~torch.isin(merged, old)]
+        self._grow_bitmap(n)
+        self.ops.retire_rows(self._bitmap, new.to(self.keys_normalized.device), n)
+        self._retired = merged
+
+    def _grow_bitmap(self, n_rows: int) -> None:
+        """The bitmap covers n_rows rows (new words zero: new rows are live); made here on first use."""
+        words = max(-(-n_rows // 32), 1)
+        if self._bitmap is None:
+            self._bitmap = torch.zeros(words, dtype=torch.int32, device=self.keys_normalized.device)
+        elif self._bitmap.numel() < words:
+            grown = self._bitmap.new_zeros(max(words, 2 * self._bitmap.numel()))
+            grown[:self._bitmap.numel()] = self._bitmap
+            self._bitmap = grown
+
+    def overfetch_keeps_class(self, k: int, ceilings=None) -> bool:
+        """Does a list of k + retired_rows keys lie under the same ceiling as one of k keys, among 32, TOPK_MAX, TOPK_FILTER_MAX
+        (the ceilings of FILTERED_BY_K; TOPK_MAX is also the seeded tail pass's) and TOPK_ORDERED_MAX?  The owner of the rows
+        compacts when it does not (ToyGraphBase.topk): this index never does, it does not own the rows.  ceilings: those of
+        another search over the same rows (ToyGraphBase's two-metric branch: its fused limit and TOPK_ORDERED_MAX)."""
+        if ceilings is None:
+            ceilings = tuple(c for c, _, _ in FILTERED_BY_K) + (TOPK_ORDERED_MAX,)
+        under = lambda n: next((c for c in ceilings if n <= c), None)
+        return under(k + self.retired_rows) is not None and under(k + self.retired_rows) == under(k)
+
+    def rebase(self, keys_normalized: torch.Tensor) -> None:
+        """The physical rows changed arbitrarily (the owner compacted them): `keys_normalized` is the bank's new normalised
+        matrix, of the same width.  A new bank for everything derived from ROWS -- what seal drops, the tail count, the bitmap
+        and the retired ids, the padded store, a statistics word still in flight -- and for _spec: a learnt prior is a lower bound
+        of a k-th best score, which removing rows can only LOWER (seal's argument the other way round: there rows only arrive),
+        so the priors are learnt again.  Kept: _i8_off / _filter_off, _demoted and the re-probe clocks, _queries, _overflowed --
+        verdicts on the queries and on what kind of bank this is, which taking a few rows out does not change."""
+        if keys_normalized.dim() != 2 or keys_normalized.shape[1] != self.dim:
+            raise ValueError(f"KeyIndex.rebase: {tuple(keys_normalized.shape)} is not a bank of width {self.dim}")
+        if self._width is not None and self._width != self.dim:
+            keys_normalized = self.ops.pad_cols(keys_normalized, self._width)
+        self.keys_normalized = self._store = keys_normalized
+        self._sealed_rows, self._tail_rows = int(keys_normalized.shape[0]), 0
+        self._bf16 = self._packed = None
+        self._collapsed = None if self._dedup else False
+        self._i8_ok = self.i8_classes = None
+        self._retired = self._bitmap = None
+        self._pending = None
+        self._spec = {}
 
     @staticmethod
     def _capturing() -> bool:
@@ -185,6 +275,8 @@ class KeyIndex:
         else:
             self.keys_normalized = self._store = keys_normalized
         self._tail_rows = n_new - self._sealed_rows
+        if self._bitmap is not None:
+            self._grow_bitmap(n_new)   # (zero bits: the new rows are live)
         if not self.tail_enabled or getattr(self.ops, "topk_cosine_tail", None) is None:
             self.seal()
         else:
@@ -468,7 +560,30 @@ class KeyIndex:
         return bool(ops.sharded_speculates(B, plan_n, self._width, k, n_shards))
 
     def topk(self, q: torch.Tensor, k: int, idx_base: int = 0, exchange=None, plan_n: int = 0, prior=None):
-        """exchange / plan_n: this index holds one shard of a row-sharded bank (ShardedToyGraphBase): the filtered path
+        """The canonical top-k of the bank's LIVE rows, indices over the physical rows (+ idx_base).  With nothing retired this is
+        _topk_rows and nothing else: no bitmap, no extra launch.  With r retired rows the whole of _topk_rows -- sealing rule,
+        route, tail pass, collapsed expansion, padding -- runs for k_in = min(k + r, physical rows) keys and ONE
+        ops.topk_drop_rows brings the lists back to k: the same bits as a fresh index over the live rows, mapped through the
+        increasing map from live to physical rows.  The other arguments: _topk_rows."""
+        if self._retired is None:
+            return self._topk_rows(q, k, idx_base, exchange, plan_n, prior)
+        if exchange is not None:
+            raise RagraphNativeError("KeyIndex.topk: a shard of a sharded bank (exchange) with retired rows: removal from a "
+                                     "key-sharded bank is not supported")
+        n, r = self._sealed_rows + self._tail_rows, self.retired_rows
+        if k > n - r:
+            raise RagraphNativeError(f"KeyIndex.topk: k={k} exceeds the {n - r} live rows of the bank ({r} of {n} retired)")
+        k_in = min(k + r, n)
+        if k_in > TOPK_ORDERED_MAX:
+            raise RagraphNativeError(f"KeyIndex.topk: k={k} with {r} retired rows needs lists of {k_in} > {TOPK_ORDERED_MAX} "
+                                     "(TOPK_ORDERED_MAX) keys: compact the bank (the owner of the rows: ToyGraphBase.compact, "
+                                     "then KeyIndex.rebase)")
+        s, i = self._topk_rows(q, k_in, idx_base)
+        s, i, _ = self.ops.topk_drop_rows(s, i, self._bitmap, n, k, idx_base=idx_base)   # (never short: k <= live rows)
+        return s, i
+
+    def _topk_rows(self, q: torch.Tensor, k: int, idx_base: int = 0, exchange=None, plan_n: int = 0, prior=None):
+        """The canonical top-k of the PHYSICAL rows.  exchange / plan_n: this index holds one shard of a row-sharded bank (ShardedToyGraphBase): the filtered path
         sharpens its per-query bounds across the shards through `exchange` (kernels.topk_cosine_filtered), and every
         decision that changes which collectives run is taken from plan_n -- the largest shard's size -- so that all
         ranks take it alike.  prior (with exchange only): the speculative first bound the owner of the sharded bank chose for

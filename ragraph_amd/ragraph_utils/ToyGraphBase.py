@@ -6,6 +6,8 @@ recomputes it on every retrieve (SimilarityFunctions.py:11; 2 GB of traffic per 
 Storage grows geometrically (the reference re-allocates with torch.cat per resource graph, ToyGraphBase.py:116-119), and so
 do the normalised caches once they exist: an append normalises the NEW rows into them and hands the longer matrix to the
 bank's K.KeyIndex (KeyIndex.extend: the new rows are its tail), instead of dropping caches and index.
+Rows leave the same way (remove_resources): they are retired behind the live index -- stored still, marked in a bitmap,
+dropped from every answer -- until compact() gathers the live rows of every store.
 """
 from __future__ import annotations
 
@@ -181,6 +183,76 @@ class ToyGraphBase:
     def _reset_caches(self) -> None:
         self._keys_normalized = self._positions_normalized = self._index = self._kn_store = self._pn_store = None
 
+    # ---- removal ------------------------------------------------------------------------------
+    @property
+    def retired_rows(self) -> int:
+        """Physical rows removed (remove_resources) and still stored; the bank's index is the authority."""
+        return 0 if self._index is None else self._index.retired_rows
+
+    @property
+    def num_resources(self) -> int:
+        """The live rows: what retrieval answers over (resource_* stay physical until compact())."""
+        return self._keys.n - self.retired_rows
+
+    def remove_resources(self, rows) -> None:
+        """Take the physical rows `rows` (ids over resource_keys: what topk returns) out of the bank.  With an index or a
+        normalised cache alive the rows are RETIRED (K.KeyIndex.retire): nothing stored moves, every copy, duplicate group and
+        learnt bound stays, and retrieval over-fetches by retired_rows and drops them (K.topk_drop_rows) -- until compact().
+        A bank that has neither yet is simply compacted at once.  An id out of range raises IndexError before anything changes."""
+        ids = torch.as_tensor(rows).detach().to("cpu", torch.int64).reshape(-1)
+        n = self._keys.n
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n):
+            raise IndexError(f"remove_resources: row ids outside [0, {n}) (lowest {int(ids.min())}, highest {int(ids.max())})")
+        if not ids.numel():
+            return
+        if self._index is None and self._keys_normalized is None and self._positions_normalized is None:
+            self._keep_rows(self._live_positions(ids))
+            return
+        if self._index is None:
+            self._index = K.KeyIndex(self.keys_normalized)
+        self._index.retire(ids)
+
+    def _live_positions(self, retired: Tensor) -> Tensor:
+        """The physical rows that are not in `retired` (host ids), ascending: an int64 device tensor."""
+        live = torch.ones(self._keys.n, dtype=torch.bool, device=self.device)
+        live[retired.to(self.device)] = False
+        return K.mask_positions(live)
+
+    def _keep_rows(self, live: Tensor) -> None:
+        """Every store becomes its rows `live` (K.gather_rows: bit copies), one store at a time."""
+        for bank in (self._keys, self._values, self._labels) + ((self._positions,) if self._positions.n else ()):
+            bank.buf = K.gather_rows(bank.buf[:bank.n], live)
+            bank.n = bank.buf.shape[0]
+        # (a normalised row is a function of its own row alone: the gathered cache is the cache of the gathered rows, bit for bit)
+        if self._keys_normalized is not None:
+            self._keys_normalized = K.gather_rows(self._keys_normalized, live)
+            self._kn_store = self._adopt_normalized(self._keys_normalized)
+        if self._positions_normalized is not None:
+            self._positions_normalized = K.gather_rows(self._positions_normalized, live)
+            self._pn_store = self._adopt_normalized(self._positions_normalized)
+
+    def compact(self):
+        """Drop the retired rows from every store: keys, values, labels, the position codes when present, and the normalised
+        key and code caches that exist; then K.KeyIndex.rebase (copies, groups and priors start over; demotions, re-probe
+        clocks and counters stay).  Returns the int64 device tensor of live positions -- new row j was old row live[j] --, or None
+        when nothing was retired.  The stores are gathered one at a time and each old store is released before the next is
+        gathered: the peak extra memory is ONE store's worth (the widest: N x emb_size floats), not a second bank.  Reads the
+        live count back (K.mask_positions): never under a stream capture."""
+        if not self.retired_rows:
+            return None
+        live = self._live_positions(self._index.retired_ids)
+        self._keep_rows(live)
+        self._index.rebase(self.keys_normalized)
+        return live
+
+    def _compact_before_uniform_draws(self) -> None:
+        """Noisy retrieval draws rows uniformly over the PHYSICAL rows and could draw a retired one: compact first."""
+        if self.retired_rows:
+            if K.KeyIndex._capturing():
+                raise K.RagraphNativeError("noisy retrieval over a bank with retired rows compacts it first, which a stream "
+                                           "capture cannot record: call compact() before capturing")
+            self.compact()
+
     @property
     def keys_normalized(self) -> Tensor:
         if self._keys_normalized is None:
@@ -242,12 +314,29 @@ class ToyGraphBase:
             self._require_positions()
             if search_positions is None:
                 raise ValueError("structure_weight != 0: topk needs the query rows' position codes (search_positions)")
-        if self.resource_keys.shape[0] < k:
-            raise RuntimeError(f"selected index k out of range: bank has {self.resource_keys.shape[0]} rows, k={k}")
+        n_live = self.resource_keys.shape[0] - self.retired_rows   # (resource_keys: a captured step records that it reads the bank)
+        if n_live < k:
+            raise RuntimeError(f"selected index k out of range: bank has {n_live} rows, k={k}")
+        # retired rows never move a call into a slower list class: past a ceiling the bank is compacted first (not under a
+        # capture, where the over-fetch goes as far as TOPK_ORDERED_MAX)
+        mixed_ceilings = (32, K.TOPK_ORDERED_MAX)   # (K.topk_cosine_mix: fused up to 32 keys, score slabs beyond)
+        if self.retired_rows and not K.KeyIndex._capturing() and not self._index.overfetch_keeps_class(
+                k, mixed_ceilings if self.structure_weight != 0 else None):
+            self.compact()
         if self.structure_weight != 0:
             pos = search_positions.reshape(1, -1) if search_positions.dim() == 1 else search_positions
-            return K.topk_cosine_mix(q, self.keys_normalized, pos, self.positions_normalized, self.structure_weight,
-                                     self.semantic_weight, k)
+            r, n = self.retired_rows, self._keys.n
+            if not r:
+                return K.topk_cosine_mix(q, self.keys_normalized, pos, self.positions_normalized, self.structure_weight,
+                                         self.semantic_weight, k)
+            k_in = min(k + r, n)   # (this branch bypasses KeyIndex: the same over-fetch and the same drop around its own search)
+            if k_in > K.TOPK_ORDERED_MAX:
+                raise K.RagraphNativeError(f"topk: k={k} with {r} retired rows needs lists of {k_in} > {K.TOPK_ORDERED_MAX} "
+                                           "keys: compact() the bank (not done under a stream capture)")
+            s, i = K.topk_cosine_mix(q, self.keys_normalized, pos, self.positions_normalized, self.structure_weight,
+                                     self.semantic_weight, k_in)
+            s, i, _ = K.topk_drop_rows(s, i, self._index.retired_bitmap, n, k)
+            return s, i
         if self._index is None:
             self._index = K.KeyIndex(self.keys_normalized)
         return self._index.topk(q, k)  # fp32 streaming / tile kernel or, for large batches, the bf16-filtered exact path
@@ -262,6 +351,8 @@ class ToyGraphBase:
         are K.noise_rows of a fresh seed (last_noise_seed), keyed by the query's row in the call -- or by `row_ids` /
         `row_base + b` when the caller holds a slice of a larger batch -- written into the tail of one [B, k' + m] matrix."""
         retrieve_num = 2 * self.retrieve_num if add_noise else self.retrieve_num
+        if add_noise:
+            self._compact_before_uniform_draws()
         pos = self.search_positions(search_adj, search_positions, anchors)         # (None unless structure_weight != 0)
         _, idx = self.topk(search_keys, retrieve_num, pos)                         # :66-67
         if add_noise and self.flavour == "node" and self.noise_rng == "device":
@@ -302,6 +393,8 @@ class ToyGraphBase:
         when the caller already holds retrieve_indices(search_keys, True); want_labels=False skips the label means).
         Node flavour with noise_rng = "device" and no `idx`: the top-2k list alone goes into K.gather_reduce_noisy, which
         computes the noise rows itself -- the bits of the reduction over retrieve_indices' matrix for the same seed."""
+        if idx is None:   # (a caller's own idx was made by retrieve_indices(search_keys, True), which compacted)
+            self._compact_before_uniform_draws()
         if idx is None and self.flavour == "node" and self.noise_rng == "device":
             pos = self.search_positions(search_adj, search_positions, anchors)
             _, top = self.topk(search_keys, 2 * self.retrieve_num, pos)
@@ -331,7 +424,9 @@ class ToyGraphBase:
     # ---- persistence (the reference rebuilds its bank on every run) -------------------
     def save(self, path: str) -> None:
         """keys | values | labels | positions as one .pt, format v2 (the normalised caches are derived and rebuilt on
-        load).  `positions` holds as many rows as the bank has codes for: all of them, or none."""
+        load).  `positions` holds as many rows as the bank has codes for: all of them, or none.  Live rows only: a bank with
+        retired rows is compacted first."""
+        self.compact()
         torch.save({"format": "ragraph_amd.bank.v2", "keys": self.resource_keys.cpu(), "values": self.resource_values.cpu(),
                     "labels": self.resource_labels.cpu(), "positions": self.resource_positions.cpu()}, path)
 
