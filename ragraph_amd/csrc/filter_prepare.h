@@ -16,7 +16,9 @@
 // exact scan), [18] / [19] the smallest / largest final exact k-th best score of the call's queries as order-preserving
 // ints (f2ord; what the owner of the bank builds the next call's prior from), [20] the call's final *overflow (so that ONE
 // copy of these words tells the owner everything), [21] a tight bound was in force, [22] soft misses, [23] the repair that ran
-// (filter_verify_fixup.h), [24..32) reserved.  Host-side mirror, by name: ragraph_amd/filter_stats.py (keep the two alike).
+// (filter_verify_fixup.h), [24] a tight call's step delta = (t - prior) / 16 as float bits (0: not reported) and [25 .. 28] the
+// judged queries whose final k-th best is below t + delta, + 2 delta, + 4 delta, + 8 delta (filter_verify_prior_kernel: with [22]
+// five points of the low tail's cumulative count), [29..32) reserved.  Host-side mirror, by name: ragraph_amd/filter_stats.py (keep the two alike).
 constexpr int FILTER_STATS_INTS = 32;
 constexpr int FILTER_STATS_MAGIC = 0x52414753;
 __device__ __forceinline__ void note_candidates(int* cstat, int64_t b, int n) {

@@ -32,7 +32,12 @@ __device__ __forceinline__ bool zero_query_level(unsigned char fl, int final_lev
 // CU -- such a level is a chain of memory latencies per query, and occupancy is what hides them; the rare longer list
 // takes the lane-private row reads.
 // LW: 64 (every k <= 64: a lane per winner) or 128 (lists of 65 .. 128 keys: two winners per lane, rescore_common.h).
-template <int D, int CPL, bool FEWTILE = false, int LW = 64>
+// SKIP (the FINAL launch of a call under a tight bound, idx_base == 0, prev_* == out_*: run_tight_repair): the lists are empty
+// unless the all-queries repair level ran, and an unflagged query with an empty list would merge nothing into the row it read
+// and write the same row back -- its count is 0 already and a final launch notes no candidates.  So the wave loads the count
+// and the flag FIRST and returns on them, before the query row is read, LDS is touched or anything is written; every other
+// query goes on as ever.  (A template flag: the level launches keep their three loads in flight together, and their code.)
+template <int D, int CPL, bool FEWTILE = false, int LW = 64, bool SKIP = false>
 __global__ void __launch_bounds__(128, FEWTILE ? 4 : 1) topk_rescore_coop_kernel(const float* __restrict__ Qn, const float* __restrict__ Kn,
                                                                 int* __restrict__ count,
                                                                 const int* __restrict__ cand, int64_t B, int cap, int cs, int k,
@@ -50,6 +55,9 @@ __global__ void __launch_bounds__(128, FEWTILE ? 4 : 1) topk_rescore_coop_kernel
   // (the count, the flag and the query row are independent loads: issued together, one latency)
   int n = count[b * cs];
   const unsigned char fl = flag[b];
+  if constexpr (SKIP) {
+    if (n == 0 && fl == 0) return;  // (wave-uniform) nothing to merge: the row stays as it is
+  }
   bool over = fl != 0;
   float4 qv4 = make_float4(0.f, 0.f, 0.f, 0.f);
   if (lane < D / 4) qv4 = reinterpret_cast<const float4*>(Qn + b * D)[lane];
@@ -312,7 +320,8 @@ __device__ __forceinline__ bool rescore_scored_query(const float4* __restrict__ 
 // SMALL (calls of 8192 queries and more, whose lists average ~120 entries and whose second round ~25 rows): half tiles and
 // at most four entry slots per lane -- 15 KB less LDS per workgroup and ~50 fewer registers, three waves per SIMD instead
 // of two for a kernel that lives on hiding row-gather latency; the few longer lists take lane-private row reads.
-template <int D, bool SMALL = false, int LW = 32>
+// SKIP: as in topk_rescore_coop_kernel.
+template <int D, bool SMALL = false, int LW = 32, bool SKIP = false>
 __global__ void __launch_bounds__(128) topk_rescore_scored_kernel(const float* __restrict__ Qn, const float* __restrict__ Kn,
                                                                   int* __restrict__ count, const int2* __restrict__ cand,
                                                                   int64_t B, int cap, int cs, int k, int64_t idx_base,
@@ -332,6 +341,9 @@ __global__ void __launch_bounds__(128) topk_rescore_scored_kernel(const float* _
   // (the count, the flag and the query row are independent loads: issued together, one latency)
   int n = count[b * cs];
   const unsigned char fl = flag[b];
+  if constexpr (SKIP) {
+    if (n == 0 && fl == 0) return;  // (wave-uniform) nothing to merge: the row stays as it is
+  }
   bool over = fl != 0;
   float4 qv4 = make_float4(0.f, 0.f, 0.f, 0.f);
   if (lane < D / 4) qv4 = reinterpret_cast<const float4*>(Qn + b * D)[lane];
@@ -533,7 +545,8 @@ static void wide_timing_report() {
 #define RG_WSTAMP(i_)
 static void wide_timing_report() {}
 #endif
-template <int D, bool SLICED, bool COOP, int LW = 32>
+// SKIP (as in topk_rescore_coop_kernel; calls of 257 .. 2047 queries under a tight bound, so never SLICED): the workgroup returns.
+template <int D, bool SLICED, bool COOP, int LW = 32, bool SKIP = false>
 __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __restrict__ Qn, const float* __restrict__ Kn,
                                                                 int* __restrict__ count,
                                                                 const int* __restrict__ cand, int64_t B, int64_t N, int cap,
@@ -554,6 +567,9 @@ __global__ void __launch_bounds__(256) topk_rescore_wide_kernel(const float* __r
   const int64_t b = blockIdx.x;
   constexpr int LWS = LW > 64 ? 128 : 64;  // the form of the helpers that know a lane per winner (64) or two (128)
   RG_WSTAMP(0);
+  if constexpr (SKIP && !SLICED) {
+    if (count[b * cs] == 0 && flag[b] == 0) return;  // (block-uniform) nothing to merge: the row stays as it is
+  }
   if (threadIdx.x < D / 4) qs[threadIdx.x] = reinterpret_cast<const float4*>(Qn + b * D)[threadIdx.x];
   __syncthreads();
   RG_WSTAMP(1);

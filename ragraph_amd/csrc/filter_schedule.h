@@ -52,6 +52,8 @@ struct FilterEnv {
   int spec_two_shards;  // RAGRAPH_FILTER_SPEC_SHARDS_TWO_LEVELS: from this many shards a three-level plan runs two levels
                         // under a prior (default 2: every sharded bank; 0 = never)
   int tight_levels;     // RAGRAPH_FILTER_TIGHT_LEVELS: levels of a call under a tight bound (default 1; 2: the plan's last two -- A/B)
+  int final_skip;       // RAGRAPH_FILTER_FINAL_SKIP: the final rescoring of a call under a tight bound returns on an empty list
+                        // (filter_rescore.h: SKIP; default 1; 0: every wave reads and rewrites its row -- A/B)
 };
 static int filter_env_int(const char* name, int dflt) {
   const char* e = getenv(name);
@@ -63,7 +65,7 @@ static FilterEnv filter_env() {
   return {filter_env_int("RAGRAPH_FILTER_I8", -1), filter_env_int("RAGRAPH_FILTER_SCORED", -1), filter_env_int("RAGRAPH_FILTER_PIPE", 1),
           filter_env_int("RAGRAPH_FILTER_SKEW", 1),
           filter_env_int("RAGRAPH_FILTER_PARTNER_LEAD", 1), filter_env_int("RAGRAPH_FILTER_I8_QW", 0), scored_shards, spec_two_shards,
-          filter_env_int("RAGRAPH_FILTER_TIGHT_LEVELS", 1)};
+          filter_env_int("RAGRAPH_FILTER_TIGHT_LEVELS", 1), filter_env_int("RAGRAPH_FILTER_FINAL_SKIP", 1)};
 }
 
 // Scored candidate lists for the int8 levels (topk_rescore_scored_kernel): calls whose rescoring is bound by the row

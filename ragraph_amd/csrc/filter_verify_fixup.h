@@ -12,19 +12,42 @@
 // (Zero queries -- flag 2 -- are answered without a scan and not judged; queries already listed by the final level
 // -- flag 1 / an overflowed list -- carry -inf or stale rows: listed twice would be scanned twice, so they are skipped by
 // their flag.)
+// Under a TIGHT bound t (below; delta > 0 then, 0 otherwise) the same read of the k-th best scores also counts the LOW TAIL of
+// their distribution: the judged queries (flag 0, proven against the prior) whose final k-th best is below t + m delta for
+// m = 1, 2, 4, 8 go to stats[25 .. 28], and stats[24] holds delta's bits (0: not reported).  With stats[22] -- the count below
+// t itself: a query's k-th best found is below t iff its final one is -- that is five points of the cumulative count, from
+// which the owner of the bank places the next call's t at a soft-miss COUNT (ragraph_amd/kernels_index.py).  The edges are
+// formed in fp32 as t + m delta (m delta is exact: a power of two).
+// FILTER_VERIFY_ROWS queries per thread: the launch is bound by its atomics on the one line of statistics words, not by the
+// 400 KB it reads (100 000 queries, 12 us with three words per 256 queries; the four tail words took that to 26 us), so a
+// workgroup judges 1024 queries and the words see a quarter of the workgroups.
+constexpr int FILTER_TAIL_EDGES = 4;
+constexpr int FILTER_VERIFY_ROWS = 4;
 __global__ void __launch_bounds__(256) filter_verify_prior_kernel(const float* __restrict__ out_s, int64_t B, int k, float prior,
                                                                   int speculative, const unsigned char* __restrict__ flag,
                                                                   int* __restrict__ overflow, int* __restrict__ overflow_list,
-                                                                  int* __restrict__ stats) {
-  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+                                                                  int* __restrict__ stats, float tight, float delta) {
   int lo = INT_MAX, hi = INT_MIN, failed = 0;
-  if (q < B && flag[q] != 2) {
-    const float kth = out_s[q * k + k - 1];
-    if (speculative && flag[q] == 0 && !(kth >= prior)) {
-      overflow_list[atomicAdd(overflow, 1)] = (int)q;
-      failed = 1;
-    } else if (kth > RG_NEG_INF) {
-      lo = hi = f2ord(kth);
+  const bool tail = delta > 0.f;   // (launch-uniform)
+  int below[FILTER_TAIL_EDGES] = {0, 0, 0, 0};
+#pragma unroll
+  for (int r = 0; r < FILTER_VERIFY_ROWS; ++r) {
+    const int64_t q = ((int64_t)blockIdx.x * FILTER_VERIFY_ROWS + r) * 256 + threadIdx.x;
+    float judged = __builtin_huge_valf();   // the k-th best of a query the tail counts (+inf: below no edge)
+    if (q < B && flag[q] != 2) {
+      const float kth = out_s[q * k + k - 1];
+      if (speculative && flag[q] == 0 && !(kth >= prior)) {
+        overflow_list[atomicAdd(overflow, 1)] = (int)q;
+        failed += 1;
+      } else if (kth > RG_NEG_INF) {
+        lo = min(lo, f2ord(kth));
+        hi = max(hi, f2ord(kth));
+        if (flag[q] == 0) judged = kth;
+      }
+    }
+    if (tail) {
+#pragma unroll
+      for (int e = 0; e < FILTER_TAIL_EDGES; ++e) below[e] += __popcll(__ballot(judged < tight + (float)(1 << e) * delta));
     }
   }
 #pragma unroll
@@ -35,12 +58,14 @@ __global__ void __launch_bounds__(256) filter_verify_prior_kernel(const float* _
   }
   // one set of atomics per WORKGROUP (a returning atomic on one address costs ~11 ns chip-wide: 1600 waves of a 100 000-query
   // call at three each were 38 us of a launch that reads 400 KB)
-  __shared__ int red[3][4];
+  __shared__ int red[3 + FILTER_TAIL_EDGES][4];
   const int w = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
     red[0][w] = lo;
     red[1][w] = hi;
     red[2][w] = failed;
+#pragma unroll
+    for (int e = 0; e < FILTER_TAIL_EDGES; ++e) red[3 + e][w] = below[e];
   }
   __syncthreads();
   if (threadIdx.x == 0 && stats) {
@@ -50,6 +75,14 @@ __global__ void __launch_bounds__(256) filter_verify_prior_kernel(const float* _
     if (lo != INT_MAX) atomicMin(stats + 18, lo);
     if (hi != INT_MIN) atomicMax(stats + 19, hi);
     if (failed) atomicAdd(stats + 17, failed);
+    if (tail) {
+      if (blockIdx.x == 0) stats[24] = __float_as_int(delta);
+#pragma unroll
+      for (int e = 0; e < FILTER_TAIL_EDGES; ++e) {
+        const int n = red[3 + e][0] + red[3 + e][1] + red[3 + e][2] + red[3 + e][3];
+        if (n) atomicAdd(stats + 25 + e, n);
+      }
+    }
   }
 }
 
@@ -73,7 +106,11 @@ __global__ void __launch_bounds__(256) filter_verify_prior_kernel(const float* _
 // verdict against p (filter_verify_prior_kernel: a repaired query whose final k-th best is below p was repaired from a bound
 // that was too high -- a hard miss, scanned) and the fixup launch, unchanged.
 // Statistics words: [21] = 1 a tight bound was in force, [22] soft misses, [23] the repair that ran (0 none, 1 the 256-query
-// call, 2 the all-queries level).
+// call, 2 the all-queries level), [24] delta = (t - p) / 16 as float bits and [25 .. 28] the judged queries whose final k-th
+// best is below t + delta, + 2 delta, + 4 delta, + 8 delta (filter_verify_prior_kernel above).
+// The FINAL rescoring of such a call finds an empty list for every query the all-queries level did not serve -- all of them
+// unless it ran -- and such a query's merge would rewrite the row it read: with idx_base == 0 its wave returns on the count and
+// the flag alone (filter_rescore.h: SKIP).
 __global__ void __launch_bounds__(256) filter_tight_verdict_kernel(float* __restrict__ out_s, int64_t* __restrict__ out_i, int64_t B,
                                                                    int k, float tight, float prior,
                                                                    const unsigned char* __restrict__ flag, float* __restrict__ theta,

@@ -695,24 +695,28 @@ static RescoreKind rescore_kind(int64_t B, int k, bool scored, bool few) {
 // Exact rescoring of a level's candidates (+ merge with the running result when `merge`) and canonical selection.  Every
 // kind lists the queries whose list overflowed for topk_overflow_fixup_kernel (scan_n = 0: the one-wave-per-query kernels'
 // own wave scanning a million keys took 94 ms).
-template <int D, int LW>
+// SKIP (run_tight_repair's final launch alone, and only with idx_base == 0): the kernels' form that returns on an empty list of
+// an unflagged query -- the merge would rewrite the row it read (filter_rescore.h).
+template <int D, int LW, bool SKIP = false>
 static int run_rescore(const FilterWs& f, const float* Kn, int64_t N, int64_t B, int cap, int k, int64_t idx_base, int merge,
                        int final_level, float* out_scores, int64_t* out_idx, int* overflow, RescoreKind kind, const FilterThr& thr,
                        int* cstat, hipStream_t st) {
+  if constexpr (SKIP)
+    RG_REQUIRE(merge && final_level && idx_base == 0 && !cstat, RAGRAPH_EINVAL, "topk_cosine_filtered: not a launch that may skip rows");
   const float* ps = merge ? out_scores : nullptr;
   const int64_t* pi = merge ? out_idx : nullptr;
   const int cs = filter_count_stride(B);
   const int64_t scan_n = 0;
 #define RG_SCORED(SMALL_)                                                                                                        \
-  hipLaunchKernelGGL((topk_rescore_scored_kernel<D, SMALL_, LW>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,    \
+  hipLaunchKernelGGL((topk_rescore_scored_kernel<D, SMALL_, LW, SKIP>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,    \
                      reinterpret_cast<const int2*>(f.cand), B, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx,   \
                      overflow, f.overflow_list, f.flag, scan_n, thr, cstat)
 #define RG_WIDE(SLICED_, COOP_, GRID_, PART_S_, PART_I_)                                                                         \
-  hipLaunchKernelGGL((topk_rescore_wide_kernel<D, SLICED_, COOP_, LW>), GRID_, dim3(256), 0, st, f.Qn, Kn, f.count, f.cand, B, N,    \
+  hipLaunchKernelGGL((topk_rescore_wide_kernel<D, SLICED_, COOP_, LW, SKIP && !(SLICED_) && !(COOP_)>), GRID_, dim3(256), 0, st, f.Qn, Kn, f.count, f.cand, B, N,    \
                      cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx, overflow, f.overflow_list, f.flag, PART_S_, \
                      PART_I_, cstat)
 #define RG_COOP(FEW_)                                                                                                            \
-  hipLaunchKernelGGL((topk_rescore_coop_kernel<D, 32, FEW_, (LW > 64 ? 128 : 64)>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,    \
+  hipLaunchKernelGGL((topk_rescore_coop_kernel<D, 32, FEW_, (LW > 64 ? 128 : 64), SKIP && !(FEW_)>), dim3((unsigned)cdiv(B, 2)), dim3(128), 0, st, f.Qn, Kn, f.count,    \
                      f.cand, B, cap, cs, k, idx_base, ps, pi, final_level, out_scores, out_idx, overflow, f.overflow_list,       \
                      f.flag, scan_n, cstat)
   switch (kind) {
@@ -892,7 +896,11 @@ static int run_tight_repair(const FilteredArgs& a, const FilterCall& c, const Fi
   rc = run_pass<D>(f, a.Kb, K8, B, 0, N, thr, c.cap, 0, lv.int8, lv.scored, in.env, in.cus, -1, st,
                    FilterGate{stats + 22, FILTER_REPAIR_Q + 1, INT_MAX});
   if (rc != RAGRAPH_OK) return rc;
-  // the call's final rescoring: the level's lists (empty unless it ran) merged with the running rows
+  // the call's final rescoring: the level's lists (empty unless it ran) merged with the running rows.  Without an index
+  // base a query with an empty list and no flag keeps its row as it is, and its wave returns before reading anything else
+  if (a.idx_base == 0 && in.env.final_skip)
+    return run_rescore<D, LW, true>(f, a.Kn, N, B, c.cap, k, 0, 1, 1, a.out_scores, a.out_idx, a.overflow,
+                                    rescore_kind(B, k, lv.scored, false), thr, nullptr, st);
   return run_rescore<D, LW>(f, a.Kn, N, B, c.cap, k, a.idx_base, 1, 1, a.out_scores, a.out_idx, a.overflow,
                         rescore_kind(B, k, lv.scored, false), thr, nullptr, st);
 }
@@ -1041,8 +1049,8 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
 
   // 7. verify / fixup
   if (c.spec && !sharded) {   // (a shard's lists prove nothing alone: the owner of a row verifies the MERGED k-th best)
-    hipLaunchKernelGGL(filter_verify_prior_kernel, dim3((unsigned)cdiv(B, 256)), dim3(256), 0, st, out_scores, B, k, in.prior, 1, f.flag,
-                       a.overflow, f.overflow_list, stats);
+    hipLaunchKernelGGL(filter_verify_prior_kernel, dim3((unsigned)cdiv(B, 256 * FILTER_VERIFY_ROWS)), dim3(256), 0, st, out_scores, B, k, in.prior, 1, f.flag,
+                       a.overflow, f.overflow_list, stats, c.tight ? in.tight : 0.f, c.tight ? (in.tight - in.prior) / 16.f : 0.f);
     RG_CHECK_LAUNCH("topk_cosine_filtered(verify)");
   }
   // overflowed queries (none on ordinary banks) and the queries a prior was too high for: exact fp32 scan on the device --

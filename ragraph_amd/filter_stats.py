@@ -21,13 +21,32 @@ KTH_HI = 19        # largest
 OVERFLOW = 20      # the call's final overflow count
 TIGHT = 21         # a tight bound was in force
 SOFT_MISSES = 22   # queries the tight bound was too high for
-REPAIR = 23        # the repair that ran (1: the 256-query call, 2: the all-queries level); [24, 32) reserved
+REPAIR = 23        # the repair that ran (1: the 256-query call, 2: the all-queries level)
+TAIL_DELTA = 24    # a tight call's step delta = (t - prior) / 16 as float bits (bits2f); 0: the tail counts are not reported
+TAIL_BELOW = 25    # + j, j < len(TAIL_STEPS): judged queries whose final k-th best is below t + TAIL_STEPS[j] * delta
+TAIL_STEPS = (1, 2, 4, 8)   # [29, 32) reserved
 
 
 def ord2f(v: int) -> float:
     """The float behind an order-preserving int (csrc/filter_common.h f2ord: negative floats have their 31 low bits flipped)."""
     v = int(v)
     return struct.unpack("<f", struct.pack("<i", v ^ 0x7FFFFFFF if v < 0 else v))[0]
+
+
+def bits2f(v: int) -> float:
+    """The float whose bits an int word holds (TAIL_DELTA)."""
+    return struct.unpack("<f", struct.pack("<i", int(v)))[0]
+
+
+def tail_points(words, t: float):
+    """[(score, queries whose final k-th best is below it)] of a call that ran under the tight bound t: t itself (SOFT_MISSES)
+    and the TAIL_STEPS edges, formed as the device forms them; None when the call did not report them."""
+    if len(words) < TAIL_BELOW + len(TAIL_STEPS) or not words[TIGHT] or not words[TAIL_DELTA]:
+        return None
+    delta = bits2f(words[TAIL_DELTA])
+    if not delta > 0.0:
+        return None
+    return [(float(t), int(words[SOFT_MISSES]))] + [(float(t) + m * delta, int(words[TAIL_BELOW + j])) for j, m in enumerate(TAIL_STEPS)]
 
 
 def levels(words) -> list:

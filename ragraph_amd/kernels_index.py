@@ -1,6 +1,7 @@
 """Bank-side dispatch of the exact top-k (torch only: importable on a CPU box for the gloo tests)."""
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -82,8 +83,9 @@ class KeyIndex:
     # about 0.1 ms (any number up to 256) where a miss of the prior costs a scan: t needs no margin of the spread.  The scores
     # of the bench's queries have sigma = 1 / 16 and their k-th best sits 4 sigma out, where 0.002 of score is 13 % more
     # candidates (measured at the bench shape: 0 soft misses in every polled step over its 8 distinct batches, 152 candidates
-    # per query; t 0.004 higher: 10 soft misses, 0.2 ms less per call -- not worth a repair in most steps); a call that reports
-    # more than TIGHT_MAX_SOFT soft misses doubles the margin (up to TIGHT_MARGIN_MAX), one
+    # per query; t 0.004 higher: 10 soft misses, 0.2 ms less per call -- which the rule below TIGHT_MAX_SOFT now collects).  This
+    # rule is where t STARTS and what calls without tail counts follow: a call that reports more than TIGHT_MAX_SOFT soft
+    # misses doubles the margin (up to TIGHT_MARGIN_MAX), one
     # whose repair took the all-queries level withdraws t for the re-probe interval.  RAGRAPH_SPEC_TIGHT=0: the prior alone (A/B).
     # From TIGHT_MIN_BATCH queries: the verdict and the (empty) repair are eight more launches, ~13 us, and up to 4096 queries
     # the call under the prior already runs one level, so t only saves candidates there -- 1M x 256, ms per call without / with
@@ -92,6 +94,33 @@ class KeyIndex:
     TIGHT_MARGIN = 0.002
     TIGHT_MARGIN_MAX = 0.064
     TIGHT_MAX_SOFT = 32
+    # Placing t at a soft-miss COUNT.  The rule above knows the minimum of the k-th best scores only, so it keeps t below all of
+    # them, and every query admits the keys between t and its own k-th best for nothing: at the bench shape t = 0.2455 passes
+    # 129.6 candidates per query, t = 0.2494 (10 soft misses) 101.0 and saves 0.22 ms per call net of the 0.1 ms repair, which
+    # costs the same for 1 or 256 rows (profiles/tight_prior.txt section 5).  A tight call reports five points of the low
+    # tail's cumulative count -- the judged queries whose final k-th best is below t (SOFT_MISSES) and below t + m delta,
+    # m = 1, 2, 4, 8, delta = (t - prior) / 16 (TAIL_DELTA, TAIL_BELOW; csrc/filter_verify_fixup.h) --, and a polled call that
+    # does moves t to where their log-linear interpolation meets TIGHT_TARGET_SOFT (_aim_tight).  Conditions, none of them a
+    # measurement: the target is at most TIGHT_TARGET_SOFT_MAX = 64, a quarter of the 256-row repair, so a call at four times
+    # its expected count still takes the cheap repair and not one more level (+15 ms); t never moves above the highest reported
+    # edge t + 8 delta, which is also the most it rises per polled call; it never goes to or below the prior, nor below the
+    # rule above (lowest - margin: fewer misses than none buy nothing); a count within a factor of two of the target leaves t
+    # where it is (a count of 32 scatters by +-6 between batches of one distribution: chasing that moves t every call);
+    # a call beyond twice the target re-aims DOWN from its own counts, by the slope of its lowest rising segment.  The
+    # all-queries repair withdraws t exactly as above and forgets the aimed t (the re-probe starts from the rule above); calls
+    # whose words lack TAIL_DELTA follow the rule above unchanged.  RAGRAPH_TIGHT_TARGET_SOFT=n sets the target (clamped to 64);
+    # 0 keeps the rule above (A/B).
+    # Batch classes: the repair is one pass of the direct kernel over the bank, about 0.1 ms at 1M x 256 whatever its row count,
+    # and what a higher t saves grows with the batch -- measured against the rule above (profiles/tight_quantile.txt): 100 000 x
+    # 1M x 256 -0.3 ms per step and 20 000 x 500k x 128 1.22 -> 1.12 ms, but 4096 x 1M x 256 0.83 - 0.86 -> 0.89 - 0.91 ms and 4096
+    # x 4M x 64 0.85 -> 0.92.  Saving and cost both grow with the bank, the cost also with the row width, so the break-even
+    # batch is proportional to D (about 128 D from those four points): t is aimed for calls of at least
+    # TIGHT_TARGET_QUERIES_PER_DIM x D queries -- twice the break-even -- and from such calls' counts only; smaller calls keep the
+    # rule above.  A count is a count of ONE batch size: an aimed t serves calls of up to twice the queries of the call it was
+    # aimed from (at most twice its soft misses), larger ones start from the rule above and aim for themselves.
+    TIGHT_TARGET_SOFT = 32
+    TIGHT_TARGET_SOFT_MAX = 64
+    TIGHT_TARGET_QUERIES_PER_DIM = 256
     DEDUP_MIN_ROWS = 2048
     DEDUP_MAX_UNIQUE = 0.9
     DEDUP_MAX_GROUP = 64
@@ -128,7 +157,7 @@ class KeyIndex:
         self._filter_off = False  # set when this bank defeats the filter (see _poll_overflow)
         self._i8_off = False      # set when this bank defeats the INT8 levels only (clustered keys: too many within the int8 bound)
         self.i8_classes = None    # the int8 copy's two classes of granules as read for _i8_ok (kernels.int8_copy_classes)
-        self._pending = None      # (pinned word, event, batch, had int8 levels) of the last filtered call's overflow count
+        self._pending = None      # (pinned word, event, batch, had int8 levels, k, tight bound) of the last filtered call's overflow count
         self._i8_ok = None        # the int8 copy's error row read (once, lazily): accurate enough for int8 levels?
         self._seen_i8, self._seen_bf16 = [0, 0], [0, 0]   # [queries, overflowed] of the polled calls with / without int8
         self._queries = 0                                  # queries answered so far (the clock of the re-probes)
@@ -144,6 +173,7 @@ class KeyIndex:
         self._spec = {}
         self.spec_enabled = os.environ.get("RAGRAPH_SPEC", "1") != "0"   # (RAGRAPH_SPEC=0: every call with its bound pass -- A/B)
         self.tight_enabled = os.environ.get("RAGRAPH_SPEC_TIGHT", "1") != "0"
+        self.tight_target = min(max(int(os.environ.get("RAGRAPH_TIGHT_TARGET_SOFT", self.TIGHT_TARGET_SOFT)), 0), self.TIGHT_TARGET_SOFT_MAX)
         self.last_tight = None           # the tight bound the last filtered call ran with (None: none)
         self._notes = 0                  # calls offered to _note_overflow (small calls report every fourth once settled)
         self.last_stats = None           # device view of the last filtered call's statistics words (this index, this stream)
@@ -356,7 +386,7 @@ class KeyIndex:
         speculative = False
         if len(pend) > 4 and pend[4] and len(words) > FS.KTH_HI and labelled:
             speculative = bool(words[FS.SPECULATIVE])
-            n_over = self._judge_prior(pend[4], B, words, n_over)   # (what is left is the lists' fault)
+            n_over = self._judge_prior(pend[4], B, words, n_over, pend[5] if len(pend) > 5 else None)   # (what is left is the lists' fault)
         self._overflowed += n_over
         i8_was_off = self._i8_off               # (the call ran under this setting: the overflow rule below judges IT)
         # the call's sampled candidate counts (int8 levels only are judged -- and only of a call with a bound pass: what a
@@ -381,9 +411,9 @@ class KeyIndex:
         elif acc[0] >= 4096:
             acc[0] = acc[1] = 0
 
-    def _judge_prior(self, k: int, B: int, words, n_over: int) -> int:
-        """A polled call's statistics words: feed the k-th-best history; judge a speculative call (misses, candidates,
-        overflowed lists).  Returns the overflow count the LISTS are to be judged by: a speculative call's misses are not
+    def _judge_prior(self, k: int, B: int, words, n_over: int, tight=None) -> int:
+        """A polled call's statistics words (`tight`: the tight bound that call ran with, if known): feed the k-th-best history;
+        judge a speculative call (misses, candidates, overflowed lists).  Returns the overflow count the LISTS are to be judged by: a speculative call's misses are not
         their fault, and neither are lists that overflowed under a prior (far below most queries' k-th best it floods them:
         the prior goes, the bank is judged by its calls with a bound pass)."""
         st = self._spec_state(k)
@@ -402,7 +432,7 @@ class KeyIndex:
             return lists_over
         st["used"] += 1
         st["failed"] += failed
-        self._judge_tight(st, words)
+        self._judge_tight(st, words, tight)
         loose = cand is not None and st["cand"] is not None and cand > self.SPEC_MAX_CANDIDATES * max(st["cand"], 32.0)
         if failed or loose or lists_over:
             probed_at = st.get("probed_at")
@@ -414,17 +444,47 @@ class KeyIndex:
                 st["queries"] = 0
         return 0   # (a speculative call says nothing about the lists)
 
-    def _judge_tight(self, st: dict, words):
+    def _judge_tight(self, st: dict, words, tight=None):
         """A polled speculative call's words TIGHT (a tight bound was in force), SOFT_MISSES and REPAIR (1: the 256-query
-        repair ran, 2: the all-queries level): widen the margin after a flood of soft misses, withdraw t after the level."""
+        repair ran, 2: the all-queries level): withdraw t after the level; a call that reports its tail counts (TAIL_DELTA; `tight`
+        is the t it ran with) aims the next t at the target count, any other widens the margin after a flood of soft misses."""
         if len(words) <= FS.REPAIR or not words[FS.TIGHT]:
             return
         st["soft"] = st.get("soft", 0) + words[FS.SOFT_MISSES]
         st["tight_used"] = st.get("tight_used", 0) + 1
+        points = FS.tail_points(words, tight) if self.tight_target and tight is not None else None
         if words[FS.REPAIR] == 2:
             st["tight_off_at"] = self._queries
-        if words[FS.REPAIR] == 2 or words[FS.SOFT_MISSES] > self.TIGHT_MAX_SOFT:
+            st.pop("tight_aimed", None)
+        elif points is not None and self._aims_tight(words[FS.QUERIES]):
+            st["tight_aimed"] = (self._aim_tight(points, self.tight_target), words[FS.QUERIES])
+        else:
+            points = None   # (a batch class that keeps the rule of the margin)
+        if words[FS.REPAIR] == 2 or (points is None and words[FS.SOFT_MISSES] > self.TIGHT_MAX_SOFT):
             st["tight_margin"] = min(2.0 * st.get("tight_margin", self.TIGHT_MARGIN), self.TIGHT_MARGIN_MAX)
+
+    def _aims_tight(self, B: int) -> bool:
+        """Is t placed at a soft-miss count for calls of B queries against this bank (TIGHT_TARGET_QUERIES_PER_DIM)?"""
+        return bool(self.tight_target) and B >= self.TIGHT_TARGET_QUERIES_PER_DIM * (self._width or self.dim)
+
+    @staticmethod
+    def _aim_tight(points, target: int) -> float:
+        """The t at which the cumulative count [(score, queries below it)] of a tight call -- its own t first -- meets `target`,
+        log-linear between the points (a count of 0 stands for half a query); at most the highest point; below the first point
+        by the slope of the lowest rising segment; the first point itself within a factor of two of the target."""
+        (t, c0), top = points[0], points[-1][0]
+        if target <= 2 * c0 <= 4 * target:
+            return t
+        lg = lambda c: math.log(max(float(c), 0.5))
+        if c0 < target:
+            for (x0, n0), (x1, n1) in zip(points, points[1:]):
+                if n1 >= target:   # (n0 < target <= n1: the segment rises)
+                    return min(x0 + (x1 - x0) * (lg(target) - lg(n0)) / (lg(n1) - lg(n0)), top)
+            return top
+        for x1, n1 in points[1:]:
+            if n1 > c0:
+                return t - (lg(c0) - lg(target)) * (x1 - t) / (lg(n1) - lg(c0))
+        return t - (top - t)   # (every judged query below t: one span down)
 
     def _tight_for(self, B: int, k: int, prior):
         """The tight bound for a call of B queries that runs under `prior`, or None (no prior -- which covers captures and
@@ -441,6 +501,9 @@ class KeyIndex:
         if not st["hist"]:
             return None
         t = min(h[0] for h in st["hist"]) - st.get("tight_margin", self.TIGHT_MARGIN)
+        aimed = st.get("tight_aimed")
+        if aimed is not None and self._aims_tight(B) and B <= 2 * aimed[1]:
+            t = max(t, aimed[0])   # (aimed at a soft-miss count by the tail counts of a polled call of aimed[1] queries: _judge_tight)
         return t if t > prior else None
 
     def _demote(self, what: str):
@@ -528,7 +591,7 @@ class KeyIndex:
                 if stats is not None:
                     self._host_word[1:1 + stats.numel()].copy_(stats, non_blocking=True)
             self._event.record()
-            self._pending = (self._host_word, self._event, B, had_i8, k)
+            self._pending = (self._host_word, self._event, B, had_i8, k, self.last_tight if stats is not None else None)
 
     def _cap_i8(self):
         """Before a filtered call: cap this thread's int8 levels for THIS bank (ops.set_max_i8_levels; the caller resets it
