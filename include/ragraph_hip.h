@@ -138,6 +138,33 @@ int ragraph_topk_cosine_mix_f32(const float* Q, int64_t B, const float* Kn, int6
                                 const float* Pn, int A, float w_struct, float w_sem, int k, int64_t idx_base,
                                 float* out_scores, int64_t* out_idx, void* ws, size_t ws_bytes, void* stream);
 
+/* Structure-aware retrieval from a semantic candidate list
+ *   -- RAGraph_node_fewshot/ragraph_utils/ToyGraphBase.py:47-65, for the rows where a proof shows that the canonical semantic
+ *   top-k' already holds the mixed top-k (ragraph_amd/csrc/topk_mix_rerank.hip).
+ *   sem_scores, sem_idx [B,k_list]: the canonical semantic top-k_list of every query (the bits of ragraph_topk_cosine_f32;
+ *       indices carry idx_base).   Pq [B,A] raw query codes, normalised inside as ragraph_topk_cosine_mix_f32 normalises them;
+ *       Pn [N,A] the bank's normalised codes.
+ *   For every listed key: s_struct (the A-step fmaf chain from +0) and fl(fl(s_struct * w_struct) + fl(s_sem * w_sem)), the
+ *       operations of ragraph_topk_cosine_mix_f32; then the canonical top-k of the k_list mixed scores -> out_scores, out_idx [B,k].
+ *   unproven [B] int32: 0 when the row's k-th best mixed score is STRICTLY greater than
+ *       fl(fl(s_last * w_sem) + slack), s_last the list's last score and slack the fused mixed kernels' own
+ *       (|w_struct| (1 + 2^-10) rounded up): no key outside the list can enter or tie, the row holds the bits of
+ *       ragraph_topk_cosine_mix_f32.  1 otherwise -- also for a non-finite score or an index outside [idx_base, idx_base + N)
+ *       (never read) --: the row's output is NOT the answer and the caller recomputes it with the exact call.
+ *   *unproven_count: the number of flags set (cleared inside; vector atomic adds).  It decides no result.
+ *   1 <= A <= 16, 1 <= k < k_list <= 128, w_sem > 0 and finite, w_struct finite, idx_base >= 0; RAGRAPH_EINVAL with a message
+ *   before any launch otherwise (null pointers, out aliasing the lists included).  ws: ragraph_topk_mix_rerank_workspace_bytes
+ *   (the normalised query codes).  Two launches and a 4-byte memset; no synchronisation, no read-back: capturable.
+ * ragraph_topk_rows_scatter_f32: out rows pos[m] <- rows m of (scores, idx) [M,k], pos int64 positions in [0,B) (others write
+ *   nothing): the recomputed rows written back over a call's lists.  M = 0 launches nothing. */
+size_t ragraph_topk_mix_rerank_workspace_bytes(int64_t B, int A);
+int ragraph_topk_mix_rerank_f32(const float* sem_scores, const int64_t* sem_idx, int64_t B, int k_list, const float* Pq,
+                                const float* Pn, int64_t N, int A, float w_struct, float w_sem, int k, int64_t idx_base,
+                                float* out_scores, int64_t* out_idx, int* unproven, int* unproven_count, void* ws,
+                                size_t ws_bytes, void* stream);
+int ragraph_topk_rows_scatter_f32(const float* scores, const int64_t* idx, const int64_t* pos, int64_t M, int k, int64_t B,
+                                  float* out_scores, int64_t* out_idx, void* stream);
+
 /* a1, large batches: the same result through a bf16 MFMA filter (ragraph_amd/csrc/topk_filter.hip).
  *   Exact by construction: (1) a lower bound of every query's final k-th best score -- the k-th exact score over a sample
  *   of the bank, or, for banks of >= 8192 keys, min over k parts of a prefix of the best approximate score in the part,

@@ -86,6 +86,10 @@ SIGNATURES = {
     "ragraph_topk_cosine_mix_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
     "ragraph_topk_cosine_mix_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _f32, _f32, _i32, _i64, _vp, _vp, _vp,
                                           _sz, _vp]),
+    "ragraph_topk_mix_rerank_workspace_bytes": (_sz, [_i64, _i32]),
+    "ragraph_topk_mix_rerank_f32": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _i32, _f32, _f32, _i32, _i64, _vp, _vp, _vp, _vp,
+                                          _vp, _sz, _vp]),
+    "ragraph_topk_rows_scatter_f32": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp]),
     "ragraph_topk_merge_f32": (_i32, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "ragraph_topk_cosine_tail_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "ragraph_topk_cosine_tail_f32": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

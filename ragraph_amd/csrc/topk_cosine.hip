@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "mix_slack.h"
 #include "topk_large.h"
 #include "segment_plan.h"
 
@@ -1583,8 +1584,7 @@ extern "C" int ragraph_topk_cosine_mix_f32(const float* Q, int64_t B, const floa
   p.A = A;
   p.w_struct = w_struct;
   p.w_sem = w_sem;
-  // |s_struct| <= |a||b| (1 + A 2^-23) for rows normalised to within a few ulp of 1: 2^-10 covers it many times over
-  p.mix_slack = nextafterf((float)(fabs((double)w_struct) * (1.0 + 1.0 / 1024)), __builtin_huge_valf());
+  p.mix_slack = mix_slack_of(w_struct);   // (mix_slack.h: shared with the rerank of filtered candidate lists)
   return fused_topk<false, true>(p, pl, D, idx_base, out_scores, out_idx, st);
 }
 

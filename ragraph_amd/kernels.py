@@ -203,6 +203,93 @@ def topk_cosine_mix(q: torch.Tensor, keys_normalized: torch.Tensor, pos_q: torch
     return scores, idx
 
 
+MIX_FILTER_MAX_K = 64      # mix_filter_list(k) <= TOPK_FILTER_MAX: the longest list the filtered entries finish
+
+
+def mix_filter_list(k: int) -> int:
+    """k', the semantic candidates KeyIndex.topk_mix asks the filter for when the mixed top-k is wanted."""
+    return min(128, max(32, 2 * k))
+
+
+def mix_filter_helps(B: int, n_keys: int, D: int, k: int) -> bool:
+    """True where the mixed top-k through the filter (KeyIndex.topk_mix: filtered semantic top-k', topk_mix_rerank, one 4-byte
+    read-back, exact repair of the unproven rows) is the faster way to the bits of topk_cosine_mix.  Host arithmetic only;
+    RAGRAPH_MIX_FILTER=0 (read per call) and RAGRAPH_EXACT_FP32=1 switch the route off."""
+    if os.environ.get("RAGRAPH_MIX_FILTER", "1") == "0" or os.environ.get("RAGRAPH_EXACT_FP32") == "1":
+        return False
+    if D not in (64, 128, 256) or not 1 <= k <= MIX_FILTER_MAX_K:
+        return False
+    return mix_filter_measured(B, n_keys, D, k)
+
+
+def mix_filter_measured(B: int, n_keys: int, D: int, k: int) -> bool:
+    """The measured part of mix_filter_helps: the shapes where tools/topk_mix_filtered_probe.py measured the route faster than the
+    exact fused call by more than the spread of the pair (profiles/topk_mix_filtered.txt).  What was not measured stays out."""
+    # MI355X, ms per call, exact vs routed at the few-shot weights (0.001, 0.999), where no row is unproven (k = 10 / 20 / 40):
+    #   100 000 x 1M x 256: 393 vs 20.5 / 403 vs 21.3 / 1649 vs 26.0;   4096 x 1M x 256: 18.0 vs 1.09 / 19.7 vs 1.13 / 67.4 vs 1.43;
+    #   256 x 1M x 256: 1.86 vs 0.22 / 3.05 vs 0.23 / 4.22 vs 0.29;   100 000 x 1M x 128: 207 vs 11.8 / 215 vs 12.2 / 1309 vs 14.8;
+    #   65 536 keys, D = 128 and 256, 256 / 4096 / 100 000 queries: ROUTE at every k.
+    # The rule does not know the weights: where they leave most rows unproven -- (0.05, 0.95) at k >= 20 and (0.3, 0.7) everywhere on
+    # that data -- the routed call costs the exact call plus 2 - 8 %, and the demotion (KeyIndex.MIX_FILTER_MAX_UNPROVEN) ends it
+    # after one call.  16 queries: k = 10 goes to the single-launch kernel (no filtered route), k = 20 lost or drew at 65 536 keys
+    # and won at 1M; nothing between 16 and 256 queries was measured.  D = 64 and banks below 65 536 keys: not measured.
+    # Memory keeps the rule narrower than the clock would: the mixed call promises to stay far below a B x N score matrix (growth
+    # below B * N / 2 bytes), and the filtered call brings the bank's bf16 copy (2 N D bytes) and its own workspace -- 1.1 GB at
+    # 5000 x 200 000 x 256, more than twice that promise.  Kept: the measured classes whose matrix dwarfs both, banks of >= 1M keys
+    # from 4096 queries; the smaller shapes that won on time stay on the exact call until the route's footprint is dealt with.
+    return n_keys >= (1 << 20) and D in (128, 256) and B >= 4096
+
+
+def topk_mix_rerank(sem_scores: torch.Tensor, idx: torch.Tensor, pos_q: torch.Tensor, pos_normalized: torch.Tensor,
+                    w_struct: float, w_sem: float, k: int, idx_base: int = 0):
+    """The canonical top-k of  w_struct * cos(position codes) + w_sem * s_sem  over the keys of canonical semantic lists
+    (sem_scores, idx) [B, k'], k < k' <= 128 -- the operations of topk_cosine_mix on those keys -- and the proof that no key
+    outside a list can enter or tie (ragraph_topk_mix_rerank_f32; w_sem > 0).  Returns (scores [B,k], idx [B,k], unproven_flags
+    [B] int32, unproven_count [1] int32): a row whose flag is 0 holds the bits of topk_cosine_mix; a row whose flag is 1 does NOT
+    and must be recomputed by it.  pos_q [B,A] raw (normalised inside), pos_normalized [N,A]; idx carries idx_base.
+    No synchronisation, no read-back."""
+    L = _ready()
+    s = _f32c(sem_scores, "topk_mix_rerank.sem_scores")
+    i = _idxc(idx, "topk_mix_rerank.idx")
+    pq = _f32c(pos_q, "topk_mix_rerank.pos_q")
+    pn = _f32c(pos_normalized, "topk_mix_rerank.pos_normalized")
+    if s.dim() != 2 or s.shape != i.shape:
+        raise RagraphNativeError(f"topk_mix_rerank: lists {tuple(s.shape)} / {tuple(i.shape)}")
+    if pq.dim() != 2 or pn.dim() != 2 or pq.shape[1] != pn.shape[1] or pq.shape[0] != s.shape[0]:
+        raise RagraphNativeError(f"topk_mix_rerank: codes {tuple(pq.shape)} x {tuple(pn.shape)} do not match lists {tuple(s.shape)}")
+    B, kl = s.shape
+    Nk, A = pn.shape
+    out_s = torch.empty((B, k), dtype=torch.float32, device=s.device)
+    out_i = torch.empty((B, k), dtype=torch.int64, device=s.device)
+    flags = torch.empty(B, dtype=torch.int32, device=s.device)
+    count = torch.zeros(1, dtype=torch.int32, device=s.device)
+    if B == 0:
+        return out_s, out_i, flags, count
+    # (the normalised query codes: B * A floats of this call's own, exactly sized -- not the shared grow-only scratch)
+    ws = torch.empty(L.ragraph_topk_mix_rerank_workspace_bytes(B, A), dtype=torch.uint8, device=s.device)
+    N.check(L.ragraph_topk_mix_rerank_f32(s.data_ptr(), i.data_ptr(), B, kl, pq.data_ptr(), pn.data_ptr(), Nk, A, float(w_struct),
+                                          float(w_sem), k, idx_base, out_s.data_ptr(), out_i.data_ptr(), flags.data_ptr(),
+                                          count.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "topk_mix_rerank")
+    return out_s, out_i, flags, count
+
+
+def scatter_topk_rows_(scores: torch.Tensor, idx: torch.Tensor, pos: torch.Tensor, rows_s: torch.Tensor, rows_i: torch.Tensor):
+    """scores[pos[m]] = rows_s[m], idx[pos[m]] = rows_i[m] in place (lists [B,k] f32 / i64, rows [M,k], pos [M] int64):
+    ragraph_topk_rows_scatter_f32.  Returns (scores, idx)."""
+    L = _ready()
+    if not (scores.is_cuda and scores.is_contiguous() and scores.dtype == torch.float32 and idx.is_cuda and idx.is_contiguous()
+            and idx.dtype == torch.int64 and scores.dim() == 2 and scores.shape == idx.shape):
+        raise RagraphNativeError("scatter_topk_rows_: the lists must be contiguous [B,k] f32 / i64 ROCm device tensors")
+    rs, ri, pos = _f32c(rows_s, "scatter_topk_rows_.rows"), _idxc(rows_i, "scatter_topk_rows_.rows"), _idxc(pos, "scatter_topk_rows_.pos")
+    M = pos.numel()
+    if rs.shape != (M, scores.shape[1]) or ri.shape != rs.shape:
+        raise RagraphNativeError(f"scatter_topk_rows_: rows {tuple(rs.shape)} / {tuple(ri.shape)} for {M} positions of {tuple(scores.shape)}")
+    if M:
+        N.check(L.ragraph_topk_rows_scatter_f32(rs.data_ptr(), ri.data_ptr(), pos.data_ptr(), M, scores.shape[1], scores.shape[0],
+                                                scores.data_ptr(), idx.data_ptr(), _stream()), "scatter_topk_rows_")
+    return scores, idx
+
+
 def keys_to_bf16(keys_normalized: torch.Tensor) -> torch.Tensor:
     """bf16 copy of the bank for topk_cosine_filtered, in MFMA fragment order (csrc/filter_common.h): rows zero-padded to
     a multiple of 256 + one row holding the largest rounding error; int16 storage, 2 D bytes per key."""

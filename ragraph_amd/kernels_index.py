@@ -133,6 +133,12 @@ class KeyIndex:
     # path).  RAGRAPH_BANK_TAIL=0: extend seals at once -- the bank of one version this class was before (A/B, escape hatch).
     TAIL_DIVISOR = 8
     TAIL_MAX_ROWS = 512
+    # Mixed retrieval through the filter (topk_mix): a call whose unproven share exceeds this is answered all the same -- its
+    # unproven rows by the exact call -- but later calls with its weights and k go straight to the exact call, until the rows
+    # or the weights change.  The largest of 1/16, 1/8, 1/4, 1/2 at which the route still beat the exact call by more than the
+    # spread at both 4096 and 100 000 queries x 1M x 256 (profiles/topk_mix_filtered.txt, forced shares; ms exact vs routed at
+    # 1/16, 1/8, 1/4, 1/2: 18.0 vs 3.0, 4.2, 6.5, 10.9 and 393 vs 49.7, 76.6, 131, 226).
+    MIX_FILTER_MAX_UNPROVEN = 1.0 / 2
 
     def __init__(self, keys_normalized: torch.Tensor, ops=None, dedup: bool = True):
         if ops is None:
@@ -186,6 +192,10 @@ class KeyIndex:
         # retired rows (retire): the sorted host ids (int64 CPU tensor; the authority) and the device bitmap over the physical
         # rows (int32 words, bit r & 31 of word r >> 5); both None until a row is retired
         self._retired = self._bitmap = None
+        # topk_mix: the (w_struct, w_sem, k) whose calls go straight to the exact call, the weights they were judged under, and
+        # counters for the tests and the probe
+        self._mix_demoted, self._mix_weights = set(), None
+        self.mix_stats = {"filtered_calls": 0, "exact_calls": 0, "rows_unproven": 0, "demotions": 0}
 
     @property
     def sealed_rows(self) -> int:
@@ -238,6 +248,7 @@ class KeyIndex:
         self._grow_bitmap(n)
         self.ops.retire_rows(self._bitmap, new.to(self.keys_normalized.device), n)
         self._retired = merged
+        self._mix_demoted.clear()   # (the live rows changed: topk_mix judges them again)
 
     def _grow_bitmap(self, n_rows: int) -> None:
         """The bitmap covers n_rows rows (new words zero: new rows are live); made here on first use."""
@@ -278,6 +289,7 @@ class KeyIndex:
         self._retired = self._bitmap = None
         self._pending = None
         self._spec = {}
+        self._mix_demoted.clear()
 
     @staticmethod
     def _capturing() -> bool:
@@ -305,6 +317,8 @@ class KeyIndex:
         else:
             self.keys_normalized = self._store = keys_normalized
         self._tail_rows = n_new - self._sealed_rows
+        if n_new > n_old:
+            self._mix_demoted.clear()   # (new rows: topk_mix judges the bank again)
         if self._bitmap is not None:
             self._grow_bitmap(n_new)   # (zero bits: the new rows are live)
         if not self.tail_enabled or getattr(self.ops, "topk_cosine_tail", None) is None:
@@ -643,6 +657,67 @@ class KeyIndex:
                                      "then KeyIndex.rebase)")
         s, i = self._topk_rows(q, k_in, idx_base)
         s, i, _ = self.ops.topk_drop_rows(s, i, self._bitmap, n, k, idx_base=idx_base)   # (never short: k <= live rows)
+        return s, i
+
+    def _mix_filter_open(self, B: int, k: int, k_list: int, w_struct: float, w_sem: float) -> bool:
+        """Does topk_mix take the filtered route for this call as the index stands?  No side effect."""
+        ops = self.ops
+        if not (0.0 < w_sem < math.inf) or not math.isfinite(w_struct) or self._capturing():
+            return False
+        if any(getattr(ops, name, None) is None for name in ("topk_mix_rerank", "mask_positions", "gather_rows", "scatter_topk_rows_")):
+            return False
+        n, D = self._sealed_rows + self._tail_rows, self._width or self.dim
+        if k_list > n - self.retired_rows or not self._says("mix_filter_helps", B, n, D, k):
+            return False
+        k_in = min(k_list + self.retired_rows, n)   # (topk's over-fetch)
+        if k_in > TOPK_FILTER_MAX:
+            return False
+        route = self._route(B, self._sealed_rows, D, k_in)
+        if route == COLLAPSED:   # the unique rows' own index answers: its route counts
+            inner = self._collapsed[0]
+            route = inner._route(B, inner._sealed_rows, D, min(k_in, inner._sealed_rows))
+        return route in (FILTERED, WIDE, WIDE128) and (float(w_struct), float(w_sem), k) not in self._mix_demoted
+
+    def topk_mix(self, q: torch.Tensor, pos_q: torch.Tensor, pos_normalized: torch.Tensor, w_struct: float, w_sem: float, k: int,
+                 exact):
+        """The canonical top-k of  w_struct * cos(position codes) + w_sem * cos(embeddings)  over the bank's live rows: the bits
+        of `exact(q, pos_q, k)`, the owner's exact mixed call (ops.topk_cosine_mix over its rows, with its own over-fetch for
+        retired rows), reached through the filter where that pays:
+        1. topk(q, k'), k' = ops.mix_filter_list(k) > k -- the canonical semantic candidates, by whatever route, tail, retired
+           rows, collapsed duplicates and priors as ever;
+        2. ops.topk_mix_rerank: the exact mixed scores of those k' keys, their canonical top-k, and per row the proof that no
+           key outside the list can enter or tie (k-th best mixed score > fl(fl(s_last * w_sem) + slack));
+        3. ONE 4-byte read-back of the unproven count -- the price of this route: a synchronisation, so never under a capture;
+        4. unproven rows (ops.mask_positions of the flags: one more read-back, only then) are gathered, answered by `exact`
+           and written back (ops.scatter_topk_rows_).  Nothing approximate is ever returned.
+        The route is taken when w_sem > 0, the stream is not being captured, ops.mix_filter_helps says so, _route sends a list
+        of k' keys to one of the filtered entries and (w_struct, w_sem, k) is not demoted; otherwise the call IS exact(q, pos_q,
+        k).  A call whose unproven share exceeds MIX_FILTER_MAX_UNPROVEN demotes its (w_struct, w_sem, k) until the rows (extend,
+        retire, rebase) or the weights change: a demotion never changes a bit, only the cost.  mix_stats counts the calls of
+        either kind, the unproven rows and the demotions."""
+        ops, st, B = self.ops, self.mix_stats, int(q.shape[0])
+        weights = (float(w_struct), float(w_sem))
+        if weights != self._mix_weights:
+            self._mix_weights = weights
+            self._mix_demoted.clear()
+        k_list = getattr(ops, "mix_filter_list", lambda kk: min(128, max(32, 2 * kk)))(k)
+        if B == 0 or not self._mix_filter_open(B, k, k_list, w_struct, w_sem):
+            st["exact_calls"] += 1
+            return exact(q, pos_q, k)
+        s_sem, i_sem = self.topk(q, k_list)
+        s, i, flags, count = ops.topk_mix_rerank(s_sem, i_sem, pos_q, pos_normalized, w_struct, w_sem, k)
+        unproven = int(count.item())   # the read-back
+        st["filtered_calls"] += 1
+        st["rows_unproven"] += unproven
+        if unproven == B:
+            s, i = exact(q, pos_q, k)
+        elif unproven:
+            rows = ops.mask_positions(flags.ne(0))
+            rs, ri = exact(ops.gather_rows(q, rows), ops.gather_rows(pos_q, rows), k)
+            ops.scatter_topk_rows_(s, i, rows, rs, ri)
+        if unproven > self.MIX_FILTER_MAX_UNPROVEN * B:
+            self._mix_demoted.add((*weights, k))
+            st["demotions"] += 1
         return s, i
 
     def _topk_rows(self, q: torch.Tensor, k: int, idx_base: int = 0, exchange=None, plan_n: int = 0, prior=None):

@@ -325,21 +325,31 @@ class ToyGraphBase:
             self.compact()
         if self.structure_weight != 0:
             pos = search_positions.reshape(1, -1) if search_positions.dim() == 1 else search_positions
-            r, n = self.retired_rows, self._keys.n
-            if not r:
-                return K.topk_cosine_mix(q, self.keys_normalized, pos, self.positions_normalized, self.structure_weight,
-                                         self.semantic_weight, k)
-            k_in = min(k + r, n)   # (this branch bypasses KeyIndex: the same over-fetch and the same drop around its own search)
-            if k_in > K.TOPK_ORDERED_MAX:
-                raise K.RagraphNativeError(f"topk: k={k} with {r} retired rows needs lists of {k_in} > {K.TOPK_ORDERED_MAX} "
-                                           "keys: compact() the bank (not done under a stream capture)")
-            s, i = K.topk_cosine_mix(q, self.keys_normalized, pos, self.positions_normalized, self.structure_weight,
-                                     self.semantic_weight, k_in)
-            s, i, _ = K.topk_drop_rows(s, i, self._index.retired_bitmap, n, k)
-            return s, i
+            if self._index is None and K.padded_dim(q.shape[1]) == q.shape[1]:   # (another width: no padded bank copy for this alone)
+                self._index = K.KeyIndex(self.keys_normalized)
+            if self._index is None:
+                return self._topk_mix_exact(q, pos, k)
+            # through the filter where that pays (K.KeyIndex.topk_mix: the same bits), else the exact call below
+            return self._index.topk_mix(q, pos, self.positions_normalized, self.structure_weight, self.semantic_weight, k,
+                                        self._topk_mix_exact)
         if self._index is None:
             self._index = K.KeyIndex(self.keys_normalized)
         return self._index.topk(q, k)  # fp32 streaming / tile kernel or, for large batches, the bf16-filtered exact path
+
+    def _topk_mix_exact(self, q: Tensor, pos: Tensor, k: int):
+        """The exact mixed top-k of the live rows (K.topk_cosine_mix: no filter, no read-back, capturable)."""
+        r, n = self.retired_rows, self._keys.n
+        if not r:
+            return K.topk_cosine_mix(q, self.keys_normalized, pos, self.positions_normalized, self.structure_weight,
+                                     self.semantic_weight, k)
+        k_in = min(k + r, n)   # (this branch bypasses KeyIndex: the same over-fetch and the same drop around its own search)
+        if k_in > K.TOPK_ORDERED_MAX:
+            raise K.RagraphNativeError(f"topk: k={k} with {r} retired rows needs lists of {k_in} > {K.TOPK_ORDERED_MAX} "
+                                       "keys: compact() the bank (not done under a stream capture)")
+        s, i = K.topk_cosine_mix(q, self.keys_normalized, pos, self.positions_normalized, self.structure_weight,
+                                 self.semantic_weight, k_in)
+        s, i, _ = K.topk_drop_rows(s, i, self._index.retired_bitmap, n, k)
+        return s, i
 
     def retrieve_indices(self, search_keys: Tensor, add_noise: bool, search_adj=None,
                          search_positions: Tensor | None = None, anchors: Tensor | None = None,
