@@ -91,13 +91,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // the bits depend on it.  ragraph_amd/kernels.py keeps the same number as ROW_BLOCK.
 constexpr int ROW_BLOCK = 4096;
 
-#define RG_NEG_INF (-__builtin_huge_valf())
-#define RG_IDX_NONE INT_MAX
-
-// Canonical top-k order: score descending, then index ascending.  Strict total order when indices are unique.
-__device__ __forceinline__ bool cand_better(float s1, int i1, float s2, int i2) {
-  return (s1 > s2) || (s1 == s2 && i1 < i2);
-}
+#define RG_NEG_INF (-__builtin_huge_valf())   // (the score of a top-k list's empty entry: topk_order.h)
 
 // Epilogue activations (selectors in ragraph_hip.h).
 __device__ __forceinline__ float apply_act(float x, int act, float alpha) {

@@ -2,6 +2,7 @@
 // topk_filter_direct.hip: the register-fed kernel for up to 256 queries).
 #pragma once
 #include "common.h"
+#include "topk_order.h"   // (f2ord / ord2f: the group maxima and the k-th-score words)
 #include <climits>
 
 namespace ragraph {
@@ -117,13 +118,6 @@ float filter_thread_prior();
 int launch_overflow_fixup(int D, const float* Qn, const float* Kn, int64_t N, int k, int64_t idx_base, const int* count,
                           const int* list, float* out_s, int64_t* out_i, int* done, float* part_s, int64_t* part_i, int64_t B,
                           void* stream);
-
-// float <-> int with the same order (for atomicMax on scores of either sign)
-__device__ __forceinline__ int f2ord(float f) {
-  const int b = __float_as_int(f);
-  return b >= 0 ? b : b ^ 0x7FFFFFFF;
-}
-__device__ __forceinline__ float ord2f(int o) { return __int_as_float(o >= 0 ? o : o ^ 0x7FFFFFFF); }
 
 // How a filter launch obtains a query's pass threshold thr[q] = theta[q] - eps(q), where theta[q] is a proven lower
 // bound of the query's final k-th best exact score: the k-th exact score of everything rescored so far (prev_scores),

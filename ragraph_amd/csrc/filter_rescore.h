@@ -162,25 +162,26 @@ __device__ __forceinline__ bool rescore_scored_query(const float4* __restrict__ 
   const int r1key = lane < SCORED_R1 ? stage[lane] : -1;
   __builtin_amdgcn_wave_barrier();
   const float e1 = coop_scores_few<D>(qrow, Kn, r1key, lane, sm);
-  // W: round 1 (lanes 0..15) and the previous winners (lanes 16..16+k-1) as canonical 64-bit keys (0 = no pair)
+  // W: round 1 (lanes 0..15) and the previous winners (lanes 16..16+k-1) as canonical 64-bit keys in two words (topk_order.h:
+  // order_key, pair_lo; 0 = no pair)
   unsigned wh = 0u, wl = 0u;
   unsigned vh = 0u, vl = 0u;  // (LW = 64) row V: the previous winners
   if (lane < SCORED_R1) {
-    wh = select_ord(e1);
-    wl = ~(unsigned)r1key;
+    wh = order_key(e1);
+    wl = pair_lo(r1key);
   } else if (LW == 32 && prev_s && lane < SCORED_R1 + k) {
     const int64_t pv = prev_i[lane - SCORED_R1];
     if (pv < INT_MAX) {
-      wh = select_ord(prev_s[lane - SCORED_R1]);
-      wl = ~(unsigned)(int)pv;
+      wh = order_key(prev_s[lane - SCORED_R1]);
+      wl = pair_lo((int)pv);
     }
   }
   if constexpr (LW == 64) {
     if (prev_s && lane < k) {
       const int64_t pv = prev_i[lane];
       if (pv < INT_MAX) {
-        vh = select_ord(prev_s[lane]);
-        vl = ~(unsigned)(int)pv;
+        vh = order_key(prev_s[lane]);
+        vl = pair_lo((int)pv);
       }
     }
   }
@@ -223,7 +224,7 @@ __device__ __forceinline__ bool rescore_scored_query(const float4* __restrict__ 
       }
     }
   }
-  const float theta_e = n_w >= k ? select_unord(kh) : RG_NEG_INF;
+  const float theta_e = n_w >= k ? order_unkey(kh) : RG_NEG_INF;
   // (an entry's integer is (I << 1) | class of its key's granule: each class has its own bound -- compared on the doubled scale)
   const int t_e0 = filter_threshold_i8_at(thr, b, theta_e, 0), t_e1 = filter_threshold_i8_at(thr, b, theta_e, 1);
   auto twice = [](int t) { return t <= -(1 << 24) ? INT_MIN : (t >= (1 << 24) ? INT_MAX : 2 * t); };
@@ -253,7 +254,7 @@ __device__ __forceinline__ bool rescore_scored_query(const float4* __restrict__ 
       const int c = c0 + lane;
       const int kk = (lane < ROWS && c < ns) ? surv[c] : -1;
       const float acc = ns - c0 <= 16 ? coop_scores_few<D>(qrow, Kn, kk, lane, sm) : coop_scores<D, ROWS>(qrow, Kn, kk, lane, sm);
-      const unsigned sh = select_ord(acc), sl = ~(unsigned)kk;
+      const unsigned sh = order_key(acc), sl = pair_lo(kk);
       const bool beats = kk >= 0 && pair_gt(sh, sl, kh, kl);
       const unsigned long long bm = __ballot(beats);
       const int cnt = __popcll(bm);
@@ -297,18 +298,18 @@ __device__ __forceinline__ bool rescore_scored_query(const float4* __restrict__ 
       }
   }
   if (w_valid && rank_w < k) {
-    out_s[rank_w] = select_unord(wh);
-    out_i[rank_w] = (int64_t)(int)~wl + base;
+    out_s[rank_w] = order_unkey(wh);
+    out_i[rank_w] = (int64_t)pair_id(wl) + base;
   }
   if constexpr (LW == 64) {
     if (v_valid && rank_v < k) {
-      out_s[rank_v] = select_unord(vh);
-      out_i[rank_v] = (int64_t)(int)~vl + base;
+      out_s[rank_v] = order_unkey(vh);
+      out_i[rank_v] = (int64_t)pair_id(vl) + base;
     }
   }
   if (lane < nb && rank_b < k) {
-    out_s[rank_b] = select_unord(bh);
-    out_i[rank_b] = (int64_t)(int)~bl + base;
+    out_s[rank_b] = order_unkey(bh);
+    out_i[rank_b] = (int64_t)pair_id(bl) + base;
   }
   if (lane < k && lane >= n_w + nb) {
     out_s[lane] = RG_NEG_INF;
@@ -442,6 +443,7 @@ __device__ __forceinline__ void exact_scan_query(const float4* qs /* LDS: the qu
       const float s = __shfl(sc, src);
       const int id = __shfl(key, src);
       if constexpr (LW <= 64) {
+        // (as in exact_scan_wave, rescore_common.h)
         const unsigned long long ahead = __ballot(lane < k && cand_better(es, ei, s, id));
         const int pos = __popcll(ahead);
         const float us = __shfl_up(es, 1);

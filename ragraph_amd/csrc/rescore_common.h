@@ -8,20 +8,13 @@
 namespace ragraph {
 
 // ---- canonical top-k of a wave's 64 NSL (score, id) pairs (score descending, id ascending; k <= LW) -------------------
-// A pair travels as one 64-bit key whose unsigned order is the canonical order: the score's bits made monotone in the
-// upper word, ~id in the lower; an empty slot (-inf, INT_MAX) and a pair already taken are key 0, which decodes to
-// (-inf, INT64_MAX).  Round r: every lane's best remaining key, the wave's maximum of those -- four DPP steps inside
+// A pair travels as its 64-bit key (topk_order.h: pair_key), whose unsigned order is the canonical order; an empty slot
+// (-inf, INT_MAX) and a pair already taken are key 0, which decodes to (-inf, INT64_MAX).
+// Round r: every lane's best remaining key, the wave's maximum of those -- four DPP steps inside
 // each row of 16 lanes (quad_perm / row_half_mirror / row_mirror: no LDS traffic) and the four row maxima through
 // v_readlane, i.e. a wave-uniform value -- which lane r keeps and every lane strikes from its slots.  (The __shfl_xor
 // butterfly this replaces was twelve dependent ds_bpermute per round: ~0.8 us a round, 8 us a call at k = 10, three
 // such calls in a row in the rescoring of a small batch.)
-__device__ __forceinline__ unsigned select_ord(float f) {
-  unsigned u = __float_as_uint(f);
-  if (u == 0x80000000u) u = 0u;  // -0 == +0
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float select_unord(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o); }
-
 template <int CTRL>
 __device__ __forceinline__ void select_dpp_max(unsigned& hi, unsigned& lo) {
   const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp((int)hi, (int)hi, CTRL, 0xF, 0xF, false);
@@ -41,9 +34,9 @@ __device__ __forceinline__ void wave_select(const float (&s)[NSL], const int (&i
   unsigned khi[NSL], klo[NSL];
 #pragma unroll
   for (int u = 0; u < NSL; ++u) {
-    const bool empty = id[u] == INT_MAX;
-    khi[u] = empty ? 0u : select_ord(s[u]);
-    klo[u] = empty ? 0u : ~(unsigned)id[u];
+    const bool empty = id[u] == RG_IDX_NONE;   // (pair_key's rule, on the two words the rounds compare)
+    khi[u] = empty ? 0u : order_key(s[u]);
+    klo[u] = empty ? 0u : pair_lo(id[u]);
   }
   if constexpr (NSL <= 2 || LW > 64) {
     // Up to 128 pairs: RANK BY COUNTING instead of k rounds.  Every key is broadcast once (v_readlane, a wave-uniform
@@ -75,8 +68,8 @@ __device__ __forceinline__ void wave_select(const float (&s)[NSL], const int (&i
 #pragma unroll
     for (int u = 0; u < NSL; ++u) {
       if (mine[u] != 0ull && rank[u] < k) {
-        out_s[rank[u]] = select_unord(khi[u]);
-        out_i[rank[u]] = (int64_t)(int)~klo[u] + base;
+        out_s[rank[u]] = order_unkey(khi[u]);
+        out_i[rank[u]] = (int64_t)pair_id(klo[u]) + base;
       }
     }
     if constexpr (LW > 64) {
@@ -92,7 +85,7 @@ __device__ __forceinline__ void wave_select(const float (&s)[NSL], const int (&i
     if (kth_out) {
 #pragma unroll
       for (int u = 0; u < NSL; ++u)
-        if (mine[u] != 0ull && rank[u] == k - 1) *kth_out = select_unord(khi[u]);
+        if (mine[u] != 0ull && rank[u] == k - 1) *kth_out = order_unkey(khi[u]);
       if (lane == 0 && n_real < k) *kth_out = RG_NEG_INF;
     }
     return;
@@ -133,9 +126,9 @@ __device__ __forceinline__ void wave_select(const float (&s)[NSL], const int (&i
   }
   if (lane < k) {
     const bool empty = (my_hi | my_lo) == 0u;
-    out_s[lane] = empty ? RG_NEG_INF : select_unord(my_hi);
-    out_i[lane] = empty ? INT64_MAX : (int64_t)(int)~my_lo + base;
-    if (kth_out && lane == k - 1) *kth_out = empty ? RG_NEG_INF : select_unord(my_hi);
+    out_s[lane] = empty ? RG_NEG_INF : order_unkey(my_hi);
+    out_i[lane] = empty ? INT64_MAX : (int64_t)pair_id(my_lo) + base;
+    if (kth_out && lane == k - 1) *kth_out = empty ? RG_NEG_INF : order_unkey(my_hi);
   }
 }
 
@@ -358,6 +351,8 @@ __device__ __forceinline__ void exact_scan_wave(const float4* qrow, const float*
       pend &= pend - 1;
       const float s = __shfl(sc, src);
       const int id = __shfl(key, src);
+      // (topk_order.h's lds_insert_coop on a register-resident list.  Kept in place, here and in exact_scan_query: as a shared
+      // function it changed the instructions of every kernel that inlines a scan)
       const unsigned long long ahead = __ballot(lane < k && cand_better(es, ei, s, id));
       const int pos = __popcll(ahead);
       const float us = __shfl_up(es, 1);

@@ -11,35 +11,12 @@
 //   position_code    1/(d+1) if d < dis_q else 0 to anchors   PositionAwareEncoder.py:6-24
 //
 // topk_rows is HBM streaming (4 B per score): one 256-thread workgroup per row, 16 B/lane coalesced loads, a wave-level
-// threshold, and the wave-cooperative sorted insert shared with the fused kernels; the 4 wave lists are merged at the
+// threshold, and the wave-cooperative sorted insert shared with the fused kernels (topk_order.h); the 4 wave lists are merged at the
 // end.  Canonical order (score desc, index asc), so it agrees with the fused cosine top-k on the same scores.
 #include "common.h"
+#include "topk_order.h"
 
 namespace ragraph {
-
-__device__ __forceinline__ float rows_insert_coop(float* ls, int* li, int k, float s, int idx, int lane) {
-  const bool mine = lane < k;
-  float es = mine ? ls[lane] : 0.f;
-  int ei = mine ? li[lane] : 0;
-  const unsigned long long ahead = __ballot(mine && cand_better(es, ei, s, idx));
-  const int pos = __popcll(ahead);
-  const float us = __shfl_up(es, 1);
-  const int ui = __shfl_up(ei, 1);
-  if (pos < k) {
-    if (lane == pos) {
-      es = s;
-      ei = idx;
-    } else if (lane > pos) {
-      es = us;
-      ei = ui;
-    }
-    if (mine && lane >= pos) {
-      ls[lane] = es;
-      li[lane] = ei;
-    }
-  }
-  return __shfl(es, k - 1);
-}
 
 __global__ void __launch_bounds__(256) topk_rows_kernel(const float* __restrict__ S, int64_t N, int64_t ld, int k,
                                                         float* __restrict__ out_s, int64_t* __restrict__ out_i) {
@@ -80,7 +57,7 @@ __global__ void __launch_bounds__(256) topk_rows_kernel(const float* __restrict_
             const int src = __ffsll((long long)pend) - 1;
             pend &= pend - 1;
             const float sc = __shfl(e[r], src);
-            thr = rows_insert_coop(ls[wave], li[wave], k, sc, (int)(4 * (c0 + src) + r), lane);
+            thr = lds_insert_coop(ls[wave], li[wave], 0, k, 1, sc, (int)(4 * (c0 + src) + r), lane);
             pend &= __ballot(e[r] >= thr);
           }
         }
@@ -94,7 +71,7 @@ __global__ void __launch_bounds__(256) topk_rows_kernel(const float* __restrict_
     while (pend) {
       const int src = __ffsll((long long)pend) - 1;
       pend &= pend - 1;
-      thr = rows_insert_coop(ls[wave], li[wave], k, __shfl(v, src), (int)(e0 + src), lane);
+      thr = lds_insert_coop(ls[wave], li[wave], 0, k, 1, __shfl(v, src), (int)(e0 + src), lane);
       pend &= __ballot(v >= thr);
     }
   }
@@ -140,11 +117,6 @@ __global__ void __launch_bounds__(256) topk_rows_kernel(const float* __restrict_
 // integer image of the floats, 256-bin histograms in LDS), then one ordered pass that writes the indices of every score
 // above it and of the first (k - #above) scores equal to it -- the canonical tie rule (score descending, index
 // ascending) -- in ASCENDING index order.  Deterministic: no atomics on global memory, positions by prefix sums.
-__device__ __forceinline__ unsigned select_key(float f) {  // larger float -> larger unsigned
-  unsigned b = __float_as_uint(f);
-  if (b == 0x80000000u) b = 0;  // -0 and +0 are one score (they compare equal: a tie, broken by index)
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 
 __global__ void __launch_bounds__(256) topk_select_rows_kernel(const float* __restrict__ S, int64_t N, int64_t ld, int64_t k,
                                                                float* __restrict__ out_kth, int64_t* __restrict__ out_idx) {
@@ -163,7 +135,7 @@ __global__ void __launch_bounds__(256) topk_select_rows_kernel(const float* __re
     hist[tid] = 0;
     __syncthreads();
     for (int64_t e = tid; e < N; e += 256) {
-      const unsigned key = select_key(row[e]);
+      const unsigned key = order_key(row[e]);
       if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
     }
     __syncthreads();
@@ -198,7 +170,7 @@ __global__ void __launch_bounds__(256) topk_select_rows_kernel(const float* __re
     unsigned key = 0;
     bool gt = false, eq = false;
     if (e < N) {
-      key = select_key(row[e]);
+      key = order_key(row[e]);
       gt = key > kth_key;
       eq = key == kth_key;
     }
@@ -272,7 +244,7 @@ __global__ void __launch_bounds__(256) select_hist_kernel(const float* __restric
   const int64_t e0 = (int64_t)blockIdx.x * SELECT_CHUNK;
   const int64_t e1 = e0 + SELECT_CHUNK < N ? e0 + SELECT_CHUNK : N;
   for (int64_t e = e0 + tid; e < e1; e += 256) {
-    const unsigned key = select_key(row[e]);
+    const unsigned key = order_key(row[e]);
     if ((key & mask) == prefix) atomicAdd(&h[(key >> shift) & 255u], 1u);
   }
   __syncthreads();
@@ -313,7 +285,7 @@ __global__ void __launch_bounds__(256) select_count_kernel(const float* __restri
   const int64_t e1 = e0 + SELECT_CHUNK < N ? e0 + SELECT_CHUNK : N;
   unsigned g = 0, q = 0;
   for (int64_t e = e0 + tid; e < e1; e += 256) {
-    const unsigned key = select_key(row[e]);
+    const unsigned key = order_key(row[e]);
     g += key > kth;
     q += key == kth;
   }
@@ -375,7 +347,7 @@ __global__ void __launch_bounds__(256) select_compact_kernel(const float* __rest
     const int64_t e = e0 + tid;
     bool gt = false, eq = false;
     if (e < c1) {
-      const unsigned key = select_key(row[e]);
+      const unsigned key = order_key(row[e]);
       gt = key > kth_key;
       eq = key == kth_key;
     }

@@ -23,55 +23,9 @@
 #include "mix_slack.h"
 #include "topk_large.h"
 #include "segment_plan.h"
+#include "topk_order.h"
 
 namespace ragraph {
-
-// Wave-cooperative insert into a SORTED k-list (k <= 64) that lives in LDS as [k][QS]: lane p holds entry p, one
-// ballot finds the insert position, one shuffle shifts the tail.  All 64 lanes must call it with wave-uniform
-// (q, s, idx).  Returns the new k-th best score.
-__device__ __forceinline__ float list_insert_coop(float* ls, int* li, int q, int k, int QS, float s, int idx,
-                                                  int lane) {
-  const bool mine = lane < k;
-  float es = mine ? ls[lane * QS + q] : 0.f;
-  int ei = mine ? li[lane * QS + q] : 0;
-  // entries that stay ahead of the candidate: a prefix of the sorted list
-  const unsigned long long ahead = __ballot(mine && cand_better(es, ei, s, idx));
-  const int pos = __popcll(ahead);
-  const float us = __shfl_up(es, 1);
-  const int ui = __shfl_up(ei, 1);
-  if (pos < k) {  // wave-uniform
-    if (lane == pos) {
-      es = s;
-      ei = idx;
-    } else if (lane > pos) {
-      es = us;
-      ei = ui;
-    }
-    if (mine && lane >= pos) {
-      ls[lane * QS + q] = es;
-      li[lane * QS + q] = ei;
-    }
-  }
-  return __shfl(es, k - 1);
-}
-
-// Lane-private insert into the sorted k-list at `ls/li` (this lane's query): shift from the tail.  Used in the DENSE
-// regime (first tiles of a stream, when most lanes hold candidates): 32 queries insert in parallel, ~1k cycles per
-// round of up to 64 candidates, where the cooperative insert would take them one at a time.
-__device__ __forceinline__ void list_insert_lane(float* ls, int* li, int k, int stride, float s, int idx) {
-  if (!cand_better(s, idx, ls[(k - 1) * stride], li[(k - 1) * stride])) return;
-  int p = k - 1;
-  while (p > 0) {
-    const float ps = ls[(p - 1) * stride];
-    const int pi = li[(p - 1) * stride];
-    if (!cand_better(s, idx, ps, pi)) break;
-    ls[p * stride] = ps;
-    li[p * stride] = pi;
-    --p;
-  }
-  ls[p * stride] = s;
-  li[p * stride] = idx;
-}
 
 // Is key `idx` in query row q's exclusion list (ascending, duplicates allowed)?  Binary search in global memory: it is
 // asked only for candidates that already beat the list's k-th score, a few hundred per query over a whole stream.
@@ -384,7 +338,7 @@ __global__ void __launch_bounds__(512, 2) topk_stream_kernel(TopkParams p) {
               my_sc = p.mask_value;
 #pragma unroll 1
             for (int hh = 0; hh < 2; ++hh) {
-              if (mask != 0 && h == hh) list_insert_lane(qls, qli, k, 1, my_sc, idx);
+              if (mask != 0 && h == hh) lds_insert_lane(qls, qli, k, 1, my_sc, idx);
             }
             mask &= mask - 1;
             thr = qls[k - 1];
@@ -404,8 +358,8 @@ __global__ void __launch_bounds__(512, 2) topk_stream_kernel(TopkParams p) {
           const float sc = __shfl(my_sc, src);
           const int idx = __shfl(key_base + (r0 & 3) + 8 * (r0 >> 2), src);
           const int qs = src & 31;
-          const float nthr = list_insert_coop(ls + (wave * 32 + qs) * k, li + (wave * 32 + qs) * k, 0, k, 1, sc, idx,
-                                              lane);
+          const float nthr = lds_insert_coop(ls + (wave * 32 + qs) * k, li + (wave * 32 + qs) * k, 0, k, 1, sc, idx,
+                                             lane);
           if (j == qs) thr = nthr;  // both half-wave lanes of that query
           if (lane == src) mask &= mask - 1;
           // drop remaining candidates the tightened threshold already excludes (only lanes of query qs can change)
@@ -736,7 +690,7 @@ __global__ void __launch_bounds__(512, 2) topk_smallb_kernel(TopkParams p) {
             if (MASKED && mask != 0 && hist_contains(p.hrp, p.hcol, qbase + j, key_base + r0)) my_sc = p.mask_value;
 #pragma unroll 1
             for (int ss = 0; ss < 4; ++ss) {
-              if (mask != 0 && sl == ss) list_insert_lane(ls + j, li + j, k, 16, my_sc, key_base + r0);
+              if (mask != 0 && sl == ss) lds_insert_lane(ls + j, li + j, k, 16, my_sc, key_base + r0);
             }
             mask &= mask - 1;
             if (live) thr = fmaxf(thr_floor, ls[(k - 1) * 16 + j]);
@@ -752,7 +706,7 @@ __global__ void __launch_bounds__(512, 2) topk_smallb_kernel(TopkParams p) {
           const float sc = __shfl(my_sc, src);
           const int idx = __shfl(key_base + r0, src);
           const int q = src & 15;
-          const float nthr = list_insert_coop(ls, li, q, k, 16, sc, idx, lane);
+          const float nthr = lds_insert_coop(ls, li, q, k, 16, sc, idx, lane);
           if (live && j == q) thr = fmaxf(thr_floor, nthr);
           if (lane == src) mask &= mask - 1;
           // drop this lane's remaining candidates that the tightened threshold already excludes

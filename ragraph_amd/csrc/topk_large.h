@@ -9,7 +9,7 @@ size_t large_select_ws_bytes(int64_t B, int64_t n, int64_t k);
 
 // The canonical top-k (score descending, index ascending; NaN never selected) of every row of either a float matrix S
 // [B, ld] (C == nullptr; the index of element e is idx_off + e) or a matrix of packed candidates C [B, ld]
-// ((~select_key << 32) | index, ascending = canonical; ~0 = none).  The result goes either to
+// ((~order_key << 32) | index, ascending = canonical; ~0 = none).  The result goes either to
 //   out_s / out_i [B, k] (out_i != nullptr): scores read from score_src[b * score_ld + index] when score_src is set (the
 //   input's exact bits), decoded from the key otherwise; indices + idx_base; missing entries (-inf, INT64_MAX), or to
 //   cand_out + b * cand_ld [k] as packed candidates, missing entries ~0.

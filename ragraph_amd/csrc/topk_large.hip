@@ -4,7 +4,7 @@
 // flavour (RAGraph_node_fewshot/ragraph_utils/ToyGraphBase.py:16,22,64).
 //
 // One workgroup per (chunk, row); a row of fewer than 65536 elements is one chunk.  Every element is a 32-bit key
-// (select_key: larger float -> larger unsigned, -0 == +0, NaN dropped) and a 32-bit index, packed as the u64
+// (topk_order.h order_key: larger float -> larger unsigned, -0 == +0, NaN dropped) and a 32-bit index, packed as the u64
 // (~key << 32) | index, whose ascending order IS the canonical order.
 //   1. histogram pass: an LDS histogram of the top 11 key bits; a block scan finds the bin that holds the k-th key.
 //      If the keys above that bin plus its members do not fit the LDS buffer (cap >= 2k), the bin is refined by a pass
@@ -19,6 +19,7 @@
 // same kernel until one chunk is left.  Deterministic: no global atomics, the result is a sorted set of unique u64.
 #include "common.h"
 #include "topk_large.h"
+#include "topk_order.h"
 
 namespace ragraph {
 
@@ -26,15 +27,6 @@ constexpr int64_t LARGE_CHUNKED_ROW = 65536;  // rows of at least this many elem
 constexpr int LARGE_MAX_CAP = 8192;           // LDS buffer entries for k = 4096: 64 KiB
 constexpr int LARGE_LDS_EXTRA = 64;           // scalars behind the buffer
 constexpr unsigned long long LARGE_NONE = ~0ull;
-
-__device__ __forceinline__ unsigned large_key(float f) {  // larger float -> larger unsigned; -0 and +0 are one score
-  unsigned b = __float_as_uint(f);
-  if (b == 0x80000000u) b = 0;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float large_unkey(unsigned key) {
-  return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
 
 struct LargeArgs {
   const void* src;  // float [B, ld] or packed u64 [B, ld]
@@ -79,7 +71,7 @@ __device__ __forceinline__ unsigned large_load4(const void* row, int64_t p, int6
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      key[j] = large_key(f[j]);
+      key[j] = order_key(f[j]);
       idx[j] = idx_off + (unsigned)(p + j);
       valid |= (f[j] == f[j]) ? (1u << j) : 0u;
     }
@@ -290,7 +282,7 @@ __global__ void __launch_bounds__(256) topk_large_kernel(LargeArgs a) {
       int64_t i = INT64_MAX;
       if (c != LARGE_NONE) {
         const unsigned ix = (unsigned)c;
-        s = a.score_src ? a.score_src[b * a.score_ld + ix] : large_unkey(~(unsigned)(c >> 32));
+        s = a.score_src ? a.score_src[b * a.score_ld + ix] : order_unkey(~(unsigned)(c >> 32));
         i = (int64_t)ix + a.idx_base;
       }
       a.out_s[b * k + r] = s;

@@ -21,6 +21,7 @@
 // unproven row; it decides no result (the flags say which rows are recomputed, the count only whether any is).
 #include "common.h"
 #include "mix_slack.h"
+#include "topk_order.h"
 
 namespace ragraph {
 

@@ -103,9 +103,6 @@ struct SmallGeo {  // unit geometry of a fragment-order copy whose keys take 2 D
   static constexpr int UNIT_KEYS = 32 * SUBS;
 };
 
-__device__ __forceinline__ unsigned small_f2u(float f) { return (unsigned)f2ord(f) ^ 0x80000000u; }  // order-preserving, > 0
-__device__ __forceinline__ float small_u2f(unsigned u) { return ord2f((int)(u ^ 0x80000000u)); }
-
 template <int D, bool I8>
 struct SmallLds {
   static constexpr int QLD = D + 4;  // floats per query row in LDS (16-B pad: a column of 16 rows spreads over the banks)
@@ -121,11 +118,6 @@ struct SmallLds {
   static constexpr size_t bytes_stream = small + 32 * 4 * 12;
   static constexpr size_t bytes = bytes_stream;
 };
-
-// canonical 64-bit key of a pair (rescore_common.h: wave_select's order)
-__device__ __forceinline__ unsigned long long small_key64(float s, int key) {
-  return ((unsigned long long)select_ord(s) << 32) | (unsigned)~(unsigned)key;
-}
 
 // Canonical top-k of a list held as NPL canonical keys per lane (0 = empty): the k-th largest of the 64 lanes' best keys
 // bounds the k-th best of all from below, the keys at or above it (a few dozen) are compacted into `surv` and ranked by
@@ -166,8 +158,8 @@ __device__ __forceinline__ bool small_select_held(const unsigned long long (&hel
     id2[u] = INT_MAX;
     if (lane + 64 * u < ns) {
       const unsigned long long key = surv[lane + 64 * u];
-      s2[u] = select_unord((unsigned)(key >> 32));
-      id2[u] = (int)~(unsigned)key;
+      s2[u] = pair_score(key);
+      id2[u] = pair_id((unsigned)key);
     }
   }
   __builtin_amdgcn_wave_barrier();
@@ -813,7 +805,7 @@ __global__ void __launch_bounds__(512, 2) topk_small_kernel(SmallParams p) {
 #pragma unroll
       for (int u = 0; u < SMALL_WG_LIST / 64; ++u) {
         const int i = lane + 64 * u;
-        held[u] = (i < n && wg_q[i] == q) ? small_key64(wg_s[i], wg_k[i]) : 0ull;
+        held[u] = (i < n && wg_q[i] == q) ? pair_key_real(wg_s[i], wg_k[i]) : 0ull;
         cq += __popcll(__ballot(held[u] != 0ull));
       }
       if (cq < k) continue;   // (wave-uniform)
@@ -833,7 +825,7 @@ __global__ void __launch_bounds__(512, 2) topk_small_kernel(SmallParams p) {
 #pragma unroll
       for (int u = 0; u < SMALL_WG_LIST / 64; ++u)
         if (held[u] != 0ull && held[u] < bound) wg_q[lane + 64 * u] = -1;   // below this workgroup's own k-th best
-      if (lane == 0) raise_theta(q, select_unord((unsigned)(bound >> 32)));
+      if (lane == 0) raise_theta(q, pair_score(bound));
     }
   };
   {
@@ -1012,7 +1004,7 @@ __global__ void __launch_bounds__(512, 2) topk_small_kernel(SmallParams p) {
       // k = 10: 18 vs 11.6 us for the two queries of a wave)
       unsigned long long held[4];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) held[u] = lane + 64 * u < n ? small_key64(pf_s[c][u], pf_k[c][u]) : 0ull;
+      for (int u = 0; u < 4; ++u) held[u] = lane + 64 * u < n ? pair_key_real(pf_s[c][u], pf_k[c][u]) : 0ull;
       if (small_select_held<4>(held, k, lane, p.idx_base, surv, os, oi, kth_lds + q)) continue;
     } else if (n <= 1024) {  // the list in registers: sixteen pairs per lane, all loads in flight at once
       unsigned long long held[16];
@@ -1021,7 +1013,7 @@ __global__ void __launch_bounds__(512, 2) topk_small_kernel(SmallParams p) {
 #pragma unroll
       for (int u = 0; u < 16; ++u) load_pair(lane + 64 * u, s16[u], id16[u]);
 #pragma unroll
-      for (int u = 0; u < 16; ++u) held[u] = id16[u] == INT_MAX ? 0ull : small_key64(s16[u], id16[u]);
+      for (int u = 0; u < 16; ++u) held[u] = pair_key(s16[u], id16[u]);
       if (small_select_held<16>(held, k, lane, p.idx_base, surv, os, oi, kth_lds + q)) continue;
     }
     // longer lists (and ties by the hundred: a bank of duplicates the collapsing did not see): chunks of 1024 pairs -- sixteen

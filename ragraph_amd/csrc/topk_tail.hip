@@ -25,6 +25,7 @@
 //     local number, as its index is below idx_base_tail, and ascending with r as the seed's canonical order; the lane that
 //     places it turns it back into an int64 index.  No list leaves LDS except the S > 1 partials.
 #include "common.h"
+#include "topk_order.h"
 
 namespace ragraph {
 
@@ -59,48 +60,6 @@ struct TailParams {
   int* tickets = nullptr;          // S > 1: [G], zero at the launch
 };
 
-// The two list inserts of the small-batch kernel (topk_cosine.hip: list_insert_coop / list_insert_lane) on lists laid out [k][16].
-// Cooperative: lane p holds entry p, one ballot finds the position, one shuffle shifts the rest; all 64 lanes call it with
-// wave-uniform (q, s, idx).  Returns the new k-th best score.
-__device__ __forceinline__ float tail_insert_coop(float* ls, int* li, int q, int k, float s, int idx, int lane) {
-  const bool mine = lane < k;
-  float es = mine ? ls[lane * 16 + q] : 0.f;
-  int ei = mine ? li[lane * 16 + q] : 0;
-  const unsigned long long ahead = __ballot(mine && cand_better(es, ei, s, idx));
-  const int pos = __popcll(ahead);
-  const float us = __shfl_up(es, 1);
-  const int ui = __shfl_up(ei, 1);
-  if (pos < k) {  // wave-uniform
-    if (lane == pos) {
-      es = s;
-      ei = idx;
-    } else if (lane > pos) {
-      es = us;
-      ei = ui;
-    }
-    if (mine && lane >= pos) {
-      ls[lane * 16 + q] = es;
-      li[lane * 16 + q] = ei;
-    }
-  }
-  return __shfl(es, k - 1);
-}
-// Lane-private: shift from the end of this lane's query's list (ls / li already offset by the query).
-__device__ __forceinline__ void tail_insert_lane(float* ls, int* li, int k, float s, int idx) {
-  if (!cand_better(s, idx, ls[(k - 1) * 16], li[(k - 1) * 16])) return;
-  int p = k - 1;
-  while (p > 0) {
-    const float ps = ls[(p - 1) * 16];
-    const int pi = li[(p - 1) * 16];
-    if (!cand_better(s, idx, ps, pi)) break;
-    ls[p * 16] = ps;
-    li[p * 16] = pi;
-    --p;
-  }
-  ls[p * 16] = s;
-  li[p * 16] = idx;
-}
-
 // Merge of nlists sorted lists of k entries by RANK: entry `pos` of list a has `pos` entries of its own list in front of it and, in
 // every other list b, the prefix that a binary search finds (canonical order, with the list number as the last word so that
 // identical empty entries (-inf, RG_IDX_NONE) of different lists still order one way).  Its rank is the sum, the ranks are a
@@ -125,6 +84,7 @@ __device__ __forceinline__ void merge_ranked(int nsets, int nlists, int k, int l
         float bs;
         int bi;
         get(set, b, mid, bs, bi);
+        // (the three-word cand_better, written out: calling it here changed the kernel's instructions)
         if (bs > es || (bs == es && (bi < ei || (bi == ei && b < a)))) lo = mid + 1;
         else hi = mid;
       }
@@ -138,9 +98,6 @@ __device__ __forceinline__ void merge_ranked(int nsets, int nlists, int k, int l
 // rank would cost a binary search per entry and list): lane g < nlists holds the head of list g, a round is one wave argmax
 // -- canonical order, the holder's lane as the last word, so that every lane agrees on ONE winner even among identical empty
 // entries --, the winner's lane advances.  Lane r < k returns round r's winner in (rs, ri).
-__device__ __forceinline__ bool head_better(float s1, int i1, int l1, float s2, int i2, int l2) {
-  return (s1 > s2) || (s1 == s2 && (i1 < i2 || (i1 == i2 && l1 < l2)));
-}
 template <typename Next>
 __device__ __forceinline__ void merge_heads(int nlists, int k, int lane, Next next, float& rs, int& ri) {
   float hs = RG_NEG_INF;
@@ -156,7 +113,7 @@ __device__ __forceinline__ void merge_heads(int nlists, int k, int lane, Next ne
       const float os = __shfl_xor(ws, off);
       const int oi = __shfl_xor(wi, off);
       const int ol = __shfl_xor(wl, off);
-      if (head_better(os, oi, ol, ws, wi, wl)) {
+      if (cand_better(os, oi, ol, ws, wi, wl)) {
         ws = os;
         wi = oi;
         wl = ol;
@@ -291,7 +248,7 @@ __global__ void __launch_bounds__(256) topk_tail_kernel(TailParams p) {
             const float my_sc = r0 == 1 ? acc[1] : r0 == 2 ? acc[2] : r0 == 3 ? acc[3] : acc[0];
 #pragma unroll 1
             for (int ss = 0; ss < 4; ++ss) {
-              if (mask != 0 && sl == ss) tail_insert_lane(ls + j, li + j, k, my_sc, key_base + r0);
+              if (mask != 0 && sl == ss) lds_insert_lane(ls + j, li + j, k, 16, my_sc, key_base + r0);
             }
             mask &= mask - 1;
             if (live) thr = fmaxf(thr_floor, ls[(k - 1) * 16 + j]);
@@ -307,7 +264,7 @@ __global__ void __launch_bounds__(256) topk_tail_kernel(TailParams p) {
           const float sc = __shfl(my_sc, src);
           const int idx = __shfl(key_base + r0, src);
           const int q = src & 15;
-          const float nthr = tail_insert_coop(ls, li, q, k, sc, idx, lane);
+          const float nthr = lds_insert_coop(ls, li, q, k, 16, sc, idx, lane);
           if (live && j == q) thr = fmaxf(thr_floor, nthr);
           if (lane == src) mask &= mask - 1;
           RG_TAIL_PRUNE();

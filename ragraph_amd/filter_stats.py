@@ -28,7 +28,7 @@ TAIL_STEPS = (1, 2, 4, 8)   # [29, 32) reserved
 
 
 def ord2f(v: int) -> float:
-    """The float behind an order-preserving int (csrc/filter_common.h f2ord: negative floats have their 31 low bits flipped)."""
+    """The float behind an order-preserving int (csrc/topk_order.h f2ord: negative floats have their 31 low bits flipped)."""
     v = int(v)
     return struct.unpack("<f", struct.pack("<i", v ^ 0x7FFFFFFF if v < 0 else v))[0]
 
