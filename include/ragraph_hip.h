@@ -631,6 +631,22 @@ int ragraph_coo_to_csr_i64(const int64_t* row, const int64_t* col, int64_t E, in
 /* rows[e] = the row of CSR slot e (the inverse of rowptr: torch.repeat_interleave(arange(n), counts) without its prefix sum). */
 int ragraph_csr_row_ids_i64(const int64_t* rowptr, int64_t n, int64_t nnz, int64_t* rows, void* stream);
 
+/* Dense [rows, cols] fp32 (row stride lda >= cols) -> CSR: the form the reference hands every layer (a dense [n, n] adjacency,
+ * RAGraph_node/layers/gcn.py:26-40, built by RAGraph_node/ragraph_utils/utility.py:43-66) and the form of a bag-of-words
+ * feature matrix.  Entry (r, c) is kept iff a[r * lda + c] != 0.0f -- torch.nonzero's rule: -0.0 is dropped; NaN, +-inf and
+ * denormals are kept, with their bits.  Entries are stored row-major, columns ascending inside a row.  Count pass (one wave
+ * per row, ballots), the library's scan, fill pass (the same walk) in one call; no allocation, synchronisation or read-back.
+ *   rowptr int64 [rows + 1]: ALWAYS the true prefix counts;  status int64 [2]: status[0] = the true entry count, status[1] = 1
+ *   iff that count exceeds `capacity`;  col int32 / val fp32 [capacity]: the entries whose slot is below `capacity` -- nothing
+ *   at or behind col[capacity] / val[capacity] is written (a caller that sized them by a guess checks status[1]).
+ *   col == val == NULL with capacity == 0: the count-only form -- rowptr and status, nothing else.
+ * rows >= 0, cols >= 0, rows * cols < 2^31 (a dense fp32 matrix of 2^31 elements is 8 GiB) and rows < 2^31 - 1, else
+ * RAGRAPH_EINVAL; an empty shape gives an all-zero rowptr.  128-bit loads when a is 16-byte aligned and lda % 4 == 0; one
+ * chunk per row for cols <= 64.  ws: ragraph_dense_to_csr_workspace_bytes(rows, cols) (0 for a shape outside the limits). */
+size_t ragraph_dense_to_csr_workspace_bytes(int64_t rows, int64_t cols);
+int ragraph_dense_to_csr_f32(const float* a, int64_t rows, int64_t cols, int64_t lda, int64_t capacity, int64_t* rowptr,
+                             int32_t* col, float* val, int64_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* pos[j] = the position of the j-th non-zero byte of mask (ascending), *count = their number: the boolean indexing of the edge
  * flavour's per-step edge dropout (RAGraph_edge/modules/utils.py:40-53, edges[mask]) on the library's own prefix sums. */
 size_t ragraph_mask_positions_workspace_bytes(int64_t E);

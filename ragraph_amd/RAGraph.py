@@ -241,7 +241,8 @@ class RAGraphGraph(RAGraph):
 
     @staticmethod
     def _mean_rows(x):
-        seg = torch.tensor([0, x.shape[0]], dtype=torch.int64, device=x.device)
+        # ([0, n] made on the device: a host-made tensor would be a copy inside a HIP graph capture)
+        seg = torch.arange(2, dtype=torch.int64, device=x.device) * x.shape[0]
         return K.segment_reduce(x, seg, mean_mode=True)  # [1,D]
 
     def _queries(self, emb, g):

@@ -113,6 +113,8 @@ SIGNATURES = {
     "ragraph_coo_to_csr_workspace_bytes": (_sz, [_i64, _i64]),
     "ragraph_coo_to_csr_i64": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ragraph_csr_row_ids_i64": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    "ragraph_dense_to_csr_workspace_bytes": (_sz, [_i64, _i64]),
+    "ragraph_dense_to_csr_f32": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ragraph_mask_positions_workspace_bytes": (_sz, [_i64]),
     "ragraph_mask_positions_i64": (_i32, [_vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "ragraph_spmm_csr_panels_f32": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _vp, _i32, _vp]),

@@ -10,8 +10,19 @@ rows on the device), so the whole forward can be captured ONCE into a HIP graph 
     out = fwd(new_features)                                       # copy into the static input + one graph launch
 
 The result tensor is the graph's static output buffer (clone it to keep it across calls).  Anything the forward reads
-besides the captured inputs -- the adjacency, the bank, the weights -- is read from the same device addresses at every
-replay: update those tensors in place, and re-capture after a bank grows (add_resources reallocates).
+besides the captured inputs -- a closed-over CSRGraph, the bank, the weights -- is read from the same device addresses at
+every replay: update those tensors in place, and re-capture after a bank grows (add_resources reallocates).
+
+The adjacency may be a captured input too, in the reference's DENSE form:
+
+    fwd = CapturedForward(lambda x, a: model(x, a), features, dense_adj)   # dense_adj fp32 [n, n], n <= K.ROW_BLOCK
+    out = fwd(new_features, new_dense_adj)                                 # same padded size, any pattern
+
+Every replay then converts the adjacency on the device (ragraph_dense_to_csr_f32: count, scan, fill -- no read-back) into
+col / val buffers of n * n slots behind true row pointers (CSRGraph.padded), which the inference kernels walk by the row
+pointers alone.  Graphs of different sizes share one capture when they are padded with zero rows and columns to one n: a
+padded node has no edges, and its output rows are the caller's to ignore.  The conversion costs a few launches per replay
+(profiles/dense_to_csr.txt): a caller whose adjacency never changes still does better closing over a CSRGraph.
 """
 from __future__ import annotations
 

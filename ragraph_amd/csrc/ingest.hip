@@ -470,3 +470,178 @@ extern "C" int ragraph_csr_rows_edges_f32(const int64_t* rowptr, const int32_t* 
   RG_CHECK_LAUNCH("csr_rows_edges");
   return RAGRAPH_OK;
 }
+
+// ---- dense [rows, cols] -> CSR (the reference's adjacency and bag-of-words forms, RAGraph_node/layers/gcn.py:26-40) ------------
+// One wave per row, four rows per workgroup.  The lanes walk the row in chunks: one ballot per chunk position gives every kept
+// entry its rank inside the chunk (v_mbcnt over the lanes below) and the chunk's total (s_bcnt1), which the wave carries as a
+// running offset -- columns ascend inside a row without any sort.  An entry is kept iff its bits are not those of +0 or -0
+// (torch.nonzero's rule: NaN, infinities and denormals stay, whatever the denormal mode of the comparison), and moves as an
+// integer word, so a NaN keeps its payload.  FILL = false: cnt[r] = the row's count (cnt[rows] = 0: the exclusive scan of rows + 1
+// terms ends in the total); FILL = true: the same walk behind excl[r], storing only slots below `capacity`; a row without entries
+// is not read again.  WALK: D2C_ONE (cols <= 64: one chunk, no loop -- PROTEINS-sized graphs), D2C_SCALAR (64 columns per chunk,
+// any alignment), D2C_VEC4 (256 columns per chunk, one 128-bit load per lane: every row starts on 16 bytes).
+namespace ragraph {
+
+enum { D2C_ONE = 0, D2C_SCALAR = 1, D2C_VEC4 = 2 };
+
+__device__ __forceinline__ int lanes_below(unsigned long long m) {   // set bits of m below this lane
+  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
+__device__ __forceinline__ bool d2c_keep(uint32_t bits) { return (bits << 1) != 0u; }
+
+template <bool FILL, int WALK>
+__global__ void __launch_bounds__(256) dense_to_csr_kernel(const uint32_t* __restrict__ a, int64_t rows, int64_t cols, int64_t lda,
+                                                           int* __restrict__ cnt, const int* __restrict__ excl, int64_t capacity,
+                                                           int32_t* __restrict__ col, uint32_t* __restrict__ val) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (!FILL && blockIdx.x == 0 && threadIdx.x == 0) cnt[rows] = 0;
+  if (r >= rows) return;
+  int64_t at = 0;
+  if (FILL) {
+    at = excl[r];
+    if ((int64_t)excl[r + 1] == at || at >= capacity) return;   // (wave-uniform: an empty row, or one wholly behind the capacity)
+  }
+  const uint32_t* __restrict__ row = a + r * lda;
+  int total = 0;
+  auto put = [&](int64_t s, int64_t c, uint32_t bits) {
+    if (s < capacity) {
+      col[s] = (int32_t)c;
+      val[s] = bits;
+    }
+  };
+  if (WALK == D2C_ONE) {
+    const uint32_t v = lane < cols ? row[lane] : 0u;
+    const bool keep = d2c_keep(v);
+    const unsigned long long m = __ballot(keep);
+    if (FILL) {
+      if (keep) put(at + lanes_below(m), lane, v);
+    } else {
+      total = __popcll(m);
+    }
+  } else if (WALK == D2C_SCALAR) {
+    for (int64_t cb = 0; cb < cols; cb += 64) {   // (wave-uniform trip count: a ballot inside)
+      const int64_t c = cb + lane;
+      const uint32_t v = c < cols ? row[c] : 0u;
+      const bool keep = d2c_keep(v);
+      const unsigned long long m = __ballot(keep);
+      if (FILL && keep) put(at + lanes_below(m), c, v);
+      const int n = __popcll(m);
+      at += n;
+      total += n;
+    }
+  } else {
+    auto load4 = [&](int64_t c) {
+      uint4 v = make_uint4(0u, 0u, 0u, 0u);
+      if (c + 3 < cols) {
+        v = *reinterpret_cast<const uint4*>(row + c);
+      } else {                                    // (the one lane that holds the row's end, and the lanes behind it)
+        if (c < cols) v.x = row[c];
+        if (c + 1 < cols) v.y = row[c + 1];
+        if (c + 2 < cols) v.z = row[c + 2];
+      }
+      return v;
+    };
+    auto chunk = [&](int64_t c, const uint4 v) {
+      const bool k0 = d2c_keep(v.x), k1 = d2c_keep(v.y), k2 = d2c_keep(v.z), k3 = d2c_keep(v.w);
+      const unsigned long long m0 = __ballot(k0), m1 = __ballot(k1), m2 = __ballot(k2), m3 = __ballot(k3);
+      if (FILL) {   // a lane's four columns are adjacent: the entries of the lanes below come first, then its own in order
+        int64_t s = at + lanes_below(m0) + lanes_below(m1) + lanes_below(m2) + lanes_below(m3);
+        if (k0) put(s, c, v.x);
+        s += k0;
+        if (k1) put(s, c + 1, v.y);
+        s += k1;
+        if (k2) put(s, c + 2, v.z);
+        s += k2;
+        if (k3) put(s, c + 3, v.w);
+      }
+      const int n = __popcll(m0) + __popcll(m1) + __popcll(m2) + __popcll(m3);
+      at += n;
+      total += n;
+    };
+    // two chunks per trip, both loads in flight before the first ballot (a chunk wholly behind the row's end is all zeros)
+    for (int64_t cb = 0; cb < cols; cb += 512) {
+      const int64_t c0 = cb + 4 * lane, c1 = c0 + 256;
+      const uint4 v0 = load4(c0), v1 = load4(c1);
+      chunk(c0, v0);
+      chunk(c1, v1);
+    }
+  }
+  if (!FILL && lane == 0) cnt[r] = total;
+}
+
+// int32 prefix sums -> rowptr int64 [rows + 1]; status[0] = the total, status[1] = 1 iff it exceeds the capacity
+__global__ void __launch_bounds__(256) dense_rowptr_kernel(const int* __restrict__ excl, int64_t rows, int64_t capacity,
+                                                           int64_t* __restrict__ rowptr, int64_t* __restrict__ status) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k > rows) return;
+  const int64_t v = (int64_t)excl[k];
+  rowptr[k] = v;
+  if (k == rows) {
+    status[0] = v;
+    status[1] = v > capacity ? 1 : 0;
+  }
+}
+
+template <bool FILL>
+static void dense_to_csr_launch(int walk, unsigned blocks, hipStream_t st, const uint32_t* a, int64_t rows, int64_t cols,
+                                int64_t lda, int* cnt, int64_t capacity, int32_t* col, uint32_t* val) {
+  const int* excl = FILL ? cnt : nullptr;
+  int* out = FILL ? nullptr : cnt;
+  if (walk == D2C_ONE)
+    hipLaunchKernelGGL((dense_to_csr_kernel<FILL, D2C_ONE>), dim3(blocks), dim3(256), 0, st, a, rows, cols, lda, out, excl, capacity,
+                       col, val);
+  else if (walk == D2C_SCALAR)
+    hipLaunchKernelGGL((dense_to_csr_kernel<FILL, D2C_SCALAR>), dim3(blocks), dim3(256), 0, st, a, rows, cols, lda, out, excl,
+                       capacity, col, val);
+  else
+    hipLaunchKernelGGL((dense_to_csr_kernel<FILL, D2C_VEC4>), dim3(blocks), dim3(256), 0, st, a, rows, cols, lda, out, excl,
+                       capacity, col, val);
+}
+
+}  // namespace ragraph
+
+extern "C" size_t ragraph_dense_to_csr_workspace_bytes(int64_t rows, int64_t cols) {
+  if (rows < 0 || cols < 0 || rows >= (int64_t)INT_MAX || (cols > 0 && rows > ((int64_t)INT_MAX) / cols)) return 0;
+  return align_up((size_t)(rows + 1) * sizeof(int), 256) + scan_temp_bytes(rows + 1);
+}
+
+extern "C" int ragraph_dense_to_csr_f32(const float* a, int64_t rows, int64_t cols, int64_t lda, int64_t capacity, int64_t* rowptr,
+                                        int32_t* col, float* val, int64_t* status, void* ws, size_t ws_bytes, void* stream) {
+  RG_REQUIRE(rows >= 0 && cols >= 0 && rows < (int64_t)INT_MAX, RAGRAPH_EINVAL, "dense_to_csr: bad shape (%lld x %lld)",
+             (long long)rows, (long long)cols);
+  RG_REQUIRE(cols == 0 || rows <= ((int64_t)INT_MAX) / cols, RAGRAPH_EINVAL,
+             "dense_to_csr: %lld x %lld entries (rows * cols must be below 2^31)", (long long)rows, (long long)cols);
+  RG_REQUIRE(lda >= cols, RAGRAPH_EINVAL, "dense_to_csr: lda=%lld < cols=%lld", (long long)lda, (long long)cols);
+  RG_REQUIRE(capacity >= 0, RAGRAPH_EINVAL, "dense_to_csr: capacity=%lld", (long long)capacity);
+  RG_REQUIRE(rowptr && status && ws && (a || rows == 0 || cols == 0), RAGRAPH_EINVAL, "dense_to_csr: null pointer");
+  RG_REQUIRE((col == nullptr) == (val == nullptr), RAGRAPH_EINVAL, "dense_to_csr: col and val go together");
+  RG_REQUIRE(col || capacity == 0, RAGRAPH_EINVAL, "dense_to_csr: capacity=%lld without col / val", (long long)capacity);
+  RG_REQUIRE(ws_bytes >= ragraph_dense_to_csr_workspace_bytes(rows, cols), RAGRAPH_EWORKSPACE,
+             "dense_to_csr: workspace too small");
+  hipStream_t st = as_stream(stream);
+  if (rows == 0 || cols == 0) {
+    hipLaunchKernelGGL(fill_i64_kernel, dim3((unsigned)cdiv(rows + 1, 256)), dim3(256), 0, st, rowptr, rows + 1, (int64_t)0);
+    hipLaunchKernelGGL(fill_i64_kernel, dim3(1), dim3(256), 0, st, status, (int64_t)2, (int64_t)0);
+    RG_CHECK_LAUNCH("dense_to_csr(empty)");
+    return RAGRAPH_OK;
+  }
+  int* cnt = static_cast<int*>(ws);
+  const size_t cnt_bytes = align_up((size_t)(rows + 1) * sizeof(int), 256);
+  const uint32_t* bits = reinterpret_cast<const uint32_t*>(a);
+  const int walk = cols <= 64 ? D2C_ONE : (aligned16(a) && lda % 4 == 0) ? D2C_VEC4 : D2C_SCALAR;
+  const unsigned row_blocks = (unsigned)cdiv(rows, 4);
+  dense_to_csr_launch<false>(walk, row_blocks, st, bits, rows, cols, lda, cnt, capacity, nullptr, nullptr);
+  RG_CHECK_LAUNCH("dense_to_csr(count)");
+  const int rc = scan_sum_i32(cnt, cnt, rows + 1, false, static_cast<char*>(ws) + cnt_bytes, ws_bytes - cnt_bytes, st);
+  if (rc != RAGRAPH_OK) return rc;
+  hipLaunchKernelGGL(dense_rowptr_kernel, dim3((unsigned)cdiv(rows + 1, 256)), dim3(256), 0, st, (const int*)cnt, rows, capacity,
+                     rowptr, status);
+  RG_CHECK_LAUNCH("dense_to_csr(rowptr)");
+  if (capacity > 0) {
+    dense_to_csr_launch<true>(walk, row_blocks, st, bits, rows, cols, lda, cnt, capacity, col, reinterpret_cast<uint32_t*>(val));
+    RG_CHECK_LAUNCH("dense_to_csr(fill)");
+  }
+  return RAGRAPH_OK;
+}

@@ -35,12 +35,13 @@ def averageemb(labels, rawret, nb_class):
     """Class-mean prototypes.  The reference (downprompt.py:59-94) averages over an UNINITIALISED [C, n, D] buffer, so
     its result is garbage-dependent; this is the evident intent: mean of the rows of each class."""
     lab = labels.reshape(-1).long().to(rawret.device)
-    order = torch.sort(lab, stable=True).indices
-    counts = torch.bincount(lab, minlength=nb_class)
-    seg = torch.zeros(nb_class + 1, dtype=torch.int64, device=rawret.device)
-    seg[1:] = torch.cumsum(counts, 0)
-    out = K.segment_reduce(K.gather_rows(rawret, order), seg, mean_mode=True)    # any D
-    out[counts == 0] = 0                                                          # (0 / 0 of an empty class)
+    C = int(nb_class)
+    # the row order and the class pointer from ONE stable COO -> CSR sort of the library's (as fewshot_mean_logits); a label
+    # outside [0, C) goes to slot C, which nobody reads
+    lab = torch.where((lab >= 0) & (lab < C), lab, torch.full_like(lab, C))
+    seg, _, order = K.coo_to_csr(lab, torch.arange(lab.numel(), dtype=torch.int64, device=lab.device), C + 1)
+    out = K.segment_reduce(K.gather_rows(rawret, order), seg, mean_mode=True)[:C]   # any D
+    out[(seg[1:C + 1] - seg[:C]) == 0] = 0                                        # (0 / 0 of an empty class)
     return out
 
 

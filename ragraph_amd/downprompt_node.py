@@ -78,17 +78,16 @@ def averageemb(labels, rawret):
     n = rawret.shape[0]
     half = int(n / 2)
     lab = labels.reshape(-1).long().to(rawret.device)
-    keep = (lab >= 0) & (lab < NB_CLASSES)             # rows of other labels are skipped (the three `if`s)
-    lab_k = lab[keep]
-    counts = torch.bincount(lab_k, minlength=NB_CLASSES)
-    if half == 0 or int(counts.max()) > half:
-        raise IndexError(f"averageemb: a class has {int(counts.max())} rows but the reference's buffer holds "
+    # rows of other labels are skipped (the three `if`s): they go to slot NB_CLASSES, which nobody reads.  The row order and
+    # the class pointer come from ONE stable COO -> CSR sort of the library's (as fewshot_mean_logits)
+    lab = torch.where((lab >= 0) & (lab < NB_CLASSES), lab, torch.full_like(lab, NB_CLASSES))
+    seg, _, order = K.coo_to_csr(lab, torch.arange(n, dtype=torch.int64, device=lab.device), NB_CLASSES + 1)
+    most = int((seg[1:NB_CLASSES + 1] - seg[:NB_CLASSES]).max())                  # (the one read-back: the reference's rule)
+    if half == 0 or most > half:
+        raise IndexError(f"averageemb: a class has {most} rows but the reference's buffer holds "
                          f"int({n}/2) = {half} per class (RAGraph_node/downprompt.py:61)")
-    order = torch.nonzero(keep).reshape(-1)[torch.sort(lab_k, stable=True).indices]
-    seg = torch.zeros(NB_CLASSES + 1, dtype=torch.int64, device=rawret.device)
-    seg[1:] = torch.cumsum(counts, 0)
     # (differentiable: a training step keeps the prototypes in the graph of its own embeddings, downprompt.py:24-25)
-    sums = AG.segment_sum(AG.gather_rows(rawret, order), seg)                     # rows added in index order
+    sums = AG.segment_sum(AG.gather_rows(rawret, order), seg)[:NB_CLASSES]        # rows added in index order
     return AG.mul_cols(sums, torch.full((rawret.shape[1],), 1.0 / half, device=rawret.device))
 
 

@@ -5,9 +5,10 @@ layers/gcn.py:36, Propagation.py:15-22): 40 GB per copy at n = 1e5.  The kernels
 fp32 val); `as_csr` accepts what reference callers pass (a dense tensor) or a CSRGraph, and converts once.
 
 Structure conversion: COO -> CSR (from_coo, transposed, permuted) runs on the library's own stable radix sort
-(ragraph_coo_to_csr_i64) -- the edge flavour rebuilds its graph on every training step; only from_dense (the reference's
-dense [n, n] input, converted once per graph) still enumerates the non-zeros with torch.nonzero.  Every floating-point
-result comes from libragraph_hip.so.
+(ragraph_coo_to_csr_i64) -- the edge flavour rebuilds its graph on every training step; from_dense (the reference's
+dense [n, n] input) runs on the library's own dense -> CSR kernels (ragraph_dense_to_csr_f32), without any read-back when it
+is given a capacity -- so a captured forward may take its adjacency as an input.  Every floating-point result comes from
+libragraph_hip.so.
 """
 from __future__ import annotations
 
@@ -38,6 +39,17 @@ class CSRGraph:
     _has_long_rows: bool | None = field(default=None, repr=False)
     _transposed: "CSRGraph | None" = field(default=None, repr=False)
     _tile_plans: dict = field(default_factory=dict, repr=False)
+    # padded: col / val hold MORE slots than rowptr[n] entries (from_dense with a capacity: sized without a read-back, as
+    # under HIP graph capture).  The slots behind rowptr[n] are never written and never read by a kernel that walks the
+    # row pointers; what enumerates slots instead (row_ids, transposed, permuted, tile_plan, tiled_values) raises.
+    padded: bool = False
+    status: torch.Tensor | None = field(default=None, repr=False)   # padded: int64 [2] on the device, (entries, overflowed?)
+
+    def _no_padding(self, who: str):
+        if self.padded:
+            raise K.RagraphNativeError(f"CSRGraph.{who}: a padded graph is inference-only (its col / val hold unwritten "
+                                       "slots behind rowptr[n]: convert the adjacency without a capacity, outside a "
+                                       "capture, to train through it or to reorder it)")
 
     @property
     def shape(self):
@@ -75,6 +87,7 @@ class CSRGraph:
     def transposed(self) -> "CSRGraph":
         """CSR of A^T (row j lists the i with A[i][j] != 0, ascending i), cached: what a backward pass through the SpMM
         multiplies by, and what PageRank pulls along."""
+        self._no_padding("transposed")
         if self._transposed is None:
             # (the edges are row-major already: a STABLE sort by column alone leaves every transposed row ascending)
             self._transposed, _ = CSRGraph.from_coo(self.col, self.row_ids(), self.val, self.n)
@@ -82,6 +95,7 @@ class CSRGraph:
 
     def row_ids(self) -> torch.Tensor:
         """rows[e] = the row of CSR slot e (int64)."""
+        self._no_padding("row_ids")
         if self.rowptr.is_cuda:
             return K.csr_row_ids(self.rowptr, self.nnz)
         return torch.repeat_interleave(torch.arange(self.n, device=self.device), self.rowptr[1:] - self.rowptr[:-1])
@@ -99,6 +113,7 @@ class CSRGraph:
         Destination rows: C chunks of RC = 128 RG rows (RG <= 9: the chunk's 32-column sums fill a workgroup's LDS), as few
         passes over the chunks as that allows; source rows: S blocks of at most TILE_SOURCE_BYTES of 128-byte lines; edges:
         one stable sort (the library's own) by (chunk, 8-lane group, source block) -- inside a bucket the CSR order stays."""
+        self._no_padding("tile_plan")
         share = 1 if panels >= 8 else 8 // max(panels, 1)
         if share in self._tile_plans:
             return self._tile_plans[share]
@@ -150,6 +165,7 @@ class CSRGraph:
 
     def tiled_values(self, plan, val: torch.Tensor) -> torch.Tensor:
         """The edge values in the plan's slots (0 in the NULL slots), cached per value tensor and version."""
+        self._no_padding("tiled_values")
         tag = (val.data_ptr(), val._version, val.numel())
         if plan._val_tag != tag:
             v3 = torch.zeros(plan.slots, dtype=torch.float32, device=val.device)
@@ -164,6 +180,7 @@ class CSRGraph:
         community-aware order (locality_order) turns Infinity-Cache gathers into L2 hits.  A row's terms are then summed
         in the NEW column order: the result equals the unpermuted one up to fp32 summation order (not bit for bit),
         which is why no forward applies this by itself -- the caller opts in, permutes X once and inverts at the end."""
+        self._no_padding("permuted")
         order = order.to(self.device, torch.int64)
         inv = torch.empty_like(order)
         inv[order] = torch.arange(self.n, device=self.device)
@@ -173,6 +190,7 @@ class CSRGraph:
     def locality_order(self) -> torch.Tensor:
         """Reverse Cuthill-McKee order of the (symmetrised) pattern -- structure-only bookkeeping, once per graph, on the
         host (scipy.sparse.csgraph): order[i] = the node that should be stored i-th."""
+        self._no_padding("locality_order")
         import numpy as np
         import scipy.sparse as sp
         from scipy.sparse.csgraph import reverse_cuthill_mckee
@@ -182,10 +200,37 @@ class CSRGraph:
 
     # ---- constructors ------------------------------------------------------------------------------------------
     @staticmethod
-    def from_dense(adj: torch.Tensor) -> "CSRGraph":
-        """Non-zeros of a dense [n,n] (or [1,n,n]) adjacency, rows ascending, columns ascending within a row."""
+    def from_dense(adj: torch.Tensor, capacity: int | None = None) -> "CSRGraph":
+        """Non-zeros of a dense [n,n] (or [1,n,n]) adjacency, rows ascending, columns ascending within a row.
+        A device fp32 tensor goes through the library (K.dense_to_csr: one 8-byte read-back of the entry count).
+        `capacity` (device tensors): col / val of that many slots and NO read-back -- the graph is `padded`, its `status`
+        tensor holds (true entry count, overflowed?) for the caller to check.  Under HIP graph capture the capacity is
+        n * n (it cannot overflow) and n must not exceed K.ROW_BLOCK (the long-row decision would need a read-back)."""
         a = adj.squeeze(0) if adj.dim() == 3 else adj
         n = a.shape[0]
+        if a.is_cuda and a.dtype == torch.float32 and a.dim() == 2:
+            short = a.shape[1] <= K.ROW_BLOCK      # no row of a matrix this narrow is a long one: no read-back to find out
+            if torch.cuda.is_current_stream_capturing():
+                if n > K.ROW_BLOCK or not short:
+                    raise K.RagraphNativeError(f"CSRGraph.from_dense: a dense adjacency is converted under HIP graph capture "
+                                               f"for n <= {K.ROW_BLOCK} only (n = {n}: whether a row is longer than "
+                                               f"{K.ROW_BLOCK} edges would be read back); convert it before the capture")
+                if torch.is_grad_enabled():
+                    raise K.RagraphNativeError("CSRGraph.from_dense: a dense adjacency converted under HIP graph capture is a "
+                                               "padded graph, and a padded graph is inference-only: capture the forward under "
+                                               "torch.no_grad() (CapturedForward does), or convert the adjacency before the "
+                                               "capture -- a captured training step closes over a CSRGraph")
+                if capacity is None:
+                    capacity = n * a.shape[1]
+            long_rows = False if short else None
+            if capacity is None:
+                rowptr, col, val = K.dense_to_csr(a)
+                return CSRGraph(rowptr, col, val, n, _has_long_rows=long_rows)
+            rowptr, col, val, status = K.dense_to_csr(a, int(capacity))
+            return CSRGraph(rowptr, col, val, n, _has_long_rows=long_rows, padded=True, status=status)
+        if capacity is not None:
+            raise ValueError("CSRGraph.from_dense: `capacity` is for fp32 device tensors")
+        # host tensors (the CPU host-logic tests) and other dtypes: the same construction with torch ops
         nz = torch.nonzero(a, as_tuple=False)  # row-major order
         rows, cols = nz[:, 0], nz[:, 1]
         rowptr = torch.zeros(n + 1, dtype=torch.int64, device=a.device)

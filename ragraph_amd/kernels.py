@@ -1628,6 +1628,65 @@ def coo_to_csr(rows: torch.Tensor, cols: torch.Tensor, n: int, sort_cols: bool =
     return rowptr, col, perm
 
 
+def dense_to_csr(a: torch.Tensor, capacity: int | None = None, max_entries: int | None = None):
+    """Dense fp32 [rows, cols] (or a [1, rows, cols] view; unit column stride, any row stride) -> CSR of the entries that
+    compare unequal to 0 (ragraph_dense_to_csr_f32: torch.nonzero's rule and order -- row-major, columns ascending; the
+    values keep their bits).
+    capacity=None: the eager form -- a count-only call, ONE 8-byte read-back of the entry count, exact-size buffers, the
+    fill.  Returns (rowptr int64 [rows+1], col int32 [nnz], val fp32 [nnz]); with `max_entries`, None -- and no fill -- when
+    the matrix holds more entries than that (a density test costs the count pass alone).
+    capacity=int: no read-back at all (capturable).  Returns (rowptr, col [capacity], val [capacity], status int64 [2] on
+    the device): rowptr holds the true prefix counts whatever the capacity, status[0] the true entry count, status[1] = 1
+    iff it exceeds `capacity` (the entries behind the capacity are then missing: the caller owns that check).  The slots
+    of col / val behind rowptr[rows] are never written."""
+    L = _ready()
+    if not isinstance(a, torch.Tensor) or not a.is_cuda:
+        raise RagraphNativeError("dense_to_csr.a: expected a ROCm device tensor (ragraph_amd has no CPU fallback)")
+    if a.dtype != torch.float32:
+        raise RagraphNativeError(f"dense_to_csr.a: expected float32, got {a.dtype}")
+    if a.dim() == 3 and a.shape[0] == 1:
+        a = a[0]
+    if a.dim() != 2:
+        raise RagraphNativeError(f"dense_to_csr.a: expected [rows, cols] or [1, rows, cols], got {tuple(a.shape)}")
+    rows, cols = a.shape
+    if (cols > 1 and a.stride(1) != 1) or (rows > 1 and a.stride(0) < cols):   # (a transposed or expanded view: one copy)
+        a = a.contiguous()
+    lda = a.stride(0) if rows > 1 else cols
+    dev = a.device
+    nbytes = L.ragraph_dense_to_csr_workspace_bytes(rows, cols)
+    if nbytes == 0:
+        raise RagraphNativeError(f"dense_to_csr: {rows} x {cols} not supported (rows * cols must be below 2^31)")
+    # (the row counts and the scan's scratch: 4 (rows + 1) bytes and a little of this call's own, exactly sized -- not the
+    # shared grow-only scratch)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    rowptr = torch.empty(rows + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(2, dtype=torch.int64, device=dev)
+    ap = a.data_ptr() if rows and cols else None
+
+    def call(cap, col, val):
+        N.check(L.ragraph_dense_to_csr_f32(ap, rows, cols, lda, cap, rowptr.data_ptr(), _ptr(col), _ptr(val),
+                                           status.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "dense_to_csr")
+
+    if capacity is not None:
+        cap = int(capacity)
+        if cap < 0:
+            raise RagraphNativeError(f"dense_to_csr: capacity={cap}")
+        # (at least one slot is allocated, so that the pointers are valid; the library is told the caller's capacity)
+        col = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)[:cap]
+        val = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)[:cap]
+        call(cap, col if cap else None, val if cap else None)
+        return rowptr, col, val, status
+    call(0, None, None)
+    nnz = int(status[0])                    # the one read-back (torch.nonzero has its own)
+    if max_entries is not None and nnz > max_entries:
+        return None
+    col = torch.empty(nnz, dtype=torch.int32, device=dev)
+    val = torch.empty(nnz, dtype=torch.float32, device=dev)
+    if nnz:
+        call(nnz, col, val)
+    return rowptr, col, val
+
+
 def csr_row_ids(rowptr: torch.Tensor, nnz: int) -> torch.Tensor:
     """rows[e] = the row of CSR slot e (ragraph_csr_row_ids_i64)."""
     L = _ready()

@@ -39,10 +39,14 @@ def sparse_features(x: torch.Tensor, probe: bool = True):
         return ent[2]
     if not probe or torch.cuda.is_current_stream_capturing():
         return None
-    csr = None
-    if int(torch.count_nonzero(x)) <= SPARSE_FEATURES_MAX_DENSITY * x.numel():
-        xs = x.detach().to_sparse_csr()
-        csr = (xs.crow_indices().contiguous(), xs.col_indices().to(torch.int32).contiguous(), xs.values().contiguous())
+    if x.dtype == torch.float32:
+        # the library's dense -> CSR: the count pass, one read-back of the entry count, the fill only for a sparse enough matrix
+        csr = K.dense_to_csr(x.detach(), max_entries=int(SPARSE_FEATURES_MAX_DENSITY * x.numel()))
+    else:
+        csr = None
+        if int(torch.count_nonzero(x)) <= SPARSE_FEATURES_MAX_DENSITY * x.numel():
+            xs = x.detach().to_sparse_csr()
+            csr = (xs.crow_indices().contiguous(), xs.col_indices().to(torch.int32).contiguous(), xs.values().contiguous())
     if len(_feature_csr) > 64:  # (entries of tensors that are gone)
         for key in [k_ for k_, v_ in _feature_csr.items() if v_[0]() is None]:
             del _feature_csr[key]

@@ -17,7 +17,7 @@ class Propagation:
             return x if rows is None else x[rows[0]:rows[1]].contiguous()
         valn = g.row_normalized_values()
         if (not (torch.is_grad_enabled() and x.requires_grad) and x.is_cuda and x.shape[1] % 32 == 0
-                and K.tiles_help(x.shape[0], x.shape[1])):
+                and K.tiles_help(x.shape[0], x.shape[1]) and not g.padded):   # (a plan enumerates slots: not of a padded graph)
             # large graphs, round 6: the GRAPH is tiled (once; CSRGraph.tile_plan) so that what an XCD gathers from at any
             # moment fits its L2 -- and the features stay panel-major between the hops as below; same bits.  The last hop of a
             # rank's row slice takes the panel kernel over that slice of the row pointers.
