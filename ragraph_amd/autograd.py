@@ -18,6 +18,14 @@ import torch
 from . import kernels as K
 
 
+def _aligned(g):
+    """An incoming gradient as the SpMM entry points take it: contiguous and on a 16-byte boundary.  Autograd hands a
+    backward whatever view its consumer made -- torch.cat behind an odd-sized piece gives a contiguous view 4 bytes off --
+    and those kernels read float4 rows (they refuse another address): such a view is copied once."""
+    g = g.contiguous()
+    return g if g.data_ptr() % 16 == 0 else g.clone()
+
+
 class _Linear(torch.autograd.Function):
     """y = act(x @ W^T + b), act in {none, leaky(alpha)}.  The fused epilogue keeps only y, from which backward reads the
     pre-activation's sign while the slope is positive (y > 0 exactly when z > 0).  For a leaky-family slope <= 0 the output
@@ -145,7 +153,7 @@ class _SpmmCsr(torch.autograd.Function):
             z, alpha_t = ctx.saved_tensors
         else:
             (y,) = ctx.saved_tensors      # (z itself when keeps_z: act_grad's sign test is then on the pre-activation)
-        gy = gy.contiguous()
+        gy = _aligned(gy)
         galpha = None
         if ctx.act != K.ACT_NONE:
             want_alpha = ctx.has_alpha and ctx.needs_input_grad[4]
@@ -207,7 +215,7 @@ class _SpmmCsrRows(torch.autograd.Function):
         g = ctx.g
         c, r, v = K.csr_rows_edges(g.rowptr, g.col, g.val, rows)
         rowptr_t, col_t, perm = K.coo_to_csr(c, r, ctx.n_cols)
-        gy = gy.contiguous().reshape(rows.numel(), -1)
+        gy = _aligned(gy).reshape(rows.numel(), -1)
         # (a column may sit in more than ROW_BLOCK requested rows only when that many were requested; the flag costs three
         # launches and changes no bit)
         gx = K.spmm_csr(rowptr_t, col_t, v[perm].contiguous(), gy, long_rows=rows.numel() > K.ROW_BLOCK)
@@ -244,7 +252,9 @@ def sigmoid_gate(x, z):
 class _GatherRows(torch.autograd.Function):
     """v[idx] for a 1-D index -- batch_user_emb = user_emb[users] (modules/RAGraph.py:343-345).  Backward scatters the
     row gradients back: rows hit several times are summed by a CSR SpMM (rows = bank rows, one unit entry per hit),
-    deterministic -- no atomics."""
+    deterministic -- no atomics.  The SpMM takes widths in 4Z only, the gather any D >= 1: the gradient's columns are padded
+    with zeros to the next multiple of 4 and the result cut back (a column's sum does not see its neighbours: for D in 4Z
+    nothing is copied and no bit moves).  An empty index gives a zero gradient."""
 
     @staticmethod
     def forward(ctx, v, idx):
@@ -256,10 +266,19 @@ class _GatherRows(torch.autograd.Function):
     def backward(ctx, g):
         (idx,) = ctx.saved_tensors
         from .graph import CSRGraph
-        m = idx.numel()
+        m, D = idx.numel(), g.shape[-1]
+        if m == 0:
+            return torch.zeros((ctx.n, D), dtype=torch.float32, device=g.device), None
+        g = g.contiguous().reshape(m, D)
+        Dp = (D + 3) // 4 * 4
+        if Dp != D:
+            gp = torch.zeros((m, Dp), dtype=torch.float32, device=g.device)
+            gp[:, :D] = g
+            g = gp
         hits, _ = CSRGraph.from_coo(idx.reshape(-1), torch.arange(m, device=idx.device), torch.ones(m, device=idx.device), ctx.n)
         hits.n_cols = m
-        return K.spmm_csr(hits.rowptr, hits.col, hits.val, g.contiguous().reshape(m, -1)), None
+        gv = K.spmm_csr(hits.rowptr, hits.col, hits.val, _aligned(g))
+        return (gv if Dp == D else gv[:, :D].contiguous()), None
 
 
 def gather_rows(v, idx):

@@ -846,6 +846,8 @@ def gather_rows(v: torch.Tensor, idx: torch.Tensor, idx_base: int = 0) -> torch.
     v = _f32c(v, "gather_rows.v")
     idx = _idxc(idx, "gather_rows.idx")
     out = torch.empty(tuple(idx.shape) + (v.shape[1],), dtype=torch.float32, device=v.device)
+    if idx.numel() == 0:      # (an empty tensor has no address to hand over)
+        return out
     N.check(L.ragraph_gather_rows_f32(v.data_ptr(), v.shape[0], v.shape[1], idx.data_ptr(), idx.numel(), idx_base,
                                       out.data_ptr(), _stream()), "gather_rows")
     return out
