@@ -1425,6 +1425,8 @@ def floyd_warshall(adj_dense: torch.Tensor) -> torch.Tensor:
     """All-pairs shortest paths with the adjacency VALUES as edge lengths -- PositionAwareEncoder.py:27-48."""
     L = _ready()
     a = _f32c(adj_dense, "floyd_warshall.adj")
+    if a.dim() != 2 or a.shape[0] != a.shape[1]:
+        raise RagraphNativeError(f"floyd_warshall: adj must be a square [n, n] matrix, got {tuple(a.shape)}")
     n = a.shape[0]
     d = torch.empty_like(a)
     N.check(L.ragraph_floyd_warshall_f32(a.data_ptr(), n, d.data_ptr(), _stream()), "floyd_warshall")
@@ -1436,6 +1438,10 @@ def position_code(dist: torch.Tensor, anchors: torch.Tensor, dis_q: float = 10.0
     L = _ready()
     d = _f32c(dist, "position_code.dist")
     anchors = _idxc(anchors, "position_code.anchors")
+    if d.dim() != 2 or d.shape[0] != d.shape[1]:
+        raise RagraphNativeError(f"position_code: dist must be a square [n, n] matrix, got {tuple(d.shape)}")
+    if anchors.dim() != 1 or anchors.numel() == 0:
+        raise RagraphNativeError(f"position_code: anchors must be a non-empty [A] vector, got {tuple(anchors.shape)}")
     out = torch.empty((d.shape[0], anchors.numel()), dtype=torch.float32, device=d.device)
     N.check(L.ragraph_position_code_f32(d.data_ptr(), d.shape[0], anchors.data_ptr(), anchors.numel(), float(dis_q),
                                         out.data_ptr(), _stream()), "position_code")
@@ -1550,6 +1556,8 @@ def pagerank(rowptr_t: torch.Tensor, col_t: torch.Tensor, val_t: torch.Tensor, o
     out_deg = _f32c(out_deg, "pagerank.out_deg")
     graph_ptr = _idxc(graph_ptr, "pagerank.graph_ptr")
     n, G = out_deg.numel(), graph_ptr.numel() - 1
+    if rowptr_t.numel() - 1 != n:
+        raise RagraphNativeError(f"pagerank: out_deg has {n} entries, rowptr_t describes {rowptr_t.numel() - 1} rows")
     sizes = graph_ptr[1:] - graph_ptr[:-1]
     graph_of = torch.repeat_interleave(torch.arange(G, device=out_deg.device, dtype=torch.int32), sizes)
     p = torch.empty(n, dtype=torch.float32, device=out_deg.device)
@@ -1580,6 +1588,11 @@ def position_codes_batch(adj: torch.Tensor, anchors: torch.Tensor, dis_q: float 
     L = _ready()
     a = _f32c(adj, "position_codes_batch.adj")
     anchors = _idxc(anchors, "position_codes_batch.anchors")
+    if a.dim() != 3 or a.shape[1] != a.shape[2]:
+        raise RagraphNativeError(f"position_codes_batch: adj must be [G, n, n], got {tuple(a.shape)}")
+    if anchors.dim() != 2 or anchors.shape[0] != a.shape[0]:
+        raise RagraphNativeError(f"position_codes_batch: anchors must be [G, A] with G = {a.shape[0]}, got "
+                                 f"{tuple(anchors.shape)}")
     G, n, _ = a.shape
     A = anchors.shape[1]
     codes = torch.empty((G, n, A), dtype=torch.float32, device=a.device)
