@@ -87,7 +87,7 @@ int ragraph_normalize_rows_f32(const float* X, int64_t n, int D, float* out, voi
  *   (torch.topk would rank NaN first) -- inputs are finite by contract.
  */
 #define RAGRAPH_TOPK_MAX 64
-/* the longest list a FILTERED call returns (ragraph_topk_cosine_filtered_wide128_f32); RAGRAPH_TOPK_MAX is the fused fp32 kernels' */
+/* the longest list a FILTERED call returns (ragraph_topk_cosine_filtered_f32); RAGRAPH_TOPK_MAX is the fused fp32 kernels' */
 #define RAGRAPH_TOPK_FILTER_MAX 128
 size_t ragraph_topk_cosine_workspace_bytes(int64_t B, int64_t N, int D, int k);
 int ragraph_topk_cosine_f32(const float* Q, int64_t B, const float* Kn, int64_t N, int D, int k, int64_t idx_base,
@@ -175,7 +175,20 @@ int ragraph_topk_rows_scatter_f32(const float* scores, const int64_t* idx, const
  *   rescored with the natural-order fp32 fmaf chain and selected in canonical order, which gives the exact top-k of
  *   everything seen so far and a tighter bound for the next level (large batches: [0,N/32), [N/32,N/4), [N/4,N); small
  *   ones: fewer, steeper levels -- ragraph_topk_cosine_filtered_plan).  The result has the same bits as
- *   ragraph_topk_cosine_f32.  D in {64,128,256}, k <= 32; lists of 33 .. 64 keys: the _wide entries below, 65 .. 128: _wide128.
+ *   ragraph_topk_cosine_f32 (beyond its k = 64: those of ragraph_topk_cosine_bank_f32, canonical order).
+ *   D in {64,128,256}, 1 <= k <= min(N, RAGRAPH_TOPK_FILTER_MAX = 128): one entry family -- _f32, _plan, _workspace_bytes,
+ *   _i8_levels -- for every k, with the same arguments, statistics words and thread-local prior, tight bound and int8 cap.
+ *   Three LIST WIDTHS, chosen by k alone: 32 (k <= 32), 64 (33 .. 64), 128 (65 .. 128).  The MFMA kernels know no k and are the
+ *   same launches at every width; every kernel that carries a list (rescoring, scored rounds, exact scans and their merges)
+ *   is instantiated once per width (at 128 a wave's list holds two entries per lane).  Candidate lists are always plain at
+ *   width 128 (RAGRAPH_FILTER_SCORED is not honoured beyond k = 64).  Any other k is RAGRAPH_EINVAL (a size of 0, 0 int8
+ *   levels), another D RAGRAPH_EUNSUPPORTED (0, 0) -- checked before any pointer is touched.
+ *   The size query's FLOOR RULE: ragraph_topk_cosine_filtered_workspace_bytes(B, N, D, k) is never less than the same shape
+ *   needs at k = 32 when k > 32, nor than at k = 64 when k > 64 (a buffer sized for a call serves every shorter list of
+ *   the shape), and the call refuses exactly what is shorter than that query reports.  For k > 32 the query returns 0 for
+ *   every shape the call refuses (k > N, k > 128, B < 1); for k <= 32 it does not look at N, and reports a size where k > N.
+ *   (While each list width had entries of its own, the query for k <= 32 answered k > 128 with a size for a call that entry
+ *   refused; it returns 0 now.)  The sharded entry below stays at k <= 32: an exchange takes lists of up to 32 keys.
  *   Kb   bf16 copy of Kn made by ragraph_keys_to_bf16 (ragraph_keys_bf16_rows(N) rows x D, uint16 storage: the bf16 rows
  *        padded to a multiple of 256 keys, a tail row, the int8 rows, their tail row, the int8 copy's granule table, and
  *        256 rows of slack that the last stage of an int8 level may read).  The int8 rows come in two classes of granules
@@ -225,7 +238,9 @@ size_t ragraph_topk_cosine_filtered_stats_offset(size_t ws_bytes);
  * starts at 0).  Returns L, or a negative error code. */
 int ragraph_topk_cosine_filtered_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]);
 /* How many of that schedule's LAST levels run on the int8 copy (v_mfma_i32_16x16x64_i8: twice the bf16 rate, a ~5x wider
- * error bound, so ~3x the candidates -- the late levels of batches of >= 1024 queries at D = 128 / 256). */
+ * error bound, so ~3x the candidates -- the late levels of batches of >= 1024 queries at D = 128 / 256), under the calling
+ * thread's cap; 0 for a shape the call refuses.  Beyond k = 32 a level is planned for 1.3 k (end / previous end) <= 1024 candidates, an int8
+ * level for half that. */
 int ragraph_topk_cosine_filtered_i8_levels(int64_t B, int64_t N, int D, int k);
 /* Cap on the int8 levels of the CALLING THREAD's following filtered calls (thread-local; -1 = the built-in rule, 0 = none);
  * returns the previous value.  For callers that know their bank: the int8 bound is only as tight as the largest entries
@@ -264,32 +279,6 @@ float ragraph_topk_cosine_filtered_set_tight_prior(float t);
 int ragraph_topk_cosine_filtered_f32(const float* Q, int64_t B, const float* Kn, const float* Kp, const uint16_t* Kb,
                                      int64_t N, int D, int k, int64_t idx_base, float* out_scores, int64_t* out_idx,
                                      int* overflow, int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream);
-/* The same call for lists of 33 <= k <= min(N, 64) keys: the arguments, the result's bits, the statistics words (at the same
- * offset of the workspace as passed) and the calling thread's prior, tight bound and int8 cap of the entry above; the MFMA
- * kernels are the same launches, and every kernel that carries a list (rescoring, scored rounds, exact scans and their
- * merges) runs in its form for 64 winners.  One path per k: these entries return RAGRAPH_EINVAL for k <= 32 and k > 64 as
- * the entries above do for k > 32; another D is RAGRAPH_EUNSUPPORTED and a size of 0.  _wide_plan writes the seven words of
- * ragraph_topk_cosine_filtered_plan; _wide_workspace_bytes is the size the wide call needs (0 for a shape it refuses; never less
- * than ragraph_topk_cosine_filtered_workspace_bytes of the same shape at k = 32). */
-size_t ragraph_topk_cosine_filtered_wide_workspace_bytes(int64_t B, int64_t N, int D, int k);
-int ragraph_topk_cosine_filtered_wide_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]);
-int ragraph_topk_cosine_filtered_wide_f32(const float* Q, int64_t B, const float* Kn, const float* Kp, const uint16_t* Kb,
-                                          int64_t N, int D, int k, int64_t idx_base, float* out_scores, int64_t* out_idx,
-                                          int* overflow, int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream);
-/* Once more for lists of 65 <= k <= min(N, RAGRAPH_TOPK_FILTER_MAX = 128) keys: the same arguments, bits (those of
- * ragraph_topk_cosine_bank_f32, canonical order), statistics words and thread-local prior, tight bound and int8 cap; no read-back,
- * HIP-graph capturable.  The MFMA kernels are the same launches; the kernels that carry a list run in their form for 128 winners
- * (two entries of a wave's list per lane).  Candidate lists are always plain here (RAGRAPH_FILTER_SCORED is not honoured beyond
- * k = 64).  One path per k: RAGRAPH_EINVAL for k <= 64 and k > 128, RAGRAPH_EUNSUPPORTED and a size of 0 for another D -- before
- * any pointer is touched.  _wide128_workspace_bytes is never less than _wide_workspace_bytes of the same shape at k = 64. */
-size_t ragraph_topk_cosine_filtered_wide128_workspace_bytes(int64_t B, int64_t N, int D, int k);
-int ragraph_topk_cosine_filtered_wide128_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]);
-/* ... and how many of that plan's levels, the last ones, run on the int8 copy (the calling thread's cap applied; 0 for a shape
- * the entry refuses): a level is planned for 1.3 k (end / previous end) <= 1024 candidates, an int8 level for half that. */
-int ragraph_topk_cosine_filtered_wide128_i8_levels(int64_t B, int64_t N, int D, int k);
-int ragraph_topk_cosine_filtered_wide128_f32(const float* Q, int64_t B, const float* Kn, const float* Kp, const uint16_t* Kb,
-                                             int64_t N, int D, int k, int64_t idx_base, float* out_scores, int64_t* out_idx,
-                                             int* overflow, int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream);
 
 /* a1 over a ROW-SHARDED bank (one shard per GPU; the reference is single-GPU, so no reference line beyond the retrieval
  * itself -- SimilarityFunctions.py:6-16 + ToyGraphBase.py:66-67).  As ragraph_topk_cosine_filtered_f32 on this shard's

@@ -22,7 +22,7 @@ SO_PATH = os.environ.get("RAGRAPH_HIP_SO", os.path.join(CSRC, "libragraph_hip.so
 OK, EINVAL, EUNSUPPORTED, EWORKSPACE, EDEVICE = 0, -1, -2, -3, -4
 ACT_NONE, ACT_RELU, ACT_PRELU, ACT_LEAKY, ACT_ELU = 0, 1, 2, 3, 4
 TOPK_MAX = 64                # the fused kernels' list limit (RAGRAPH_TOPK_MAX)
-TOPK_FILTER_MAX = 128        # the filtered calls' (RAGRAPH_TOPK_FILTER_MAX: the wide128 entry)
+TOPK_FILTER_MAX = 128        # the filtered calls' (RAGRAPH_TOPK_FILTER_MAX: lists of 128 keys)
 TOPK_ORDERED_MAX = 4096      # ordered top-k over exact fp32 score slabs (RAGRAPH_TOPK_ORDERED_MAX)
 TOPK_TAIL_MAX = 65536        # rows one seeded tail pass takes (RAGRAPH_TOPK_TAIL_MAX)
 # plan[0] of ragraph_linear_plan (RAGRAPH_LINEAR_PLAN_*): the kernel ragraph_linear_f32 runs
@@ -62,15 +62,6 @@ SIGNATURES = {
     "ragraph_topk_cosine_filtered_max_i8_levels": (_i32, [_i32]),
     "ragraph_topk_cosine_filtered_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
                                                 _sz, _vp]),
-    "ragraph_topk_cosine_filtered_wide_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
-    "ragraph_topk_cosine_filtered_wide_plan": (_i32, [_i64, _i64, _i32, _i32, _vp]),
-    "ragraph_topk_cosine_filtered_wide_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
-                                                     _sz, _vp]),
-    "ragraph_topk_cosine_filtered_wide128_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
-    "ragraph_topk_cosine_filtered_wide128_plan": (_i32, [_i64, _i64, _i32, _i32, _vp]),
-    "ragraph_topk_cosine_filtered_wide128_i8_levels": (_i32, [_i64, _i64, _i32, _i32]),
-    "ragraph_topk_cosine_filtered_wide128_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
-                                                        _sz, _vp]),
     "ragraph_topk_cosine_filtered_sharded_f32": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp,
                                                         _vp, _sz, _vp, _i64, _vp, _vp, _vp, _i32]),
     "ragraph_topk_cosine_small_ok": (_i32, [_i64, _i64, _i32, _i32]),

@@ -24,10 +24,10 @@
 // a few queries into key slices); *overflow only counts those rows.  The call never synchronises and reads nothing back.
 // Levels may run on an int8 copy of the bank instead (v_mfma_i32_16x16x64_i8, integer thresholds: filter_common.h), whose
 // candidate lists can carry the integer score that admitted each key (SCORED: topk_rescore_scored_kernel).
-// Lists of 33 .. 64 keys (ragraph_topk_cosine_filtered_wide_f32): the same launches of the MFMA kernels, which know no k, and
-// the LW = 64 instantiations of the kernels that carry a list (filter_rescore.h, filter_verify_fixup.h).
-// Lists of 65 .. 128 keys (ragraph_topk_cosine_filtered_wide128_f32): their LW = 128 instantiations, in which a wave holds two
-// entries of a list per lane; plain lists only (filter_scored_lists refuses k > 64).
+// One entry, three list widths (filter_list_width(k)): the MFMA kernels know no k and are the same launches for every k; the
+// kernels that carry a list (filter_rescore.h, filter_verify_fixup.h) run in their LW = 32 instantiations for k <= 32, LW = 64
+// for 33 .. 64, and LW = 128 for 65 .. 128, in which a wave holds two entries of a list per lane; plain lists only there
+// (filter_scored_lists refuses k > 64).
 //
 // Two filter kernels share one bank layout (filter_common.h: MFMA fragment order of v_mfma_f32_16x16x32_bf16):
 // topk_filter_direct_kernel (topk_filter_direct.hip) for up to 256 queries, and this file's RING kernel above that:
@@ -320,7 +320,7 @@ struct FilterWs {
   float* theta;         // [B] the first bound
   int* overflow_list;   // [B] queries the final level sends to the exact fallback
   int* fix_done;        // [FILTER_FIX_MAX_Q] tickets, [.. x FILTER_FIX_SLICES x 32] partial winners of the sliced fallback scans
-                        // (the wide entry: half the slices x 64 winners, the same bytes; wide128: a quarter x 128)
+                        // (lists of 64: half the slices x 64 winners, the same bytes; lists of 128: a quarter x 128)
   float* fix_s;
   int64_t* fix_i;
   float* part_s;        // (B <= 64) sliced rescoring: [B][8][k] partial winners
@@ -364,16 +364,17 @@ static size_t filter_ws_carve(char* w, const FilterShape& in, const FilterCall& 
 
 // ---- the host queries: readers of the call plan ---------------------------------------------------------------------
 // The one argument check of the plan's readers and of the call: 0, or the error code of a shape no filtered call takes.
-// One path per k: the entries built for lists of 32 take 1 <= k <= 32, the WIDE entries (lists of 64: the LW = 64 instantiations
-// of the list-carrying kernels) take 33 <= k <= 64, the WIDE128 entries (LW = 128) 65 <= k <= 128.  lw: the entry's list width.
-static int filter_shape_code(int64_t B, int64_t N, int D, int k, int lw = 32) {
+static int filter_shape_code(int64_t B, int64_t N, int D, int k) {
   if (!filter_dim_ok(D)) return RAGRAPH_EUNSUPPORTED;
-  const bool k_ok = lw == 128 ? (k >= 65 && k <= 128) : (lw == 64 ? (k >= 33 && k <= 64) : (k >= 1 && k <= 32));
-  return B >= 1 && N >= 1 && k_ok && k <= N ? RAGRAPH_OK : RAGRAPH_EINVAL;
+  return B >= 1 && N >= 1 && k >= 1 && k <= RAGRAPH_TOPK_FILTER_MAX && k <= N ? RAGRAPH_OK : RAGRAPH_EINVAL;
 }
-#define RG_REQUIRE_FILTER_SHAPE(who, B, N, D, k, lw)                                                                  \
+// The list width a call of k keys runs at: the LW instantiation of the list-carrying kernels.
+static int filter_list_width(int k) {
+  return k <= 32 ? 32 : (k <= 64 ? 64 : 128);
+}
+#define RG_REQUIRE_FILTER_SHAPE(who, B, N, D, k)                                                                      \
   do {                                                                                                                \
-    const int code__ = filter_shape_code(B, N, D, k, lw);                                                             \
+    const int code__ = filter_shape_code(B, N, D, k);                                                                 \
     RG_REQUIRE(code__ != RAGRAPH_EUNSUPPORTED, RAGRAPH_EUNSUPPORTED, who ": D=%d not in {64,128,256}", D);           \
     RG_REQUIRE(code__ == RAGRAPH_OK, RAGRAPH_EINVAL, who ": bad B/N/k");                                              \
   } while (0)
@@ -407,18 +408,39 @@ static size_t filter_workspace_bytes(int64_t B, int64_t N, int D, int k, int n_s
   return filter_workspace_bytes(in, filter_schedule(in));
 }
 
-extern "C" size_t ragraph_topk_cosine_filtered_workspace_bytes(int64_t B, int64_t N, int D, int k) {
-  return filter_workspace_bytes(B, N, D, k, 1);
-}
-// The sharded entry plans for (plan_N, n_shards): its first sample can be another one than the single bank's of plan_N rows.
-extern "C" size_t ragraph_topk_cosine_filtered_sharded_workspace_bytes(int64_t B, int64_t plan_N, int D, int k, int n_shards) {
-  if (!filter_dim_ok(D)) return 0;  // (ragraph_topk_cosine_f32 alone takes other widths)
-  const size_t a = filter_workspace_bytes(B, plan_N, D, k, n_shards), b = filter_workspace_bytes(B, plan_N, D, k, 1);
-  const size_t c = ragraph_topk_cosine_workspace_bytes(B, plan_N, D, k);   // (a short shard's exact top-k)
-  const size_t ab = a > b ? a : b;  // (exchange = NULL runs the single-bank schedule)
-  return ab > c ? ab : c;
+// Everything an entry may be asked to hold -- what the size queries report and what filtered_entry insists on.  `own`: the size
+// of the single bank's schedule at this k (filter_workspace_bytes(B, plan_N, D, k, 1): the caller has it, or its schedule).
+// The floor rule: a list of 33 .. 128 keys needs no less than the same shape at k = 32 (a handful of queries keep 8 sub-lists
+// per query while 8 k <= 256 and 4 beyond: the lists alone would make k = 33 the smaller call), a list of 65 .. 128 no less
+// than at k = 64 -- a buffer sized for a call serves every shorter list of the same shape.  With an exchange: the schedule
+// of n_shards shards that pool their first sample (another level-0 scratch), and a short shard's exact top-k.
+static size_t filter_entry_bytes(size_t own, int64_t B, int64_t plan_N, int D, int k, int n_shards, bool exchange) {
+  size_t need = own;
+  auto at_least = [&](size_t bytes) {
+    if (bytes > need) need = bytes;
+  };
+  if (k > 32 && plan_N >= 32) at_least(filter_workspace_bytes(B, plan_N, D, 32, 1));
+  if (k > 64) at_least(filter_workspace_bytes(B, plan_N, D, 64, 1));
+  if (exchange) {
+    if (n_shards > 1) at_least(filter_workspace_bytes(B, plan_N, D, k, n_shards));
+    at_least(ragraph_topk_cosine_workspace_bytes(B, plan_N, D, k));
+  }
+  return need;
 }
 
+// (k <= 32 is answered without the shape check, as ever: a size also where k > N)
+extern "C" size_t ragraph_topk_cosine_filtered_workspace_bytes(int64_t B, int64_t N, int D, int k) {
+  if (k > 32 && filter_shape_code(B, N, D, k) != RAGRAPH_OK) return 0;
+  return filter_entry_bytes(filter_workspace_bytes(B, N, D, k, 1), B, N, D, k, 1, false);
+}
+// The sharded entry plans for (plan_N, n_shards): its first sample can be another one than the single bank's of plan_N rows
+// (exchange = NULL runs the single-bank schedule: the `own` term).
+extern "C" size_t ragraph_topk_cosine_filtered_sharded_workspace_bytes(int64_t B, int64_t plan_N, int D, int k, int n_shards) {
+  if (!filter_dim_ok(D)) return 0;  // (ragraph_topk_cosine_f32 alone takes other widths)
+  return filter_entry_bytes(filter_workspace_bytes(B, plan_N, D, k, 1), B, plan_N, D, k, n_shards, true);
+}
+
+// How many trailing levels of the plan run on the int8 copy, under the calling thread's cap (0 for a shape the entry refuses).
 extern "C" int ragraph_topk_cosine_filtered_i8_levels(int64_t B, int64_t N, int D, int k) {
   if (filter_shape_code(B, N, D, k) != RAGRAPH_OK) return 0;
   FilterShape in = filter_query_shape(B, N, D, k, 1, false);
@@ -427,9 +449,9 @@ extern "C" int ragraph_topk_cosine_filtered_i8_levels(int64_t B, int64_t N, int 
   return filter_call_plan(in, filter_schedule(in)).i8_levels;
 }
 
-static int filter_plan_query(int64_t B, int64_t N, int D, int k, int64_t plan[7], int lw) {
+extern "C" int ragraph_topk_cosine_filtered_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]) {
   RG_REQUIRE(plan, RAGRAPH_EINVAL, "topk_cosine_filtered_plan: null pointer");
-  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered_plan", B, N, D, k, lw);
+  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered_plan", B, N, D, k);
   FilterShape in = filter_query_shape(B, N, D, k, 1, false);
   filter_query_follow_tight(in);
   // (the plan of one whole bank IS its schedule: filter_schedule leaves such a bank bound_keys <= N / 4 or <= ends[0] < N / 2
@@ -442,44 +464,10 @@ static int filter_plan_query(int64_t B, int64_t N, int D, int k, int64_t plan[7]
   plan[6] = c.bound_keys;
   return c.nlev;
 }
-extern "C" int ragraph_topk_cosine_filtered_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]) {
-  return filter_plan_query(B, N, D, k, plan, 32);
-}
-// The wide entry's queries (33 <= k <= 64): the same plan words, the same workspace layout -- the lists of the fixup scan
-// keep their size (half the slices of twice the winners), every other buffer is sized by k as ever.
-extern "C" int ragraph_topk_cosine_filtered_wide_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]) {
-  return filter_plan_query(B, N, D, k, plan, 64);
-}
-extern "C" size_t ragraph_topk_cosine_filtered_wide_workspace_bytes(int64_t B, int64_t N, int D, int k) {
-  if (filter_shape_code(B, N, D, k, 64) != RAGRAPH_OK) return 0;
-  // never less than the same shape needs at k = 32 (a handful of queries keep 8 sub-lists per query while 8 k <= 256 and 4
-  // beyond: the lists alone would make k = 33 the smaller call): a buffer sized for a wide call serves every shorter list
-  const size_t own = filter_workspace_bytes(B, N, D, k, 1), narrow = N >= 32 ? filter_workspace_bytes(B, N, D, 32, 1) : 0;
-  return own > narrow ? own : narrow;
-}
-// The wide128 entry's queries (65 <= k <= 128): the same again -- the fixup scan keeps a quarter of the slices of four times
-// the winners; never less than the wide entry needs for the same shape at k = 64.
-extern "C" int ragraph_topk_cosine_filtered_wide128_plan(int64_t B, int64_t N, int D, int k, int64_t plan[7]) {
-  return filter_plan_query(B, N, D, k, plan, 128);
-}
-// How many trailing levels of that plan run on the int8 copy (under the calling thread's cap, like
-// ragraph_topk_cosine_filtered_i8_levels for k <= 32; 0 for a shape the entry refuses).
-extern "C" int ragraph_topk_cosine_filtered_wide128_i8_levels(int64_t B, int64_t N, int D, int k) {
-  if (filter_shape_code(B, N, D, k, 128) != RAGRAPH_OK) return 0;
-  FilterShape in = filter_query_shape(B, N, D, k, 1, false);
-  in.i8_cap = t_max_i8_levels;
-  filter_query_follow_tight(in);
-  return filter_call_plan(in, filter_schedule(in)).i8_levels;
-}
-extern "C" size_t ragraph_topk_cosine_filtered_wide128_workspace_bytes(int64_t B, int64_t N, int D, int k) {
-  if (filter_shape_code(B, N, D, k, 128) != RAGRAPH_OK) return 0;
-  const size_t own = filter_workspace_bytes(B, N, D, k, 1), wide = ragraph_topk_cosine_filtered_wide_workspace_bytes(B, N, D, 64);
-  return own > wide ? own : wide;
-}
 
 // Would a sharded call of this shape speculate under a prior?  (Any valid one: the answer is the plan's, not the value's.)
 extern "C" int ragraph_topk_cosine_filtered_sharded_speculates(int64_t B, int64_t plan_N, int D, int k, int n_shards) {
-  if (filter_shape_code(B, plan_N, D, k) != RAGRAPH_OK || n_shards < 1) return 0;
+  if (filter_shape_code(B, plan_N, D, k) != RAGRAPH_OK || k > 32 || n_shards < 1) return 0;   // (no exchange beyond 32 keys)
   FilterShape in = filter_query_shape(B, plan_N, D, k, n_shards, true);
   in.prior = 0.f;
   return filter_call_plan(in, filter_schedule(in)).spec ? 1 : 0;
@@ -736,7 +724,7 @@ static int run_rescore(const FilterWs& f, const float* Kn, int64_t N, int64_t B,
       break;
     case RESCORE_WIDE_COOP: RG_WIDE(false, true, dim3((unsigned)B), (float*)nullptr, (int*)nullptr); break;
     case RESCORE_WIDE: RG_WIDE(false, false, dim3((unsigned)B), (float*)nullptr, (int*)nullptr); break;
-    case RESCORE_COOP_FEW:   // (the later levels of a sharded bank: no wide128 call is sharded, and at this kernel's 128
+    case RESCORE_COOP_FEW:   // (the later levels of a sharded bank: no call of 65 .. 128 keys is sharded, and at this kernel's 128
                              // registers the two-entries-per-lane form would spill)
       if constexpr (LW <= 64) {
         RG_COOP(true);
@@ -1064,55 +1052,41 @@ static int run_filtered(const FilteredArgs& a, const FilterCall& c, const Filter
 
 // Steps 1 and 2 of a call: validate, plan, and hand the plan to whoever executes it.  The thread's prior and int8 cap and the
 // per-call switches are read here and nowhere else.  The schedule (its pow() search) is computed once for a single bank of
-// up to 32 keys a list; a shard among several that pool their first sample computes the pooled one as well -- for the size its
-// query reports, and again as the call's own; the wide entry one more (k = 32) and the wide128 entry two more (k = 32, 64) for
-// the sizes their queries cover.  filter_call_plan (cheap arithmetic) runs twice per size, once for the call.
-static int filtered_entry(const FilteredArgs& a, int lw = 32) {
+// up to 32 keys a list; filter_entry_bytes adds one for each floor (k > 32: k = 32; k > 64: k = 64) and, for a shard among
+// several that pool their first sample, the pooled one -- which that shard computes again as the call's own.
+// filter_call_plan (cheap arithmetic) runs twice per size, once for the call.
+template <int LW>
+static int run_filtered_dim(const FilteredArgs& a, const FilterCall& c, const FilterShape& in) {
+  if (a.D == 256) return run_filtered<256, LW>(a, c, in);
+  if (a.D == 128) return run_filtered<128, LW>(a, c, in);
+  return run_filtered<64, LW>(a, c, in);
+}
+static int filtered_entry(const FilteredArgs& a) {
   const int64_t B = a.B, N = a.N, plan_N = a.plan_N;
   const int D = a.D, k = a.k;
   RG_REQUIRE(a.Q && a.Kn && a.Kb && a.out_scores && a.out_idx && a.overflow && a.ws, RAGRAPH_EINVAL, "topk_cosine_filtered: null pointer");
   RG_REQUIRE(a.n_shards >= 1, RAGRAPH_EINVAL, "topk_cosine_filtered: n_shards=%d", a.n_shards);
-  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered", B, N, D, k, lw);
+  RG_REQUIRE_FILTER_SHAPE("topk_cosine_filtered", B, N, D, k);
   RG_REQUIRE(N < (int64_t)INT_MAX - 1024, RAGRAPH_EUNSUPPORTED, "topk_cosine_filtered: shard rows must fit int32");
   RG_REQUIRE(plan_N >= N && (a.exchange || plan_N - N <= 1024), RAGRAPH_EINVAL, "topk_cosine_filtered: plan_N must be the largest shard's size");
   RG_REQUIRE(!a.exchange || a.theta, RAGRAPH_EINVAL, "topk_cosine_filtered: an exchange needs the theta buffer");
   RG_REQUIRE(aligned16(a.Q) && aligned16(a.Kn) && aligned16(a.Kb) && aligned16(a.ws), RAGRAPH_EINVAL,
              "topk_cosine_filtered: pointers must be 16-B aligned");
   // every call owns at least what the single bank of plan_N rows needs; the schedule behind that size is this call's own
-  // unless the call is one of several shards that pool their first sample
+  // unless the call is one of several shards that pool their first sample.  An entry refuses whatever is shorter than its
+  // size query reports, whichever schedule this call runs: the same function answers both.
   const FilterShape one = filter_query_shape(B, plan_N, D, k, 1, false);
   const FilterSchedule sc_one = filter_schedule(one);
-  size_t need = filter_workspace_bytes(one, sc_one);
-  // an entry refuses whatever is shorter than ITS OWN size query reports, whichever schedule this call runs.  `need` is the
-  // "own" term of each of those queries; only their other terms are computed here: the wide entries' shorter lists of the same
-  // shape (one more schedule at k = 32, wide128 another at k = 64), the sharded entry's pooled schedule (n_shards > 1: one more)
-  // and a short shard's exact top-k (arithmetic).  The entry for k <= 32 without an exchange computes nothing more.
-  auto at_least = [&](size_t bytes) {
-    if (bytes > need) need = bytes;
-  };
-  if (lw >= 64 && plan_N >= 32) at_least(filter_workspace_bytes(B, plan_N, D, 32, 1));
-  if (lw == 128) at_least(filter_workspace_bytes(B, plan_N, D, 64, 1));
-  if (a.exchange) {
-    if (a.n_shards > 1) at_least(filter_workspace_bytes(B, plan_N, D, k, a.n_shards));
-    at_least(ragraph_topk_cosine_workspace_bytes(B, plan_N, D, k));
-  }
+  const size_t need = filter_entry_bytes(filter_workspace_bytes(one, sc_one), B, plan_N, D, k, a.n_shards, a.exchange != nullptr);
   RG_REQUIRE(a.ws_bytes >= need, RAGRAPH_EWORKSPACE, "topk_cosine_filtered: workspace %zu < %zu", a.ws_bytes, need);
   const FilterShape in{B, N, plan_N, D, k, a.n_shards, a.exchange != nullptr, t_prior, t_max_i8_levels, false, one.env, one.cus, t_tight};
   const FilterCall c = filter_call_plan(in, a.exchange && a.n_shards > 1 ? filter_schedule(in) : sc_one);
   if (c.exact_participant) return run_exact_participant(a, c);
-  if (lw == 128) {  // (single bank only, like the wide entry)
-    if (D == 256) return run_filtered<256, 128>(a, c, in);
-    if (D == 128) return run_filtered<128, 128>(a, c, in);
-    return run_filtered<64, 128>(a, c, in);
+  switch (filter_list_width(k)) {   // (widest first: the order the kernels are instantiated in, and so their labels, stays)
+    case 128: return run_filtered_dim<128>(a, c, in);
+    case 64: return run_filtered_dim<64>(a, c, in);
+    default: return run_filtered_dim<32>(a, c, in);
   }
-  if (lw == 64) {  // (single bank only: the wide entry has no exchange, so no exact participant either)
-    if (D == 256) return run_filtered<256, 64>(a, c, in);
-    if (D == 128) return run_filtered<128, 64>(a, c, in);
-    return run_filtered<64, 64>(a, c, in);
-  }
-  if (D == 256) return run_filtered<256, 32>(a, c, in);
-  if (D == 128) return run_filtered<128, 32>(a, c, in);
-  return run_filtered<64, 32>(a, c, in);
 }
 
 extern "C" int ragraph_topk_cosine_filtered_f32(const float* Q, int64_t B, const float* Kn, const float* Kp,
@@ -1123,33 +1097,14 @@ extern "C" int ragraph_topk_cosine_filtered_f32(const float* Q, int64_t B, const
                          N, nullptr, nullptr, nullptr, 1});
 }
 
-// Lists of 33 .. 64 keys: the same call -- schedule, statistics words, the thread's prior, tight bound and int8 cap -- through
-// the LW = 64 instantiations of the kernels that carry a list (rescoring, scored rounds, scans and their merges).  The MFMA
-// kernels compare against thresholds and append to lists: they are the same launches.
-extern "C" int ragraph_topk_cosine_filtered_wide_f32(const float* Q, int64_t B, const float* Kn, const float* Kp,
-                                                     const uint16_t* Kb, int64_t N, int D, int k, int64_t idx_base,
-                                                     float* out_scores, int64_t* out_idx, int* overflow,
-                                                     int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream) {
-  return filtered_entry({Q, B, Kn, Kp, Kb, N, D, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
-                         N, nullptr, nullptr, nullptr, 1}, 64);
-}
-
-// Lists of 65 .. 128 keys: the same call once more, through the LW = 128 instantiations -- a wave's list holds two entries per
-// lane (rescore_common.h, filter_rescore.h).  Plain lists only.
-extern "C" int ragraph_topk_cosine_filtered_wide128_f32(const float* Q, int64_t B, const float* Kn, const float* Kp,
-                                                        const uint16_t* Kb, int64_t N, int D, int k, int64_t idx_base,
-                                                        float* out_scores, int64_t* out_idx, int* overflow,
-                                                        int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream) {
-  return filtered_entry({Q, B, Kn, Kp, Kb, N, D, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
-                         N, nullptr, nullptr, nullptr, 1}, 128);
-}
-
 extern "C" int ragraph_topk_cosine_filtered_sharded_f32(const float* Q, int64_t B, const float* Kn, const float* Kp,
                                                         const uint16_t* Kb, int64_t N, int D, int k, int64_t idx_base,
                                                         float* out_scores, int64_t* out_idx, int* overflow,
                                                         int64_t* overflow_idx, void* ws, size_t ws_bytes, void* stream,
                                                         int64_t plan_N, float* theta, ragraph_exchange_fn exchange,
                                                         void* ctx, int n_shards) {
+  // (no exchange for lists of 33 .. 128 keys: this entry stays at the LW = 32 instantiations, with or without an exchange)
+  RG_REQUIRE(k <= 32, RAGRAPH_EINVAL, "topk_cosine_filtered_sharded: an exchange takes lists of up to 32 keys (k=%d)", k);
   return filtered_entry({Q, B, Kn, Kp, Kb, N, D, k, idx_base, out_scores, out_idx, overflow, overflow_idx, ws, ws_bytes, stream,
                          plan_N, theta, exchange, ctx, n_shards});
 }

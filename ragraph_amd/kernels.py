@@ -409,7 +409,7 @@ FILTER_MIN_B = int(os.environ.get("RAGRAPH_FILTER_MIN_B", "1"))  # banks of >= 6
 
 
 def filter_wide_helps(B: int, n_keys: int, D: int, k: int) -> bool:
-    """filter_helps for lists of 33 .. 64 keys (the wide entry behind topk_cosine_filtered): True where the filtered call is
+    """filter_helps for lists of 33 .. 64 keys (topk_cosine_filtered at its list width of 64): True where the filtered call is
     the faster way to the bits of topk_cosine, whose fp32 score slabs are all such a k had before.  Host arithmetic only."""
     if os.environ.get("RAGRAPH_EXACT_FP32") == "1":
         return False
@@ -436,7 +436,7 @@ def filter_wide_helps(B: int, n_keys: int, D: int, k: int) -> bool:
 
 
 def filter_wide128_helps(B: int, n_keys: int, D: int, k: int) -> bool:
-    """filter_helps for lists of 65 .. 128 keys (the wide128 entry behind topk_cosine_filtered): True where the filtered call is
+    """filter_helps for lists of 65 .. 128 keys (topk_cosine_filtered at its list width of 128): True where the filtered call is
     the faster way to the bits of topk_cosine, whose fp32 score slabs are all such a k had before.  Host arithmetic only."""
     if os.environ.get("RAGRAPH_EXACT_FP32") == "1":
         return False
@@ -507,15 +507,9 @@ def topk_cosine_filtered(q: torch.Tensor, keys_normalized: torch.Tensor, keys_bf
     scores = torch.empty((B, k), dtype=torch.float32, device=q.device)
     idx = torch.empty((B, k), dtype=torch.int64, device=q.device)
     overflow = torch.empty(1, dtype=torch.int32, device=q.device)
-    wide = exchange is None and 32 < k <= 64   # (lists of 33 .. 64 keys: the wide entry -- one path per k)
-    wide128 = exchange is None and 64 < k <= N.TOPK_FILTER_MAX   # (65 .. 128: the wide128 entry)
-    if wide128:
-        nbytes = L.ragraph_topk_cosine_filtered_wide128_workspace_bytes(B, max(plan_n, Nk), D, k)
-    elif wide:
-        nbytes = L.ragraph_topk_cosine_filtered_wide_workspace_bytes(B, max(plan_n, Nk), D, k)
-    elif exchange is None:
+    if exchange is None:   # (every k up to TOPK_FILTER_MAX: the entry picks its list width)
         nbytes = L.ragraph_topk_cosine_filtered_workspace_bytes(B, max(plan_n, Nk), D, k)
-    else:  # (the sharded schedule -- planned for (plan_n, n_shards) -- can need another level-0 scratch)
+    else:  # (the sharded schedule -- planned for (plan_n, n_shards) -- can need another level-0 scratch; k <= 32: the entry refuses more)
         nbytes = L.ragraph_topk_cosine_filtered_sharded_workspace_bytes(B, max(plan_n, Nk), D, k,
                                                                         int(getattr(exchange, "n_shards", 1)))
     if nbytes == 0:
@@ -524,10 +518,9 @@ def topk_cosine_filtered(q: torch.Tensor, keys_normalized: torch.Tensor, keys_bf
     off = L.ragraph_topk_cosine_filtered_stats_offset(ws.numel())
     stats = ws[off:off + 128].view(torch.int32)   # (32 words; valid until the next filtered call on this stream)
     if exchange is None:
-        entry = L.ragraph_topk_cosine_filtered_wide128_f32 if wide128 else (
-            L.ragraph_topk_cosine_filtered_wide_f32 if wide else L.ragraph_topk_cosine_filtered_f32)
-        N.check(entry(q.data_ptr(), B, kn.data_ptr(), kp, keys_bf16.data_ptr(), Nk, D, k, idx_base, scores.data_ptr(),
-                      idx.data_ptr(), overflow.data_ptr(), None, ws.data_ptr(), ws.numel(), _stream()),
+        N.check(L.ragraph_topk_cosine_filtered_f32(q.data_ptr(), B, kn.data_ptr(), kp, keys_bf16.data_ptr(), Nk, D, k, idx_base,
+                                                   scores.data_ptr(), idx.data_ptr(), overflow.data_ptr(), None, ws.data_ptr(),
+                                                   ws.numel(), _stream()),
                 "topk_cosine_filtered")
         return (scores, idx, overflow, stats) if return_stats else (scores, idx, overflow)
     theta = torch.empty(B, dtype=torch.float32, device=q.device)

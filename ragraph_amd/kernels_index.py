@@ -868,8 +868,9 @@ class KeyIndex:
             prior = self._prior_for(B, k)
             tight = self._tight_for(B, k, prior)
             s, i, over, stats, had_i8 = self._guarded(ops.topk_cosine_filtered, q, kn, k, prior, tight, idx_base=idx_base, keys_packed=self._packed)
-            # (did THIS call have int8 levels?  The plan answers for k <= 32, under the open cap the call ran with; a wide call under
-            # an open cap is taken to have had them: an overflowing bank then leaves int8 first and the filter at the next verdict)
+            # (did THIS call have int8 levels?  The plan is asked for k <= 32, under the open cap the call ran with; a call of more
+            # keys under an open cap is taken to have had them: an overflowing bank then leaves int8 first and the filter at the
+            # next verdict.  The plan answers for every k now, but asking it there would change when a bank is demoted: kept.)
             had_i8 = had_i8 and (k > 32 or ops.filtered_i8_levels(B, n_rows, D, k) > 0)
             self.last_tight = tight
             self._note_overflow(over, B, had_i8, stats, k)

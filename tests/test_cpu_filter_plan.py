@@ -177,11 +177,12 @@ def test_queries_refuse_what_the_call_refuses(lib):
     plan = (ctypes.c_int64 * 7)()
     assert lib.ragraph_topk_cosine_filtered_plan(16, 100000, 100, 10, plan) == N.EUNSUPPORTED
     assert N.last_error() == "topk_cosine_filtered_plan: D=100 not in {64,128,256}"
-    for bad in ((0, 100000, 256, 10), (16, 0, 256, 10), (16, 100000, 256, 0), (16, 100000, 256, 33), (16, 5, 256, 10)):
+    for bad in ((0, 100000, 256, 10), (16, 0, 256, 10), (16, 100000, 256, 0), (16, 100000, 256, 129), (16, 5, 256, 10)):
         assert lib.ragraph_topk_cosine_filtered_plan(*bad, plan) == N.EINVAL
         assert N.last_error() == "topk_cosine_filtered_plan: bad B/N/k"
         assert lib.ragraph_topk_cosine_filtered_i8_levels(*bad) == 0
         assert lib.ragraph_topk_cosine_filtered_sharded_speculates(*bad, 2) == 0
+    assert lib.ragraph_topk_cosine_filtered_sharded_speculates(16, 100000, 256, 33, 2) == 0   # (no exchange beyond 32 keys)
     assert lib.ragraph_topk_cosine_filtered_plan(16, 100000, 256, 10, None) == N.EINVAL
     assert lib.ragraph_topk_cosine_filtered_sharded_speculates(16, 100000, 256, 10, 0) == 0
     assert lib.ragraph_topk_cosine_filtered_workspace_bytes(16, 100000, 100, 10) == 0

@@ -1,4 +1,4 @@
-"""The filtered exact top-k for lists of 33 .. 64 keys (ragraph_topk_cosine_filtered_wide_f32 behind
+"""The filtered exact top-k for lists of 33 .. 64 keys (ragraph_topk_cosine_filtered_f32 at its list width of 64, behind
 kernels.topk_cosine_filtered): every result is held, bit for bit, to K.topk_cosine on the same tensors -- the fp32 score
 slabs, which existing tests hold to the oracle.  No tolerance anywhere."""
 import os
@@ -65,6 +65,23 @@ def test_no_prior_every_shape_matches_the_fp32_path(dev, B, N, D, k):
     assert w[0] == K.FILTER_STATS_MAGIC and w[14] == B and w[16] == 0, w[:24]
     assert torch.equal(i, i32) and torch.equal(s, s32)
     assert over == 0 and w[20] == 0, (over, w[:24])
+
+
+@pytest.mark.parametrize("k", (33, 64))
+@pytest.mark.parametrize("B,N,D", (DIRECT[0], RING[0]))
+def test_the_int8_level_query_answers_what_the_call_runs(dev, B, N, D, k):
+    """ragraph_topk_cosine_filtered_i8_levels for 33 .. 64 keys (no such query existed per list width): without a prior it is
+    the number of trailing int8 levels in the call's own statistics words, in both launch families."""
+    from ragraph_amd import kernels as K
+
+    kn, kb, q = _bank(dev, B, N, D)
+    s, i, over, w = _call(K, q, kn, kb, k)
+    ran = [dt for dt, _, _ in K.filter_stats_levels(w)]
+    assert len(ran) == w[1] >= 1, w[:24]
+    trailing = 0
+    while trailing < len(ran) and ran[len(ran) - 1 - trailing] == "int8":
+        trailing += 1
+    assert K.filtered_i8_levels(B, N, D, k) == trailing, (ran, w[:24])
 
 
 @pytest.mark.parametrize("k", KS)

@@ -1,4 +1,4 @@
-"""The filtered exact top-k for lists of 65 .. 128 keys (ragraph_topk_cosine_filtered_wide128_f32 behind
+"""The filtered exact top-k for lists of 65 .. 128 keys (ragraph_topk_cosine_filtered_f32 at its list width of 128, behind
 kernels.topk_cosine_filtered): every result is held, bit for bit, to K.topk_cosine on the same tensors -- the ordered large-k
 path over fp32 score slabs, which existing tests hold to the oracle.  No tolerance anywhere."""
 import pytest
@@ -64,7 +64,7 @@ def test_no_prior_every_shape_matches_the_fp32_path(dev, B, N, D, k):
 
 
 def test_the_scored_switch_changes_nothing(dev, monkeypatch):
-    """The plan refuses scored lists beyond k = 64 (tests/test_cpu_filter_wide128.py): with RAGRAPH_FILTER_SCORED=1 the call of
+    """The plan refuses scored lists beyond k = 64 (tests/test_cpu_filter_wide.py): with RAGRAPH_FILTER_SCORED=1 the call of
     the shape whose int8 levels would keep them runs on plain lists and is as exact."""
     from ragraph_amd import kernels as K
 

@@ -317,9 +317,7 @@ def _filtered(B, N, D, k, bank="random", zero_queries=False, exchange_shards=0, 
                 if level0 is not None:
                     L = K.N.lib()
                     plan = (ctypes.c_int64 * 7)()
-                    query = (L.ragraph_topk_cosine_filtered_wide128_plan if k > 64 else
-                             L.ragraph_topk_cosine_filtered_wide_plan if k > 32 else L.ragraph_topk_cosine_filtered_plan)
-                    assert query(B, N, D, k, plan) == len(levels) and plan[1] == level0, list(plan)
+                    assert L.ragraph_topk_cosine_filtered_plan(B, N, D, k, plan) == len(levels) and plan[1] == level0, list(plan)
                 spec, hard, tight_on, soft, repaired = out[5]
                 if not exchange_shards:
                     assert spec == (prior is not None) and tight_on == (tight is not None)
